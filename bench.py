@@ -8,7 +8,7 @@ keys the reset RNG): there is NO collective on the step path; torch.distributed 
 max-over-ranks of the timing.  Prints ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--vehicle hexa_arm|hexa|quad]
-                  [--mode graph|eager] [--repeats 5] [--preroll 4096] [--no-cpu-baseline] [--no-extras]
+                  [--mode graph|eager] [--repeats 5] [--preroll 4096] [--no-cpu-baseline] [--no-extras] [--dump-outputs DIR]
 
 Protocol:
   * pre-roll (outside every timed region, independent of --warmup): `--preroll` steps so that episodes are staggered and the
@@ -18,7 +18,10 @@ Protocol:
   * graph mode replays ONE hipGraph of min(K, 64) steps (plus one graph for the remainder), so every timed step is a graph
     launch and `launch_mode` says what ran; eager mode issues K plain launches;
   * `--gpus N` with no torchrun environment: this process starts the N ranks itself as CHILD processes (torch.distributed.run),
-    before it has touched torch or the GPU, and relays rank 0's line.
+    before it has touched torch or the GPU, and relays rank 0's line;
+  * `--dump-outputs DIR`: right after the last timed window (before anything else steps the env) rank 0 writes what the last timed step
+    returned as DIR/<name>.npy (dump_outputs below).  The env seed and the action ring are fixed, so the same arguments give the same
+    inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +37,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 GRAPH_CHUNK = 64       # most control steps captured per hipGraph (= action ring length)
+DUMP_BUDGET = 64 << 20 # bytes, every file --dump-outputs writes together
 BASELINE_METRIC = "env-steps/sec (whole node), hexacopter+arm waypoint task at 4096 envs/GPU"   # BASELINE.json
 REFERENCE_PYTHON_STEPS_PER_S = [424, 642]   # the reference's own step(), 1 core, LSODA, measured in the build container
 
@@ -58,7 +62,14 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group / timing plumbing only, with a no-op step (CPU test of --gpus N)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed windows, write the outputs of the last timed step (rank 0's envs) as DIR/<name>.npy, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the real step, not --dry-run")
+    return args
 
 
 # ---- --gpus N without a torchrun environment: start the ranks as child processes ------------------------------------------------
@@ -109,6 +120,50 @@ def make_actions(torch, kind, n, ring, device, seed, act_dim=4):
     a[..., 0] += 1.0
     a[..., 4:] *= 3.0
     return torch.max(torch.min(a, hi), lo).contiguous()
+
+
+def step_outputs(env):
+    """Host copies of what the env's last step() produced: obs, reward, done and info bits (what step() returns), and the episode-end
+    outputs it writes for the envs that finished in it (terminal obs, episode return and length; the other envs' rows of those buffers
+    are not written by that step and are zeroed here)."""
+    import torch
+
+    done = env.done != 0
+
+    def ended(t):
+        return torch.where(done.view(-1, *[1] * (t.dim() - 1)), t, torch.zeros_like(t))
+
+    out = {"obs": env.obs, "reward": env.reward, "done": env.done, "info_bits": env.info_bits,
+           "terminal_obs": ended(env.terminal_obs), "ep_return": ended(env.ep_return), "ep_len": ended(env.ep_len)}
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET, seed=0):
+    """Write each [N, ...] array as out_dir/<name>.npy: float32 / float64 arrays as they are, integer arrays as float64 (exact).  If all of
+    them would exceed `budget` bytes, the same fixed, seeded sample of rows (in ascending order) is taken from every array and its row
+    indices are written as env_index.npy.  Returns what was written, for the result line."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    assert all(a.shape[0] == n for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    row_bytes = sum(a.itemsize * int(np.prod(a.shape[1:])) for a in arrays.values())
+    header_bytes = 256 * (len(arrays) + 1)   # .npy headers: 128 bytes each in practice
+    os.makedirs(out_dir, exist_ok=True)
+    index_path = os.path.join(out_dir, "env_index.npy")
+    if n * row_bytes + header_bytes > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=(budget - header_bytes) // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["env_index"] = rows.astype(np.float64)
+    elif os.path.exists(index_path):         # left by an earlier, sampled dump into the same directory
+        os.remove(index_path)
+    total = 0
+    for k, a in arrays.items():
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    return {"dir": os.path.abspath(out_dir), "files": sorted(k + ".npy" for k in arrays), "rows": int(next(iter(arrays.values())).shape[0]),
+            "of_rows": int(n), "bytes": total}
 
 
 def cpu_baseline(args, amd, n):
@@ -274,6 +329,9 @@ def main_worker(args):
         barrier()                         # closes the bracket; its own latency (an RCCL all-reduce) is not part of any rank's K steps
         dev_ms = ev0.elapsed_time(ev1) if not dry else wall * 1e3
         windows.append((amd.sharding.max_over_ranks(dist, wall, device), dev_ms))
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the last timed step's outputs, before the isolated launches below step this env again
+        dumped = dump_outputs(args.dump_outputs, step_outputs(env))
     stats = env.stats()
     walls = sorted(w for w, _ in windows)
     wall = statistics.median(walls)
@@ -311,6 +369,8 @@ def main_worker(args):
         "episodes_finished_in_timed_windows_rank0": stats["episodes"],
         "episodes_finished_per_window_rank0": stats["episodes"] / max(1, len(windows)),
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if not dry:
         bytes_step = env.bytes_per_env_step
         # per-launch kernel duration, isolated: HIP events stamped by the kernel's own dispatch (hipExtLaunchKernelGGL start/stop events on
