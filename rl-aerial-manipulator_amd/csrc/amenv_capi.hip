@@ -30,6 +30,16 @@
 
 using namespace amenv_dev;
 
+// which step kernel amenv_step runs (select_step_family); amenv_rollout runs the family's own rollout kernel where it has one
+enum class StepFamily {
+  Lane,         // step_kernel: one lane per env
+  LaneHelper,   // step_kernel_pw: rigid vehicles at small batches, helper waves per tile (reset RNG words, observation rows, Monitor totals)
+  Quad,         // step_kernel_quad: rigid vehicles, 4 lanes per env (amenv_quad.hpp); opt-in
+  Team,         // step_kernel_team: z,x,x-arm vehicle in the latency regime, 16 lanes per env (amenv_team.hpp); fp64 = logic-gate build
+  Staged,       // step_kernel_armk: z,x,x-arm vehicle, four RK4 stage waves + a main wave per 64-env tile; fp64 = logic-gate build
+  TwoWave,      // step_kernel_arm2w: fp32 z,x,x-arm vehicle, main + helper wave per 64-env tile
+};
+
 struct amenv {
   amenv_config cfg;
   int device = -1;
@@ -40,14 +50,8 @@ struct amenv {
   uint32_t tile_bytes = 0;
   int n_tiles = 0;
   int block = 64;
-  bool quadk = false;              // rigid vehicles in the latency regime: lane-quad kernel (4 lanes per env, amenv_quad.hpp)
-  bool armk = false;               // hexacopter + z,x,x arm between the team kernel's range and the throughput regime: stage-wave kernel (step_kernel_armk)
-  bool arm2w = false;              // hexacopter + z,x,x arm at small batches: two-wave step kernel (amenv_kernels.hpp)
-  bool pwave = false;              // rigid vehicles at small batches: second wave per tile computes the reset RNG words (step_kernel_pw)
-  bool team = false;               // lane-team kernel (16 lanes per env): fp32 z,x,x-arm vehicle in the latency regime (amenv_team.hpp)
-  void* team_consts = nullptr;     // per-lane constants of the team kernels (amenv_team_host.hpp): float4 pieces, or plain doubles for the fp64 build
-  bool quad_ok = false;            // fp32 rigid vehicle with 4 or 6 rotors, single-waypoint v2 task: lane-quad kernels (step opt-in, closed-loop rollout)
-  bool team_ok = false;            // the configuration has a team kernel (fp32, 6 rotors, z,x,x arm): constants are allocated
+  StepFamily family = StepFamily::Lane;
+  void* team_consts = nullptr;     // per-lane constants of the team / quad kernels (amenv_team_host.hpp): float4 pieces, or plain doubles for the fp64 build
   uint32_t* pol_pack = nullptr;    // amenv_rollout_policy: policy parameters as MFMA fragments (re-packed on every call)
   // n-link arm with n < 3 (amenv_vehicle.n_joints = 1 or 2): inside, the vehicle is the 3-joint one with PHANTOM links behind the real ones (zero
   // mass / inertia / offset, joint limits 0 -> command 0, state 0: every term they add is an exact zero), so every kernel family serves it;
@@ -63,8 +67,6 @@ struct amenv {
 };
 
 static thread_local std::string g_create_err;
-constexpr int kTeamAutoMax = 6144;    // AUTO: lane-team arm kernel up to this batch (see amenv_create)
-constexpr int kArmkAutoMax = 32768;   // AUTO: stage-wave arm kernel up to this batch (see amenv_create)
 
 namespace {
 
@@ -236,6 +238,12 @@ HotParams<T, NR> make_hot(const amenv& e) {
   return P;
 }
 
+// joint axes other than (z, x, x): the kernels take the general-axes body, and only the lane kernel serves them
+bool generic_axes(const amenv_vehicle& v) {
+  const double zxx[9] = {0, 0, 1, 1, 0, 0, 1, 0, 0};
+  return std::memcmp(v.joint_axis, zxx, sizeof(zxx)) != 0;
+}
+
 template <typename T>
 ArmParams<T> make_arm(const amenv& e) {
   const amenv_vehicle& v = e.cfg.vehicle;
@@ -251,8 +259,7 @@ ArmParams<T> make_arm(const amenv& e) {
 
   }
   A.kp = T(v.joint_kp); A.kd = T(v.joint_kd); A.amax = T(v.joint_acc_max);
-  const double zxx[9] = {0, 0, 1, 1, 0, 0, 1, 0, 0};
-  A.generic_axes = std::memcmp(v.joint_axis, zxx, sizeof(zxx)) == 0 ? 0 : 1;
+  A.generic_axes = generic_axes(v) ? 1 : 0;
   A.mtot = T(v.mass); A.inv_mtot = T(1.0 / v.mass);
   for (int c = 0; c < 3; c++) {
     A.tool[c] = T(v.tool_offset[c]);
@@ -263,10 +270,16 @@ ArmParams<T> make_arm(const amenv& e) {
 }
 
 // per-lane constant table / wave-uniform parameters of the team kernels: amenv_team_host.hpp (shared with the host emulation of tests/emu)
-std::vector<float> team_table_f32(const amenv_config& c) { return team_const_table<float>(c, true); }
 template <typename T> TeamParamsT<T> make_team(const amenv& e) { return make_team_params<T>(e.cfg, e.team_consts); }
-// the device copy of the parameters behind the per-lane table (the step kernel's source; the other team kernels take them as arguments)
-template <typename T> hipError_t team_write_params(amenv* e) {
+// the per-lane table on the device (float4 pieces for fp32, plain doubles for the fp64 build); with_params: the team kernels' parameters
+// behind it (the step kernel's source; the other team kernels take them as arguments)
+template <typename T> hipError_t upload_team_consts(amenv* e, bool with_params) {
+  const std::vector<T> tc = team_const_table<T>(e->cfg, sizeof(T) == 4);
+  hipError_t s;
+  if ((s = hipMalloc(&e->team_consts, with_params ? team_block_bytes<T>() : tc.size() * sizeof(T))) != hipSuccess ||
+      (s = hipMemcpy(e->team_consts, tc.data(), tc.size() * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess)
+    return s;
+  if (!with_params) return hipSuccess;
   const TeamParamsT<T> P = make_team<T>(*e);
   return hipMemcpy(static_cast<char*>(e->team_consts) + team_table_bytes<T>(), &P, sizeof(P), hipMemcpyHostToDevice);
 }
@@ -333,95 +346,174 @@ const char* validate(const amenv_config* c) {
   return nullptr;
 }
 
+// The predicates below take the internal config: validated (an arm implies 6 rotors and the v2 task) and padded (an arm of 1 or 2 joints has
+// n_joints = 3, pad_arm_config).
+// z,x,x arm on the single-waypoint task: the team, stage-wave and two-wave kernels
+bool zxx_arm1(const amenv_config& c) { return c.vehicle.n_joints == 3 && !generic_axes(c.vehicle) && c.task.num_waypoints == 1; }
+// lane-quad kernels (step: opt-in; closed loop: amenv_rollout_policy): fp32 rigid vehicle with 4 or 6 rotors, single-waypoint v2 task, default workgroup size
+bool quad_ok(const amenv_config& c) {
+  return c.vehicle.n_joints == 0 && c.dtype == AMENV_F32 && (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6) && !is_v1(&c) && c.task.num_waypoints == 1 &&
+         c.block_size == 0;
+}
+// fp32 lane-team kernels (step, rollout, closed loop: amenv_rollout_policy)
+bool team_ok(const amenv_config& c) { return c.dtype == AMENV_F32 && zxx_arm1(c); }
+
+constexpr int kTeamAutoMax = 6144;    // AUTO: lane-team kernel up to this batch
+constexpr int kArmkAutoMax = 32768;   // AUTO: stage-wave kernel up to this batch
+
+// Which step kernel a config runs: amenv_config.step_kernel, or by batch size for AUTO (crossovers measured on MI355X).
+// Returns the refusal text when a requested kernel is not built for the config.
+const char* select_step_family(const amenv_config& c, StepFamily* out) {
+  const int want = c.step_kernel, n = c.num_envs;
+  const bool autok = want == AMENV_KERNEL_AUTO, f32 = c.dtype == AMENV_F32, arm = zxx_arm1(c);
+  StepFamily f = StepFamily::Lane;
+  // team vs stage-wave kernel: 5.96 vs 6.98 us at 6144 envs, 7.04 vs 6.99 at 7168 (profiles/r03/crossover_team_vs_stage_wave.txt)
+  if (arm && (want == AMENV_KERNEL_TEAM || (f32 && autok && n <= kTeamAutoMax)))
+    f = StepFamily::Team;
+  // stage-wave vs two-wave kernel: 9.3 vs 10.6 us at 32768 envs, behind from 53248; built for one RK4 sub-step (rk4_substeps = 1 only)
+  else if (arm && c.task.rk4_substeps == 1 && (want == AMENV_KERNEL_STAGED || (f32 && autok && n > kTeamAutoMax && n <= kArmkAutoMax)))
+    f = StepFamily::Staged;
+  // two-wave vs lane kernel: still ahead at 65536 envs, 18.0 vs 19.5 us
+  else if (arm && f32 && (want == AMENV_KERNEL_HELPER || (autok && n <= 65536)))
+    f = StepFamily::TwoWave;
+  // lane-quad kernel: opt-in only, it ties with the helper-wave kernel at small batches and loses above (profiles/r02/crossover_quad_vs_pw.txt)
+  else if (quad_ok(c) && want == AMENV_KERNEL_TEAM)
+    f = StepFamily::Quad;
+  // helper waves pay while the launch is latency-bound; the Monitor wave owns one of the kStatsReplicas replicas per tile
+  else if (c.vehicle.n_joints == 0 && c.block_size == 0 && (autok ? n <= 32768 : want == AMENV_KERNEL_HELPER && n <= 64 * kStatsReplicas))
+    f = StepFamily::LaneHelper;
+  if (f == StepFamily::Lane && want == AMENV_KERNEL_HELPER)
+    return "AMENV_KERNEL_HELPER is built for fp32 z,x,x-arm vehicles and for rigid vehicles with block_size = 0 "
+           "and at most 65536 envs (its Monitor wave owns one of the 1024 replicas of the running totals per tile)";
+  if (f == StepFamily::Lane && want == AMENV_KERNEL_TEAM)
+    return "AMENV_KERNEL_TEAM is built for the 6-rotor vehicle with the z,x,x arm (16 lanes per env; fp64 = logic-gate build) and for "
+           "fp32 rigid vehicles with 4 or 6 rotors, the single-waypoint v2 task and block_size = 0 (4 lanes per env)";
+  if (f == StepFamily::Lane && want == AMENV_KERNEL_STAGED)
+    return "AMENV_KERNEL_STAGED is built for the 6-rotor vehicle with the z,x,x arm (fp64 = logic-gate build), the single-waypoint v2 task "
+           "and rk4_substeps = 1";
+  *out = f;
+  return nullptr;
+}
+
+// amenv_kernel_name: tests, tools/ and bench.py match substrings of it
+std::string kernel_name(const amenv& e) {
+  const amenv_config& c = e.cfg;
+  const char* t = c.dtype == AMENV_F64 ? "double" : "float";
+  const int nrot = (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6) ? c.vehicle.n_rotors : AMENV_MAX_ROTORS;
+  const int kw = is_v1(&c) ? 2 : (c.task.num_waypoints == 1 ? 1 : AMENV_MAX_WAYPOINTS);
+  char buf[200] = "";
+  switch (e.family) {
+    case StepFamily::Lane:
+      std::snprintf(buf, sizeof(buf), "step_kernel<%s,NROT=%d,KW=%d,%s> block=%d", t, nrot, kw, c.vehicle.n_joints ? "v2+arm3" : (is_v1(&c) ? "v1" : "v2"), e.block); break;
+    case StepFamily::LaneHelper:
+      std::snprintf(buf, sizeof(buf), "step_kernel_pw<%s,NROT=%d,KW=%d,%s> (main wave + reset wave [+ observation wave + Monitor wave] per 64-env tile)", t, nrot, kw,
+                    is_v1(&c) ? "v1" : "v2"); break;
+    case StepFamily::Quad:
+      std::snprintf(buf, sizeof(buf), "step_kernel_quad<NROT=%d,v2> (4 lanes per env, 16 envs per wave + episode-end helper wave)", c.vehicle.n_rotors); break;
+    case StepFamily::Team:
+      std::snprintf(buf, sizeof(buf), "step_kernel_team<%s,NROT=6,v2+arm3> (16 lanes per env: 4 RK4 stages x 4 components, 4 envs per wave + episode-end helper wave)", t); break;
+    case StepFamily::Staged:
+      std::snprintf(buf, sizeof(buf), "step_kernel_armk<%s,NROT=6> block=320 (4 RK4 stage waves + main wave per 64-env tile)", t); break;
+    case StepFamily::TwoWave:
+      std::snprintf(buf, sizeof(buf), "step_kernel_arm2w<float,NROT=6> block=128 (2 waves per 64-env tile)"); break;
+  }
+  std::string name = buf;
+  if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
+  return name;
+}
+
+// one kernel launch; timed: stamped at dispatch and completion with amenv_step_timed's events
+template <typename... P, typename... A>
+hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  if (timed) hipExtLaunchKernelGGL(k, grid, block, lds, s, e.ev_start, e.ev_stop, 0, args...);
+  else hipLaunchKernelGGL(k, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+
+// amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
+// runs the lane kernel
+template <typename T, int NROT, int KW, int VAR, int NJ>
+hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
+  const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
+  const ColdParams C = make_cold(e);
+  const uint32_t tb = e.tile_bytes;
+  const int32_t n = e.cfg.num_envs;
+  switch (e.family) {
+    case StepFamily::Team:   // one wave per 4 envs; the fp64 build is a logic gate of amenv_step only (amenv_rollout refuses it)
+      if constexpr (NJ == 3 && sizeof(T) == 4)
+        return launch(e, false, rollout_kernel_team<NROT>, dim3(e.n_tiles * 16), dim3(64), 0, s, e.blob, tb, n, reinterpret_cast<const float*>(io.actions), io.obs,
+                      static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, make_team<T>(e));
+      return hipErrorInvalidValue;
+    case StepFamily::Quad:   // one wave per 16 envs
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6))
+        return launch(e, false, rollout_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(64), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
+                      io.info, T_steps, tl, C, make_quad(e));
+      return hipErrorInvalidValue;
+    case StepFamily::Lane: case StepFamily::LaneHelper: case StepFamily::Staged: case StepFamily::TwoWave:
+      break;
+  }
+  ArmArg<T, NJ> AA;
+  if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
+  const int bs = e.block;
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s, e.blob,
+                tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA);
+}
+
+// amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
+// if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
 template <typename T, int NROT, int KW, int VAR, int NJ = 0>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
   const ColdParams C = make_cold(e);
-  const int bs = e.block, n_pad = e.n_tiles * 64;
-  const dim3 grid((n_pad + bs - 1) / bs), block(bs);
-  const size_t lds = size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float);
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const uint32_t tb = e.tile_bytes;
   const int32_t n = e.cfg.num_envs;
-  if constexpr (NJ == 3) {
-    if (e.team) {    // 16 lanes per env, 4 envs per workgroup (step: main wave + episode-end helper wave; rollout: one wave); fp64 = logic-gate build, step only
-      const dim3 g2(e.n_tiles * 16), b2(64), b2s(128);
-      const TeamParamsT<T> TP = make_team<T>(e);
-      const float* act = reinterpret_cast<const float*>(io.actions);
-      if (T_steps > 0) {
-        if constexpr (sizeof(T) == 4) {
-          hipLaunchKernelGGL((rollout_kernel_team<NROT>), g2, b2, 0, s, e.blob, tb, n, act, io.obs, static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, TP);
-          return hipGetLastError();
-        } else {
-          return hipErrorInvalidValue;   // (amenv_rollout refuses the fp64 team build before it gets here)
+  switch (e.family) {
+    case StepFamily::Team:   // 16 lanes per env, 4 envs per workgroup: main wave + episode-end helper wave
+      if constexpr (NJ == 3) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
+        const TeamParamsT<T> TP = make_team<T>(e);
+        return launch(e, timed, step_kernel_team<T, NROT>, dim3(e.n_tiles * 16), dim3(128), 0, s, e.blob, n, int32_t(e.n_tiles * 16),
+                      reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
+      }
+      break;
+    case StepFamily::Staged:   // one tile per 320-thread workgroup: four stage waves + main wave
+      if constexpr (NJ == 3) {
+        if constexpr (sizeof(T) == 8) {   // the fp64 logic-gate build exchanges its aggregates in fp64: > 64 KB of dynamic LDS needs the attribute
+          hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel_armk<T, NROT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+          if (ea != hipSuccess) return ea;
         }
+        const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + 12 * 64) * sizeof(float) + size_t((4 * kAggSlots + 6) * 64) * sizeof(T);   // obs rows | reset words | aggregates, joints (T)
+        return launch(e, timed, step_kernel_armk<T, NROT>, dim3(e.n_tiles), dim3(320), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
       }
-      const int32_t nb = int32_t(g2.x);   // (the step kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
-      if (timed) hipExtLaunchKernelGGL((step_kernel_team<T, NROT>), g2, b2s, 0, s, e.ev_start, e.ev_stop, 0, e.blob, n, nb, act, TP.consts, io.obs, static_cast<T*>(io.reward), io.done,
-                                       io.info, tl, C);
-      else hipLaunchKernelGGL((step_kernel_team<T, NROT>), g2, b2s, 0, s, e.blob, n, nb, act, TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (NJ == 3) {
-    if (T_steps == 0 && e.armk) {
-      if constexpr (sizeof(T) == 8) {   // the fp64 logic-gate build exchanges its aggregates in fp64: > 64 KB of dynamic LDS needs the attribute
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel_armk<T, NROT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (ea != hipSuccess) return ea;
-      }    // one tile per 320-thread workgroup: four stage waves + main wave
-      const dim3 g2(e.n_tiles), b2(320);
-      const size_t lds2 = size_t(64 * ObsDim<VAR, NJ>::value + 12 * 64) * sizeof(float) + size_t((4 * kAggSlots + 6) * 64) * sizeof(T);   // obs rows | reset words | aggregates, joints (T)
-      if (timed) hipExtLaunchKernelGGL((step_kernel_armk<T, NROT>), g2, b2, lds2, s, e.ev_start, e.ev_stop, 0, e.blob, tb, n, io.actions, io.obs, io.reward,
-                                       io.done, io.info, tl, P, C, AA);
-      else hipLaunchKernelGGL((step_kernel_armk<T, NROT>), g2, b2, lds2, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (NJ == 3 && sizeof(T) == 4) {
-    if (T_steps == 0 && e.arm2w) {   // one tile per 128-thread workgroup: main + helper wave
-      const dim3 g2(e.n_tiles), b2(128);
-      const size_t lds2 = size_t(64 * ObsDim<VAR, NJ>::value + (kArmXchgSlots + 12) * 64) * sizeof(float);   // obs rows | RK4 exchange | reset words
-      if (timed) hipExtLaunchKernelGGL((step_kernel_arm2w<T, NROT>), g2, b2, lds2, s, e.ev_start, e.ev_stop, 0, e.blob, tb, n, io.actions, io.obs, io.reward,
-                                       io.done, io.info, tl, P, C, AA);
-      else hipLaunchKernelGGL((step_kernel_arm2w<T, NROT>), g2, b2, lds2, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6)) {
-    if (e.quadk) {   // 4 lanes per env, 16 envs per workgroup (step: main wave + episode-end helper wave; rollout: one wave)
-      const dim3 g2(e.n_tiles * 4), b1(64), b2(128);
-      const QuadParams QP = make_quad(e);
-      if (T_steps > 0) {
-        hipLaunchKernelGGL((rollout_kernel_quad<NROT>), g2, b1, 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, QP);
-        return hipGetLastError();
+      break;
+    case StepFamily::TwoWave:   // one tile per 128-thread workgroup: main + helper wave
+      if constexpr (NJ == 3 && sizeof(T) == 4) {
+        const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + (kArmXchgSlots + 12) * 64) * sizeof(float);   // obs rows | RK4 exchange | reset words
+        return launch(e, timed, step_kernel_arm2w<T, NROT>, dim3(e.n_tiles), dim3(128), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
       }
-      if (timed) hipExtLaunchKernelGGL((step_kernel_quad<NROT>), g2, b2, 0, s, e.ev_start, e.ev_stop, 0, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
-                                       io.info, tl, C, QP);
-      else hipLaunchKernelGGL((step_kernel_quad<NROT>), g2, b2, 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done, io.info, tl, C, QP);
-      return hipGetLastError();
+      break;
+    case StepFamily::Quad:   // 4 lanes per env, 16 envs per workgroup: main wave + episode-end helper wave
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6))
+        return launch(e, timed, step_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(128), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
+                      io.info, tl, C, make_quad(e));
+      break;
+    case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
+      if constexpr (NJ == 0) {
+        const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions, io.obs,
+                      io.reward, io.done, io.info, tl, P, C);
+      }
+      break;
+    case StepFamily::Lane: {
+      const int bs = e.block;
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
     }
   }
-  if constexpr (NJ == 0) {
-    if (T_steps == 0 && e.pwave) {   // one tile per 128-thread workgroup: main wave + reset-RNG wave
-      const dim3 g2(e.n_tiles), b2((KW == 1 && VAR == VAR_V2) ? 256 : 128);   // + observation and Monitor waves for the single-waypoint v2 task
-      const size_t lds2 = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
-      if (timed) hipExtLaunchKernelGGL((step_kernel_pw<T, NROT, KW, VAR>), g2, b2, lds2, s, e.ev_start, e.ev_stop, 0, e.blob, tb, n, io.actions, io.obs, io.reward,
-                                       io.done, io.info, tl, P, C);
-      else hipLaunchKernelGGL((step_kernel_pw<T, NROT, KW, VAR>), g2, b2, lds2, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C);
-      return hipGetLastError();
-    }
-  }
-  if (T_steps > 0) {
-    hipLaunchKernelGGL((rollout_kernel<T, NROT, KW, VAR, NJ>), grid, block, lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, P, C, AA);
-  } else if (timed) {  // same kernel, launched with dispatch-stamped start/stop events
-    hipExtLaunchKernelGGL((step_kernel<T, NROT, KW, VAR, NJ>), grid, block, lds, s, e.ev_start, e.ev_stop, 0, e.blob, tb, n, io.actions, io.obs, io.reward, io.done,
-                          io.info, tl, P, C, AA);
-  } else {
-    hipLaunchKernelGGL((step_kernel<T, NROT, KW, VAR, NJ>), grid, block, lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
-  }
-  return hipGetLastError();
+  return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
 template <typename T, int NROT>
@@ -606,6 +698,11 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
   if (!out) return fail(nullptr, AMENV_ERR_INVALID, "amenv_create: out is NULL");
   *out = nullptr;
   if (const char* why = validate(cfg)) return fail(nullptr, AMENV_ERR_INVALID, std::string("amenv_create: ") + why);
+  const amenv_config user_cfg = *cfg;                       // the caller's dimensions (obs / action / state fields)
+  const int pub_nj = user_cfg.vehicle.n_joints;
+  const amenv_config icfg = (pub_nj == 1 || pub_nj == 2) ? pad_arm_config(user_cfg) : user_cfg;   // the (internal) vehicle the kernels run
+  StepFamily family;
+  if (const char* why = select_step_family(icfg, &family)) return fail(nullptr, AMENV_ERR_INVALID, std::string("amenv_create: ") + why);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, AMENV_ERR_NO_DEVICE, "amenv_create: no HIP device visible (this library has no CPU path)");
@@ -616,9 +713,9 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
     return fail(nullptr, AMENV_ERR_NO_DEVICE, std::string("amenv_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
   amenv* e = new (std::nothrow) amenv();
   if (!e) return fail(nullptr, AMENV_ERR_ALLOC, "amenv_create: out of host memory");
-  const amenv_config user_cfg = *cfg;                       // the caller's dimensions (obs / action / state fields)
-  e->pub_nj = user_cfg.vehicle.n_joints;
-  e->cfg = (e->pub_nj == 1 || e->pub_nj == 2) ? pad_arm_config(user_cfg) : user_cfg;
+  e->pub_nj = pub_nj;
+  e->cfg = icfg;
+  e->family = family;
   cfg = &e->cfg;                                            // everything below sets up the (internal) vehicle the kernels run
   e->device = device;
   e->nf = n_float_fields(&user_cfg);
@@ -633,6 +730,14 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
   // latency regime (few waves per CU): one wave per workgroup spreads the waves over more CUs;
   // throughput regime: 256-thread workgroups
   e->block = cfg->block_size ? cfg->block_size : (cfg->num_envs <= 65536 ? 64 : 256);
+  e->obs_dim = obs_dim_of(&user_cfg);
+  e->act_dim = act_dim_of(&user_cfg);
+  e->kname = kernel_name(*e);
+  auto alloc_failed = [e](const char* what, hipError_t s) {
+    const std::string msg = std::string("amenv_create: ") + what + ": " + hipGetErrorString(s);
+    amenv_destroy(e);
+    return fail(nullptr, AMENV_ERR_ALLOC, msg);
+  };
   DeviceGuard g(device);
   hipError_t s;
   if ((s = hipMalloc(&e->blob, e->blob_bytes)) != hipSuccess ||
@@ -641,135 +746,20 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
       (s = hipMemset(e->stats, 0, sizeof(unsigned long long) * kStatsWords)) != hipSuccess ||
       // give the padding lanes of the last tile a valid state (real envs stay untouched: episode 0)
       (s = (cfg->dtype == AMENV_F64 ? launch_reset<double>(*e, nullptr, nullptr, 1, nullptr) : launch_reset<float>(*e, nullptr, nullptr, 1, nullptr))) != hipSuccess ||
-      (s = hipDeviceSynchronize()) != hipSuccess) {
-    std::string msg = std::string("amenv_create: device allocation failed: ") + hipGetErrorString(s);
-    amenv_destroy(e);
-    return fail(nullptr, AMENV_ERR_ALLOC, msg);
+      (s = hipDeviceSynchronize()) != hipSuccess)
+    return alloc_failed("device allocation failed", s);
+  // the lane-quad / fp32 lane-team constants (every kernel of theirs: step, rollout, closed-loop rollout) + the packed policy of amenv_rollout_policy
+  const bool quad = quad_ok(*cfg), team = team_ok(*cfg);
+  if (quad || team) {
+    if ((s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) return alloc_failed(quad ? "quad constants" : "policy pack", s);
+    if ((s = upload_team_consts<float>(e, team)) != hipSuccess) return alloc_failed(quad ? "quad constants" : "team constants", s);
   }
-  // Kernel choice (amenv_config.step_kernel; AUTO by batch size).  HELPER variants exist for fp32 z,x,x-arm vehicles (two-wave kernel:
-  // measured faster up to 65536 envs, 18.0 vs 19.5 us there) and for rigid vehicles with the default workgroup size (reset-RNG /
-  // observation helper waves: faster while the launch is latency-bound, up to 32768 envs).
-  const int want = cfg->step_kernel;
-  if (cfg->vehicle.n_joints == 3 && cfg->dtype == AMENV_F32) {
-    const ArmParams<float> ap = make_arm<float>(*e);
-    e->arm2w = !ap.generic_axes && cfg->task.num_waypoints == 1 && (want == AMENV_KERNEL_AUTO ? cfg->num_envs <= 65536 : want == AMENV_KERNEL_HELPER);
-  }
-  if (cfg->vehicle.n_joints == 0 && cfg->block_size == 0)
-    e->pwave = want == AMENV_KERNEL_AUTO ? cfg->num_envs <= 32768 : (want == AMENV_KERNEL_HELPER && cfg->num_envs <= 64 * kStatsReplicas);
-  if (want == AMENV_KERNEL_HELPER && !e->arm2w && !e->pwave) {
-    amenv_destroy(e);
-    return fail(nullptr, AMENV_ERR_INVALID, "amenv_create: AMENV_KERNEL_HELPER is built for fp32 z,x,x-arm vehicles and for rigid vehicles with block_size = 0 "
-                "and at most 65536 envs (its Monitor wave owns one of the 1024 replicas of the running totals per tile)");
-  }
-  // lane-team kernel (16 lanes per env): one wavefront per SIMD up to 4096 envs; measured against the two-wave kernel on MI355X:
-  // 4.9 vs 7.5 us at 2048 envs, 5.1 vs 7.6 at 4096, 7.5 vs 7.7 at 6144, 11.4 vs 7.8 at 8192 (a team workgroup is a main wave + an
-  // episode-end helper wave: above 4096 envs the SIMDs hold more than two waves) -> AUTO up to 6144 envs with the body-parallel RK4.  With the
-  // stage-parallel RK4 (tools/gpu_cross2.sh; against the stage-wave kernel): 4.69 vs 6.91 us at 4096 envs, 6.39 vs 6.96 at 5120, 6.64 vs 6.96 at 6144,
-  // 6.71 vs 7.01 at 7168, 6.81 vs 7.07 at 8192 (two main waves per SIMD), 10.3 vs 7.2 at 10240 -> AUTO up to 8192 envs.  Round 3 (the rewritten kernel
-  // keeps its per-lane constants and all loads in flight in registers: 155 VGPRs = three wavefronts per SIMD, profiles/r03/crossover_team_vs_stage_wave.txt):
-  // 4.51 vs 6.93 us at 4096 envs, 5.47 vs 6.94 at 5120, 5.96 vs 6.98 at 6144, 7.04 vs 6.99 at 7168, 8.06 vs 7.04 at 8192 -> AUTO up to 6144 envs
-  if (cfg->vehicle.n_joints == 3 && cfg->dtype == AMENV_F32 && cfg->vehicle.n_rotors == 6 && !make_arm<float>(*e).generic_axes && cfg->task.num_waypoints == 1)
-    e->team = want == AMENV_KERNEL_AUTO ? cfg->num_envs <= kTeamAutoMax : want == AMENV_KERNEL_TEAM;
-  // fp64 logic-gate build of the SAME kernel (DPP on register pairs): opt-in only, amenv_step only
-  if (cfg->vehicle.n_joints == 3 && cfg->dtype == AMENV_F64 && cfg->vehicle.n_rotors == 6 && !make_arm<double>(*e).generic_axes && cfg->task.num_waypoints == 1 &&
-      want == AMENV_KERNEL_TEAM)
-    e->team = true;
-  // lane-quad kernel (4 lanes per env) for the rigid vehicles: fp32, 4 or 6 rotors, single-waypoint v2 task, default workgroup size
-  const bool quad_ok = cfg->vehicle.n_joints == 0 && cfg->dtype == AMENV_F32 && (cfg->vehicle.n_rotors == 4 || cfg->vehicle.n_rotors == 6) && !is_v1(cfg) &&
-                       cfg->task.num_waypoints == 1 && cfg->block_size == 0;
-  // Opt-in only (AMENV_KERNEL_TEAM), never AUTO: measured on MI355X (tools/gpu_quad.sh, profiles/r02/crossover_quad_vs_pw.txt) it ties with the
-  // helper-wave kernel where the launch is latency-bound (2.85 vs 2.86 us at 1024 envs, 2.98 vs 3.00 at 4096) and loses above (3.3 vs 3.2 us at
-  // 8192, 5.3 vs 4.3 at 32768: four times the wavefronts): at these sizes the rigid step sits on the dependent-launch floor (1.7 us) plus one
-  // load -> compute -> store round trip of memory latency, and an instruction stream half as long changes nothing.
-  e->quad_ok = quad_ok;
-  e->quadk = quad_ok && want == AMENV_KERNEL_TEAM;
-  if (e->quadk) e->pwave = false;
-  if (want == AMENV_KERNEL_TEAM && !e->team && !e->quadk) {
-    amenv_destroy(e);
-    return fail(nullptr, AMENV_ERR_INVALID, "amenv_create: AMENV_KERNEL_TEAM is built for the 6-rotor vehicle with the z,x,x arm (16 lanes per env; fp64 = logic-gate build) and for "
-                "fp32 rigid vehicles with 4 or 6 rotors, the single-waypoint v2 task and block_size = 0 (4 lanes per env)");
-  }
-  e->team_ok = cfg->vehicle.n_joints == 3 && cfg->dtype == AMENV_F32 && cfg->vehicle.n_rotors == 6 && !make_arm<float>(*e).generic_axes &&
-               !is_v1(cfg) && cfg->task.num_waypoints == 1;
-  // stage-wave kernel (four RK4 stage waves + a main wave per 64-env tile): the fp32 6-rotor vehicle with the z,x,x arm, single-waypoint v2
-  // task, one RK4 sub-step
-  const bool armk_ok = e->team_ok && cfg->task.rk4_substeps == 1;
-  // measured on MI355X (tools/gpu_armk.sh, gpu_armk2.sh): 7.0 vs 7.8 us (two-wave kernel) at 6400 envs, 7.4 vs 8.1 at 12288, 9.0 vs 10.2 at 24576, 9.3 vs
-  // 10.6 at 32768; level from 36864 (10.6 vs 10.8) to 49152; a CU holds three of its workgroups (49 KB of LDS each), so above 49152 envs the
-  // launch takes a second round of workgroups: 14.4 vs 11.8 us at 53248
-  e->armk = armk_ok && (want == AMENV_KERNEL_AUTO ? (cfg->num_envs > kTeamAutoMax && cfg->num_envs <= kArmkAutoMax) : want == AMENV_KERNEL_STAGED);
-  // fp64 logic-gate build of the SAME kernel (aggregates exchanged in fp64 through LDS): opt-in only
-  if (cfg->dtype == AMENV_F64 && cfg->vehicle.n_joints == 3 && cfg->vehicle.n_rotors == 6 && !make_arm<double>(*e).generic_axes && !is_v1(cfg) &&
-      cfg->task.num_waypoints == 1 && cfg->task.rk4_substeps == 1 && want == AMENV_KERNEL_STAGED)
-    e->armk = true;
-  if (want == AMENV_KERNEL_STAGED && !e->armk) {
-    amenv_destroy(e);
-    return fail(nullptr, AMENV_ERR_INVALID, "amenv_create: AMENV_KERNEL_STAGED is built for the 6-rotor vehicle with the z,x,x arm (fp64 = logic-gate build), the single-waypoint v2 task "
-                "and rk4_substeps = 1");
-  }
-  if (e->team || e->armk) e->arm2w = false;
-  if (e->quad_ok) {    // the lane-quad kernels' constants (step kernel: opt-in; closed-loop rollout: amenv_rollout_policy) + the packed policy
-    const std::vector<float> tc = team_table_f32(*cfg);
-    if ((s = hipMalloc((void**)&e->team_consts, tc.size() * sizeof(float))) != hipSuccess ||
-        (s = hipMemcpy(e->team_consts, tc.data(), tc.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-        (s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) {
-      std::string msg = std::string("amenv_create: quad constants: ") + hipGetErrorString(s);
-      amenv_destroy(e);
-      return fail(nullptr, AMENV_ERR_ALLOC, msg);
-    }
-  }
-  if (e->team_ok) {
-    if ((s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) {
-      std::string msg = std::string("amenv_create: policy pack: ") + hipGetErrorString(s);
-      amenv_destroy(e);
-      return fail(nullptr, AMENV_ERR_ALLOC, msg);
-    }
-    const std::vector<float> tc = team_table_f32(*cfg);
-    if ((s = hipMalloc((void**)&e->team_consts, team_block_bytes<float>())) != hipSuccess ||
-        (s = hipMemcpy(e->team_consts, tc.data(), tc.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-        (s = team_write_params<float>(e)) != hipSuccess) {
-      std::string msg = std::string("amenv_create: team constants: ") + hipGetErrorString(s);
-      amenv_destroy(e);
-      return fail(nullptr, AMENV_ERR_ALLOC, msg);
-    }
-  }
-  if (e->team && cfg->dtype == AMENV_F64) {
-    const std::vector<double> tc = team_const_table<double>(*cfg, false);
-    if ((s = hipMalloc((void**)&e->team_consts, team_block_bytes<double>())) != hipSuccess ||
-        (s = hipMemcpy(e->team_consts, tc.data(), tc.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess ||
-        (s = team_write_params<double>(e)) != hipSuccess) {
-      std::string msg = std::string("amenv_create: team constants (fp64): ") + hipGetErrorString(s);
-      amenv_destroy(e);
-      return fail(nullptr, AMENV_ERR_ALLOC, msg);
-    }
-  }
-  char buf[200];
-  if (e->pwave) std::snprintf(buf, sizeof(buf), "step_kernel_pw<%s,NROT=%d,KW=%d,%s> (main wave + reset wave [+ observation wave + Monitor wave] per 64-env tile)",
-                              cfg->dtype == AMENV_F64 ? "double" : "float",
-                              (cfg->vehicle.n_rotors == 4 || cfg->vehicle.n_rotors == 6) ? cfg->vehicle.n_rotors : AMENV_MAX_ROTORS,
-                              is_v1(cfg) ? 2 : (cfg->task.num_waypoints == 1 ? 1 : AMENV_MAX_WAYPOINTS), is_v1(cfg) ? "v1" : "v2");
-  else if (e->quadk) std::snprintf(buf, sizeof(buf), "step_kernel_quad<NROT=%d,v2> (4 lanes per env, 16 envs per wave + episode-end helper wave)", cfg->vehicle.n_rotors);
-  else if (e->team) std::snprintf(buf, sizeof(buf), "step_kernel_team<%s,NROT=6,v2+arm3> (16 lanes per env: 4 RK4 stages x 4 components, 4 envs per wave + episode-end helper wave)",
-                                  cfg->dtype == AMENV_F64 ? "double" : "float");
-  else if (e->armk) std::snprintf(buf, sizeof(buf), "step_kernel_armk<%s,NROT=6> block=320 (4 RK4 stage waves + main wave per 64-env tile)", cfg->dtype == AMENV_F64 ? "double" : "float");
-  else if (e->arm2w) std::snprintf(buf, sizeof(buf), "step_kernel_arm2w<float,NROT=6> block=128 (2 waves per 64-env tile)");
-  else std::snprintf(buf, sizeof(buf), "step_kernel<%s,NROT=%d,KW=%d,%s> block=%d", cfg->dtype == AMENV_F64 ? "double" : "float",
-                (cfg->vehicle.n_rotors == 4 || cfg->vehicle.n_rotors == 6) ? cfg->vehicle.n_rotors : AMENV_MAX_ROTORS,
-                is_v1(cfg) ? 2 : (cfg->task.num_waypoints == 1 ? 1 : AMENV_MAX_WAYPOINTS), cfg->vehicle.n_joints ? "v2+arm3" : (is_v1(cfg) ? "v1" : "v2"), e->block);
-  e->obs_dim = obs_dim_of(&user_cfg);
-  e->act_dim = act_dim_of(&user_cfg);
+  if (family == StepFamily::Team && cfg->dtype == AMENV_F64 && (s = upload_team_consts<double>(e, true)) != hipSuccess) return alloc_failed("team constants (fp64)", s);
   if (e->pub_nj == 1 || e->pub_nj == 2) {
     if ((s = hipMalloc((void**)&e->io_act, n * 7 * sizeof(float))) != hipSuccess || (s = hipMalloc((void**)&e->io_obs, n * 29 * sizeof(float))) != hipSuccess ||
-        (s = hipMalloc((void**)&e->io_term, n * 29 * sizeof(float))) != hipSuccess) {
-      std::string msg = std::string("amenv_create: n-link adapter buffers: ") + hipGetErrorString(s);
-      amenv_destroy(e);
-      return fail(nullptr, AMENV_ERR_ALLOC, msg);
-    }
-    buf[sizeof(buf) - 1] = 0;
-    std::string kn = std::string(buf) + " [" + std::to_string(e->pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
-    std::snprintf(buf, sizeof(buf), "%s", kn.c_str());
+        (s = hipMalloc((void**)&e->io_term, n * 29 * sizeof(float))) != hipSuccess)
+      return alloc_failed("n-link adapter buffers", s);
   }
-  e->kname = buf;
   *out = e;
   return AMENV_OK;
 }
@@ -842,42 +832,41 @@ int amenv_ee_position(amenv* e, float* ee_out, void* stream) {
   return AMENV_OK;
 }
 
+namespace {
+// amenv_step and amenv_step_timed after their NULL checks (who: the entry point, for the messages)
+int step_launch(amenv* e, const char* who, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits, float* terminal_obs,
+                float* ep_return, int32_t* ep_len, hipStream_t s, bool timed) {
+  if (!aligned16(actions) || !aligned16(obs) || (terminal_obs && !aligned16(terminal_obs)))
+    return fail(e, AMENV_ERR_INVALID, std::string(who) + ": actions/obs/terminal_obs must be 16-byte aligned");
+  DeviceGuard g(e->device);
+  StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, e->stats};
+  if (e->io_act) { AMENV_HIP(e, pad_actions(*e, actions, s)); io.actions = reinterpret_cast<const float4*>(e->io_act); io.obs = e->io_obs; io.terminal_obs = terminal_obs ? e->io_term : nullptr; }
+  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? dispatch_step<double>(*e, io, 0, s, timed) : dispatch_step<float>(*e, io, 0, s, timed));
+  if (e->io_act) { AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs, s)); if (terminal_obs) AMENV_HIP(e, cut_obs(*e, e->io_term, done, terminal_obs, s)); }
+  e->steps += uint64_t(e->cfg.num_envs);
+  return AMENV_OK;
+}
+}  // namespace
+
 int amenv_step(amenv* e, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits, float* terminal_obs,
                float* ep_return, int32_t* ep_len, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   if (!actions || !obs || !reward || !done || !info_bits) return fail(e, AMENV_ERR_INVALID, "amenv_step: actions/obs/reward/done/info_bits must be non-NULL");
-  if (!aligned16(actions) || !aligned16(obs) || (terminal_obs && !aligned16(terminal_obs)))
-    return fail(e, AMENV_ERR_INVALID, "amenv_step: actions/obs/terminal_obs must be 16-byte aligned");
-  DeviceGuard g(e->device);
-  hipStream_t s = (hipStream_t)stream;
-  StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, e->stats};
-  if (e->io_act) { AMENV_HIP(e, pad_actions(*e, actions, s)); io.actions = reinterpret_cast<const float4*>(e->io_act); io.obs = e->io_obs; io.terminal_obs = terminal_obs ? e->io_term : nullptr; }
-  hipError_t st = e->cfg.dtype == AMENV_F64 ? dispatch_step<double>(*e, io, 0, s, false) : dispatch_step<float>(*e, io, 0, s, false);
-  AMENV_HIP(e, st);
-  if (e->io_act) { AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs, s)); if (terminal_obs) AMENV_HIP(e, cut_obs(*e, e->io_term, done, terminal_obs, s)); }
-  e->steps += uint64_t(e->cfg.num_envs);
-  return AMENV_OK;
+  return step_launch(e, "amenv_step", actions, obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, (hipStream_t)stream, false);
 }
 
 int amenv_step_timed(amenv* e, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits,
                      float* terminal_obs, float* ep_return, int32_t* ep_len, void* stream, float* kernel_us) {
   if (!e) return AMENV_ERR_INVALID;
   if (!actions || !obs || !reward || !done || !info_bits || !kernel_us) return fail(e, AMENV_ERR_INVALID, "amenv_step_timed: NULL argument");
-  if (!aligned16(actions) || !aligned16(obs) || (terminal_obs && !aligned16(terminal_obs)))
-    return fail(e, AMENV_ERR_INVALID, "amenv_step_timed: actions/obs/terminal_obs must be 16-byte aligned");
   DeviceGuard g(e->device);
   if (!e->ev_start) { AMENV_HIP(e, hipEventCreate(&e->ev_start)); AMENV_HIP(e, hipEventCreate(&e->ev_stop)); }
-  StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, e->stats};
-  hipStream_t s = (hipStream_t)stream;
-  if (e->io_act) { AMENV_HIP(e, pad_actions(*e, actions, s)); io.actions = reinterpret_cast<const float4*>(e->io_act); io.obs = e->io_obs; io.terminal_obs = terminal_obs ? e->io_term : nullptr; }
-  hipError_t st = e->cfg.dtype == AMENV_F64 ? dispatch_step<double>(*e, io, 0, s, true) : dispatch_step<float>(*e, io, 0, s, true);
-  AMENV_HIP(e, st);
-  if (e->io_act) { AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs, s)); if (terminal_obs) AMENV_HIP(e, cut_obs(*e, e->io_term, done, terminal_obs, s)); }
+  const int rc = step_launch(e, "amenv_step_timed", actions, obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, (hipStream_t)stream, true);
+  if (rc != AMENV_OK) return rc;
   AMENV_HIP(e, hipEventSynchronize(e->ev_stop));
   float ms = 0.f;
   AMENV_HIP(e, hipEventElapsedTime(&ms, e->ev_start, e->ev_stop));
   *kernel_us = ms * 1000.0f;
-  e->steps += uint64_t(e->cfg.num_envs);
   return AMENV_OK;
 }
 
@@ -886,7 +875,7 @@ int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, v
   if (!e) return AMENV_ERR_INVALID;
   if (n_steps <= 0 || !actions) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: n_steps must be > 0 and actions non-NULL");
   if (!aligned16(actions) || (obs && !aligned16(obs))) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: actions/obs must be 16-byte aligned");
-  if (e->team && e->cfg.dtype == AMENV_F64) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: the fp64 lane-team build is a logic gate of amenv_step only");
+  if (e->family == StepFamily::Team && e->cfg.dtype == AMENV_F64) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: the fp64 lane-team build is a logic gate of amenv_step only");
   if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: arms with 1 or 2 joints are served through amenv_step (the adapters at the C ABI are per step)");
   DeviceGuard g(e->device);
   StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, nullptr, nullptr, nullptr, e->stats};
@@ -900,7 +889,8 @@ int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, v
 int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp,
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
-  if (!e->team_ok && !e->quad_ok)
+  const bool quad = quad_ok(e->cfg);
+  if (!quad && !team_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles on the single-waypoint v2 task: rigid with 4 or 6 rotors (default workgroup size), or the "
                 "6-rotor vehicle with the z,x,x arm");
   if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: arms with 1 or 2 joints are served through amenv_step");
@@ -908,7 +898,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  const int obs_dim = e->obs_dim, act_dim = e->act_dim;   // 29, 7
+  const int obs_dim = e->obs_dim, act_dim = e->act_dim;   // 20, 4 (rigid) or 29, 7 (arm)
   // parameters -> bf16 MFMA fragments + per-lane action constants (they change every PPO iteration): a tiny kernel in front, no host sync
   const int pack_threads = 4 * (kPolFrags + kPolBias) * 64 + 64 + 4 * 4 * 64;
   hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, obs_dim, act_dim, e->pol_pack);
@@ -917,39 +907,30 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
   io.seed_lo = uint32_t(seed); io.seed_hi = uint32_t(seed >> 32); io.draw0 = draw0;
   io.obs = obs; io.actions = actions; io.logp = logp; io.values = values; io.rewards = rewards; io.dones = dones; io.info = info_bits;
   io.terminal_obs = terminal_obs;
-  if (e->quad_ok) {   // rigid vehicle: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
+  const int n = e->cfg.num_envs;
+  if (quad) {   // rigid vehicle: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
     const QuadParams QP = make_quad(*e);
     const dim3 gq(e->n_tiles * 4), bq(256);
-    if (e->cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((rollout_policy_kernel_quad<4>), gq, bq, 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io, e->stats, make_cold(*e), QP);
-    else hipLaunchKernelGGL((rollout_policy_kernel_quad<6>), gq, bq, 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io, e->stats, make_cold(*e), QP);
-    AMENV_HIP(e, hipGetLastError());
-    e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
-    return AMENV_OK;
-  }
-  // The env part follows the step kernel's choice: 16 lanes per env where amenv_step runs the lane-team kernel (small batches), else one
-  // lane per env (amenv_lane_policy.hpp; 64 envs per workgroup up to 16384 envs, 128 above: one workgroup per CU either way).
-  if (!e->team) {
+    if (e->cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((rollout_policy_kernel_quad<4>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
+    else hipLaunchKernelGGL((rollout_policy_kernel_quad<6>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
+  } else if (e->family == StepFamily::Team) {
+    // The env part follows the step kernel's choice: 16 lanes per env where amenv_step runs the lane-team kernel (small batches).  One 16-env
+    // workgroup per CU up to 4096 envs (5.15 vs 5.22 us per step there); above that the variant compiled for two wavefronts per SIMD pays
+    // (measured on MI355X at 8192 envs: 7.9 vs 10.1 us per step)
+    const TeamParams TP = make_team<float>(*e);
+    if (n <= 4096) hipLaunchKernelGGL((rollout_policy_kernel_team<6, 1>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
+    else hipLaunchKernelGGL((rollout_policy_kernel_team<6, 2>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
+  } else {
+    // every other arm family: one lane per env (amenv_lane_policy.hpp; 64 envs per workgroup up to 16384 envs, 128 above: one workgroup per CU either way)
     ArmArg<float, 3> AA;
     AA.p = make_arm<float>(*e);
     const HotParams<float, 6> HP = make_hot<float, 6>(*e);
-    if (e->cfg.num_envs <= 16384)
-      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 1>), dim3(e->n_tiles), dim3(320), 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io, e->stats, HP,
-                         make_cold(*e), AA);
+    if (n <= 16384)
+      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 1>), dim3(e->n_tiles), dim3(320), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, HP, make_cold(*e), AA);
     else
-      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 2>), dim3((e->n_tiles + 1) / 2), dim3(384), 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io, e->stats,
-                         HP, make_cold(*e), AA);
-    AMENV_HIP(e, hipGetLastError());
-    e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
-    return AMENV_OK;
+      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 2>), dim3((e->n_tiles + 1) / 2), dim3(384), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, HP,
+                         make_cold(*e), AA);
   }
-  const TeamParams TP = make_team<float>(*e);
-  // one 16-env workgroup per CU up to 4096 envs (5.15 vs 5.22 us per step there); above that the variant compiled for two wavefronts per SIMD pays
-  // (measured on MI355X at 8192 envs: 7.9 vs 10.1 us per step)
-  const int occ = e->cfg.num_envs <= 4096 ? 1 : 2;
-  if (occ == 1) hipLaunchKernelGGL((rollout_policy_kernel_team<6, 1>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io,
-                                   e->stats, make_cold(*e), TP);
-  else hipLaunchKernelGGL((rollout_policy_kernel_team<6, 2>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, e->cfg.num_envs, (int)n_steps, io, e->stats,
-                          make_cold(*e), TP);
   AMENV_HIP(e, hipGetLastError());
   e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
   return AMENV_OK;
@@ -1217,9 +1198,9 @@ int amenv_arm_rhs(const amenv_config* cfg, int32_t form, int32_t dtype, const vo
   if (validate(cfg) || cfg->vehicle.n_joints != 3 || cfg->vehicle.n_rotors != 6 || (form != 0 && form != 1) || (dtype != AMENV_F32 && dtype != AMENV_F64) ||
       !state19 || !wrench4 || !cmd3 || !deriv19 || n <= 0)
     return AMENV_ERR_INVALID;
+  if (generic_axes(cfg->vehicle)) return AMENV_ERR_INVALID;   // z,x,x arm
   amenv tmp;
   tmp.cfg = *cfg;
-  if (make_arm<float>(tmp).generic_axes) return AMENV_ERR_INVALID;   // z,x,x arm
   const dim3 grid((unsigned)((n + 63) / 64)), block(64);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == AMENV_F64) {

@@ -110,6 +110,30 @@ def test_bad_config_is_refused():
         assert (b"block_size" in L.amenv_last_error(None)) == (not ok), (bs, rc, L.amenv_last_error(None))
     cfg = amd._lib.default_config("quad", 16); cfg.step_kernel = 9
     assert L.amenv_create(C.byref(cfg), 0, C.byref(h)) == -1 and b"step_kernel" in L.amenv_last_error(None)
+
+    # a kernel the config is not built for is refused before the device is touched; a config it serves gets as far as the device
+    def kernel_cfg(vehicle, kernel, task="v2", dtype="f32"):
+        cfg = amd._lib.default_config(vehicle, 64, task)
+        cfg.step_kernel = amd._lib.KERNELS[kernel]
+        cfg.dtype = amd._lib.F64 if dtype == "f64" else amd._lib.F32
+        return cfg
+    generic = kernel_cfg("hexa_arm", "helper"); generic.vehicle.joint_axis[:] = [0, 0, 1, 0, 1, 0, 1, 0, 0]   # z, y, x: the lane kernel only
+    bs64 = kernel_cfg("hexa", "helper"); bs64.block_size = 64
+    two_wp = kernel_cfg("hexa", "team"); two_wp.task.num_waypoints = 2
+    rk4_2 = kernel_cfg("hexa_arm", "staged"); rk4_2.task.rk4_substeps = 2
+    refused = [("HELPER", generic), ("HELPER", bs64), ("TEAM", kernel_cfg("quad", "team", task="v1_scaled")), ("TEAM", two_wp), ("STAGED", rk4_2),
+               ("STAGED", kernel_cfg("quad", "staged"))]
+    for name, cfg in refused:
+        assert L.amenv_create(C.byref(cfg), 0, C.byref(h)) == -1
+        assert f"amenv_create: AMENV_KERNEL_{name} is built for".encode() in L.amenv_last_error(None), (name, L.amenv_last_error(None))
+    accepted = [kernel_cfg("hexa_arm", "helper"), kernel_cfg("hexa", "helper"), kernel_cfg("hexa_arm", "team"), kernel_cfg("hexa_arm", "team", dtype="f64"),
+                kernel_cfg("quad", "team"), kernel_cfg("hexa_arm", "staged"), kernel_cfg("hexa_arm", "staged", dtype="f64")]
+    for cfg in accepted:
+        rc = L.amenv_create(C.byref(cfg), 0, C.byref(h))
+        if rc == 0:   # a machine with a GPU
+            L.amenv_destroy(h)
+        else:         # AMENV_ERR_NO_DEVICE
+            assert rc == -3 and b"no HIP device" in L.amenv_last_error(None), (rc, L.amenv_last_error(None))
     with pytest.raises(amd.AmenvError):
         amd._lib.default_config("octo", 1)
 
