@@ -2,10 +2,15 @@
 
     python examples/rl_train_gpu.py [--envs 4096] [--timesteps 4100000] [--resume ppo_model_2300000_steps.zip]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/rl_train_gpu.py ...
+    python examples/rl_train_gpu.py --task v1_raw --normalize-obs [--fused-rollout]      # initial-implementation-v1/rl_train_vecN.py
 
 Same hyper-parameters as the reference (lr 2e-4, 12 epochs, gamma .995, lambda .9, clip .2, ent 5e-4 -- 1e-4 when resuming,
 :35 -- MLP [128,64,64] tanh); the rollout is `envs x n_steps` instead of `8 x 2048`, so n_steps / batch_size are rescaled to
 keep the reference's 16,384-sample rollouts x 128-sample minibatches ratio (128 minibatches per epoch).
+--task v1_scaled / v1_raw: the recipe of v1/rl_train_vecN.py instead (10 epochs, ent .01, the 17-D v1 env); --normalize-obs wraps the env
+as its VecNormalize(norm_obs=True, norm_reward=False) does, and the statistics are saved next to the checkpoint (<save>_vec_normalize.npz,
+GpuVecNormalize.save's format).  With --fused-rollout the normaliser runs inside the launch and its statistics are frozen for each
+rollout.
 
 Defaults = the run recorded in profiles/r01/ppo_from_scratch.json: 256 envs x 512 steps, 90 M steps, ~10 minutes on one MI355X, > 90 % of
 episodes successful after 39 M steps.  Learning progress follows the number of Adam updates (1536 per iteration here), not the number of samples:
@@ -26,6 +31,9 @@ def main():
     ap.add_argument("--resume", default=None, help="SB3 zip / policy.pth to start from (rl_train.py:33-35)")
     ap.add_argument("--save", default="waypoint_controller_gpu")         # rl_train.py:57
     ap.add_argument("--vehicle", default="quad")
+    ap.add_argument("--task", default="v2", choices=["v2", "v1_scaled", "v1_raw"],
+                    help="v2: rl_train.py's env; v1_scaled / v1_raw: the v1 env files (rl_train_vecN.py imports rl_env = v1_raw) with rl_train_vecN.py's recipe")
+    ap.add_argument("--normalize-obs", action="store_true", help="observation normaliser (VecNormalize(norm_obs=True, norm_reward=False), rl_train_vecN.py:10-11)")
     ap.add_argument("--seed", type=int, default=0, help="env reset stream, initial weights and action noise (one run = one seed: PPO on this task is seed-sensitive)")
     ap.add_argument("--moment-scale", type=float, default=None, help="N m per unit moment action (amenv_vehicle.moment_scale; the reference quadrotor: 0.1)")
     ap.add_argument("--fused-rollout", action="store_true", help="collect every rollout as ONE launch (amenv_rollout_policy: the policy on bf16 matrix cores inside the env loop; "
@@ -44,12 +52,15 @@ def main():
     dist = sharding.init_process_group("nccl", torch.device("cuda", local))
     cfg = None
     if a.moment_scale is not None:
-        cfg = amd._lib.default_config(a.vehicle, a.envs)
+        cfg = amd._lib.default_config(a.vehicle, a.envs, a.task)
         cfg.vehicle.moment_scale = a.moment_scale
         cfg.seed, cfg.env_id_offset = a.seed, sh.env_id_offset
-    env = amd.GpuWaypointEnv(a.envs, device=local, vehicle=a.vehicle, seed=a.seed, env_id_offset=sh.env_id_offset, config=cfg)
-    model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=12, gamma=0.995,
-                    gae_lambda=0.9, clip_range=0.2, ent_coef=1e-4 if a.resume else 5e-4, dist=dist, fused_rollout=a.fused_rollout, seed=a.seed)
+    env = amd.GpuWaypointEnv(a.envs, device=local, vehicle=a.vehicle, seed=a.seed, env_id_offset=sh.env_id_offset, config=cfg, task=a.task)
+    norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
+    v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
+    model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
+                    gae_lambda=0.9, clip_range=0.2, ent_coef=0.01 if v1 else (1e-4 if a.resume else 5e-4), dist=dist, fused_rollout=a.fused_rollout,
+                    seed=a.seed, obs_normalizer=norm)
     if a.resume:
         model.load_policy(a.resume)
     elif a.warm_start_pid is not None:
@@ -71,6 +82,11 @@ def main():
     seconds = time.time() - t0
     if sh.rank == 0:
         print("saved", model.save(a.save))
+        if norm is not None:    # env.save("vec_normalize") of rl_train_vecN.py, in GpuVecNormalize.save's .npz format
+            import numpy as np
+            mean, var, count = norm.get()
+            np.savez(a.save + "_vec_normalize.npz", mean=mean, var=var, count=count, clip_obs=norm.clip_obs, epsilon=norm.epsilon)
+            print("saved", a.save + "_vec_normalize.npz")
         mean_reward, std_reward = amd.evaluate_policy(model, env, n_eval_episodes=max(10, a.envs))      # rl_train.py:60-61
         print(f"Mean reward: {mean_reward} +/- {std_reward}")
         if curve and curve[-1].get("success_rate", 1.0) < 0.5 and a.warm_start_pid is None and not a.resume:

@@ -335,12 +335,15 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
 /* Closed-loop rollout in ONE launch (SB3 collect_rollouts, v2/rl_train.py:38-56, for n_steps steps): per step
  *   obs_t -> actor / critic MLPs ([128, 64, 64] tanh; bf16 matrix cores, fp32 accumulate) -> a_t = mean + exp(log_std) z  (Philox keyed
  *   by (seed, global env id, draw0 + t) as amenv_gaussian_act) -> clip to the action box -> env step (as amenv_step, auto-reset included).
- * State, per-lane constants and the policy weights stay in registers between steps.  Built for fp32 vehicles on the single-waypoint v2 task:
- * the rigid vehicles with 4 or 6 rotors -- the reference's quadrotor (obs_dim 20, act_dim 4; default workgroup size; the env part is the
- * lane-quad step, 4 lanes per env: replaying the recorded clipped actions through amenv_step on a handle created with AMENV_KERNEL_TEAM
- * reproduces every row bit for bit; the first layer runs on two-part bf16 inputs and weights, which holds the action within 3e-2 of the
- * fp32 policy's on the reference checkpoint) -- and the 6-rotor vehicle with the z,x,x 3-joint arm (obs_dim 29, act_dim 7); other
- * configurations return AMENV_ERR_INVALID.  For the arm vehicle the env part is the arithmetic of the kernel amenv_step
+ * State, per-lane constants and the policy weights stay in registers between steps.  Built for fp32 vehicles:
+ * the rigid vehicles with 4 or 6 rotors on every task -- on the single-waypoint v2 task with the default workgroup size the reference's
+ * quadrotor (obs_dim 20, act_dim 4) runs the lane-quad step, 4 lanes per env: replaying the recorded clipped actions through amenv_step on
+ * a handle created with AMENV_KERNEL_TEAM reproduces every row bit for bit; on the v1 tasks (obs_dim 17, v1/rl_train_vecN.py), the v2 task
+ * with 2..4 waypoints or a set block_size one lane per env runs the arithmetic of the LANE / HELPER step kernels (replay through amenv_step
+ * on a handle created with AMENV_KERNEL_LANE is bit for bit); both rigid forms run the first layer on two-part bf16 inputs and weights,
+ * which holds the action within 3e-2 of the fp32 policy's on the reference checkpoint, and draw the same noise -- and the 6-rotor vehicle
+ * with the z,x,x 3-joint arm on the single-waypoint v2 task (obs_dim 29, act_dim 7); fp64 envs, arms with 2..4 waypoints and arms of 1 or
+ * 2 joints return AMENV_ERR_INVALID.  For the arm vehicle the env part is the arithmetic of the kernel amenv_step
  * runs for this env (16 lanes per env where that is the lane-team kernel, else one lane per env with the arithmetic of the LANE / HELPER step
  * kernels: replaying the recorded clipped actions through amenv_step on such a handle reproduces every row bit for bit; a handle whose
  * amenv_step runs the STAGED kernel agrees to rounding); both forms draw the same noise.  An opt-in ROLLOUT mode: bf16
@@ -351,6 +354,22 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
  *   info_bits    [n_steps, N] u32 or NULL;  terminal_obs [n_steps, N, obs_dim] f32 or NULL (rows written only where dones != 0) */
 int amenv_rollout_policy(amenv* env, int32_t n_steps, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions,
                          float* logp, float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream);
+
+/* amenv_rollout_policy with the observation normaliser INSIDE the launch: the rollout of `VecNormalize(env, norm_obs=True,
+ * norm_reward=False)` (v1/rl_train_vecN.py:10-11) in one launch, for every fp32 rigid vehicle with 4 or 6 rotors (single-waypoint v2
+ * included; always the one-lane-per-env form).  FROZEN-STATISTICS CONTRACT: the normaliser's mean / var are read once at entry and every
+ * published observation -- obs rows 0..n_steps, the policy's input, terminal_obs rows -- is
+ *   clip(float((double(raw) - mean) * (1 / sqrt(var + eps))), -clip, clip)
+ * under those entry statistics, bit-identical to amenv_obsnorm_apply (SB3's VecNormalize updates them before every step instead).
+ * update != 0: the raw rows 1..n_steps of every env (post-step / post-reset; not row 0, which the previous rollout or the caller's update
+ * after reset counted; not the terminal rows, as SB3's VecNormalize) are summed in fp64 inside the launch and merged once afterwards
+ * (amenv_obsnorm_update's merge with batch count n_steps x N: Chan's formula is associative, so the statistics equal n_steps per-step
+ * updates to fp64 rounding).  update == 0 (VecNormalize.training = False) leaves the statistics untouched.  The normaliser's dim must be
+ * the env's obs_dim and it must live on the env's device; arm vehicles, fp64 envs, NULL or bad arguments return AMENV_ERR_INVALID before
+ * anything is launched.  clip, eps: VecNormalize's clip_obs (10) and epsilon (1e-8).  The other arguments are amenv_rollout_policy's. */
+int amenv_rollout_policy_norm(amenv* env, amenv_obsnorm* norm, int32_t update, float clip, double eps, int32_t n_steps, const float* flat_params,
+                              uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards, uint8_t* dones,
+                              uint32_t* info_bits, float* terminal_obs, void* stream);
 
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under

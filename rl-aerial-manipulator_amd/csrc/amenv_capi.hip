@@ -22,6 +22,7 @@
 #include "amenv_team_policy.hpp"
 #include "amenv_quad_policy.hpp"
 #include "amenv_lane_policy.hpp"
+#include "amenv_rigid_policy.hpp"
 #include "amenv_obsnorm.hpp"
 #include "amenv_policy.hpp"
 #include "amenv_train.hpp"
@@ -357,6 +358,8 @@ bool quad_ok(const amenv_config& c) {
 }
 // fp32 lane-team kernels (step, rollout, closed loop: amenv_rollout_policy)
 bool team_ok(const amenv_config& c) { return c.dtype == AMENV_F32 && zxx_arm1(c); }
+// one-lane-per-env closed loop of the rigid vehicles (amenv_rigid_policy.hpp): fp32, 4 or 6 rotors, every task, any workgroup size
+bool rigid_pol_ok(const amenv_config& c) { return c.vehicle.n_joints == 0 && c.dtype == AMENV_F32 && (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6); }
 
 constexpr int kTeamAutoMax = 6144;    // AUTO: lane-team kernel up to this batch
 constexpr int kArmkAutoMax = 32768;   // AUTO: stage-wave kernel up to this batch
@@ -561,6 +564,54 @@ hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hip
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// amenv_rigid_policy.hpp: workgroup shape by batch size: 16 envs per workgroup fill the CUs at small batches, 64 or 128 envs
+// (one or two env wavefronts) cost fewer MLP wavefronts per env at large ones.  Measured on MI355X, v1_raw quadrotor with the normaliser, us per
+// step (NE = 16 / 64 / 128): 4096 envs 5.4 / 7.4 / 11.0, 8192 9.4 / 7.3 / 10.9, 16384 17.5 / 7.9 / 11.3, 32768 33.3 / 14.3 / 12.0
+// (profiles/r04/rigid_policy_crossover_*.json); the bounds sit at the interpolated crossovers.  -DAMENV_RIGID_WG16_MAX / -DAMENV_RIGID_WG64_MAX build the
+// variants the crossover was measured with (tools/build_variant.py)
+#ifndef AMENV_RIGID_WG16_MAX
+#define AMENV_RIGID_WG16_MAX 6144
+#endif
+#ifndef AMENV_RIGID_WG64_MAX
+#define AMENV_RIGID_WG64_MAX 24576
+#endif
+template <int NROT, int KW, int VAR, bool NORM>
+hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
+  const ColdParams C = make_cold(e);
+  const int n = e.cfg.num_envs;
+  if (n <= AMENV_RIGID_WG16_MAX)
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+  else if (n <= AMENV_RIGID_WG64_MAX)
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+  else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+  return hipGetLastError();
+}
+template <bool NORM>
+hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  const bool four = e.cfg.vehicle.n_rotors == 4;
+  if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
+    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM>(e, T, io, N, s);
+  if (e.cfg.task.num_waypoints == 1)
+    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM>(e, T, io, N, s);
+  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM>(e, T, io, N, s);
+}
+
+// amenv_rollout_policy[_norm] after the entry checks: pack the parameters, fill the kernel's I/O block
+PolicyIO policy_io(amenv& e, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards,
+                   uint8_t* dones, uint32_t* info_bits, float* terminal_obs, hipStream_t s) {
+  // parameters -> bf16 MFMA fragments + per-lane action constants (they change every PPO iteration): a tiny kernel in front, no host sync
+  const int pack_threads = 4 * (kPolFrags + kPolBias) * 64 + 64 + 4 * 4 * 64;
+  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, e.obs_dim, e.act_dim, e.pol_pack);
+  PolicyIO io;
+  io.pack = reinterpret_cast<const uint4*>(e.pol_pack);
+  io.seed_lo = uint32_t(seed); io.seed_hi = uint32_t(seed >> 32); io.draw0 = draw0;
+  io.obs = obs; io.actions = actions; io.logp = logp; io.values = values; io.rewards = rewards; io.dones = dones; io.info = info_bits;
+  io.terminal_obs = terminal_obs;
+  return io;
+}
+
 template <typename V>
 __global__ void calibration_copy_kernel(const V* __restrict__ src, V* __restrict__ dst, size_t n) {
   for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) dst[i] = src[i];
@@ -750,10 +801,9 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
     return alloc_failed("device allocation failed", s);
   // the lane-quad / fp32 lane-team constants (every kernel of theirs: step, rollout, closed-loop rollout) + the packed policy of amenv_rollout_policy
   const bool quad = quad_ok(*cfg), team = team_ok(*cfg);
-  if (quad || team) {
-    if ((s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) return alloc_failed(quad ? "quad constants" : "policy pack", s);
-    if ((s = upload_team_consts<float>(e, team)) != hipSuccess) return alloc_failed(quad ? "quad constants" : "team constants", s);
-  }
+  if (quad || team || rigid_pol_ok(*cfg))
+    if ((s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) return alloc_failed("policy pack", s);
+  if ((quad || team) && (s = upload_team_consts<float>(e, team)) != hipSuccess) return alloc_failed(quad ? "quad constants" : "team constants", s);
   if (family == StepFamily::Team && cfg->dtype == AMENV_F64 && (s = upload_team_consts<double>(e, true)) != hipSuccess) return alloc_failed("team constants (fp64)", s);
   if (e->pub_nj == 1 || e->pub_nj == 2) {
     if ((s = hipMalloc((void**)&e->io_act, n * 7 * sizeof(float))) != hipSuccess || (s = hipMalloc((void**)&e->io_obs, n * 29 * sizeof(float))) != hipSuccess ||
@@ -889,30 +939,26 @@ int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, v
 int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp,
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
-  const bool quad = quad_ok(e->cfg);
-  if (!quad && !team_ok(e->cfg))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles on the single-waypoint v2 task: rigid with 4 or 6 rotors (default workgroup size), or the "
-                "6-rotor vehicle with the z,x,x arm");
+  const bool quad = quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  if (!quad && !rigid && !team_ok(e->cfg))
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with the "
+                "z,x,x arm on the single-waypoint v2 task");
   if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: arms with 1 or 2 joints are served through amenv_step");
   if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
+  if (rigid && (!aligned16(obs) || !aligned16(actions) || (terminal_obs && !aligned16(terminal_obs))))
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: obs / actions / terminal_obs must be 16-byte aligned");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  const int obs_dim = e->obs_dim, act_dim = e->act_dim;   // 20, 4 (rigid) or 29, 7 (arm)
-  // parameters -> bf16 MFMA fragments + per-lane action constants (they change every PPO iteration): a tiny kernel in front, no host sync
-  const int pack_threads = 4 * (kPolFrags + kPolBias) * 64 + 64 + 4 * 4 * 64;
-  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, obs_dim, act_dim, e->pol_pack);
-  PolicyIO io;
-  io.pack = reinterpret_cast<const uint4*>(e->pol_pack);
-  io.seed_lo = uint32_t(seed); io.seed_hi = uint32_t(seed >> 32); io.draw0 = draw0;
-  io.obs = obs; io.actions = actions; io.logp = logp; io.values = values; io.rewards = rewards; io.dones = dones; io.info = info_bits;
-  io.terminal_obs = terminal_obs;
+  const PolicyIO io = policy_io(*e, flat_params, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits, terminal_obs, s);
   const int n = e->cfg.num_envs;
-  if (quad) {   // rigid vehicle: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
+  if (quad) {   // rigid vehicle, single-waypoint v2 task, default workgroup size: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
     const QuadParams QP = make_quad(*e);
     const dim3 gq(e->n_tiles * 4), bq(256);
     if (e->cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((rollout_policy_kernel_quad<4>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
     else hipLaunchKernelGGL((rollout_policy_kernel_quad<6>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
+  } else if (rigid) {   // every other rigid config (v1 tasks, 2..4 waypoints, a set workgroup size): one lane per env (amenv_rigid_policy.hpp)
+    AMENV_HIP(e, launch_rigid_policy<false>(*e, (int)n_steps, io, NormArg{nullptr, 0.0f, 0.0, 0}, s));
   } else if (e->family == StepFamily::Team) {
     // The env part follows the step kernel's choice: 16 lanes per env where amenv_step runs the lane-team kernel (small batches).  One 16-env
     // workgroup per CU up to 4096 envs (5.15 vs 5.22 us per step there); above that the variant compiled for two wavefronts per SIMD pays
@@ -1057,6 +1103,31 @@ int amenv_obsnorm_set(amenv_obsnorm* h, const double* mean, const double* var, d
   dst[2 * d] = count;
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(h->buf, staging.data(), staging.size(), hipMemcpyHostToDevice) != hipSuccess)
     return AMENV_ERR_HIP;
+  return AMENV_OK;
+}
+
+int amenv_rollout_policy_norm(amenv* e, amenv_obsnorm* h, int32_t update, float clip, double eps, int32_t n_steps, const float* flat_params, uint64_t seed,
+                              uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards, uint8_t* dones, uint32_t* info_bits,
+                              float* terminal_obs, void* stream) {
+  if (!e || !h) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: env and normaliser must be non-NULL");
+  if (!rigid_pol_ok(e->cfg))
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: built for fp32 rigid vehicles with 4 or 6 rotors (arm vehicles: amenv_rollout_policy, normalise outside)");
+  if (h->dim != e->obs_dim) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser's dim differs from the env's obs_dim");
+  if (h->device != e->device) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser lives on another device");
+  if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
+  if (!(clip > 0.0f) || !(eps >= 0.0)) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: clip must be > 0 and eps >= 0");
+  if (!aligned16(obs) || !aligned16(actions) || (terminal_obs && !aligned16(terminal_obs)))
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: obs / actions / terminal_obs must be 16-byte aligned");
+  DeviceGuard g(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  const PolicyIO io = policy_io(*e, flat_params, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits, terminal_obs, s);
+  AMENV_HIP(e, launch_rigid_policy<true>(*e, (int)n_steps, io, NormArg{h->buf, clip, eps, update}, s));
+  const int d = h->dim;
+  if (update)   // the launch left the sums of the raw rows 1..T in the batch slots: one merge of T x N rows (Chan's formula, associative)
+    hipLaunchKernelGGL(obsnorm_merge_kernel, dim3(1), dim3(((d + 63) / 64) * 64), 0, s, h->buf, d, double(n_steps) * double(e->cfg.num_envs));
+  AMENV_HIP(e, hipGetLastError());
+  e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
   return AMENV_OK;
 }
 

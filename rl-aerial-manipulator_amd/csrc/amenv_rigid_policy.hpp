@@ -1,0 +1,272 @@
+// amenv_rigid_policy.hpp -- closed-loop rollout in ONE launch for the rigid vehicles (4 or 6 rotors, fp32) on every task the step kernels
+// serve: the v1 tasks (17-D observation, 1..2 waypoints per episode; v1/rl_train_vecN.py trains them) and the v2 task with 1..4 waypoints;
+// optionally with the observation normaliser inside the launch (VecNormalize(norm_obs=True, norm_reward=False), v1/rl_train_vecN.py:10-11).
+//   * env part: ONE LANE PER ENV, step_lane<float, NROT, KW, VAR, 0> -- the arithmetic of amenv_step's LANE / HELPER kernels, so replaying the
+//     recorded clipped actions through amenv_step on such a handle reproduces every row bit for bit.  Tile addressing is by the env index
+//     (i & 63), the blob layout is the step kernels';
+//   * MLP part: amenv_quad_policy.hpp's -- packed weight fragments resident in four wavefronts, v_mfma_f32_16x16x32_bf16, five barriers
+//     per step, and the rigid-vehicle first layer: two-part bf16 inputs (xin / xlo) and two-part first-layer weights (wlo, kPolLoBase).
+//     one bf16 rounding of the input moved a trained controller's action by up to 0.107; normalised inputs reach +-10;
+//   * sampling: the quad form's Philox keying (block 0 = the four wrench entries), Box-Muller mapping and log-prob association: for the same
+//     observation both forms draw the same noise;
+//   * workgroup = NE envs: NE = 16 (one 16-env column tile, 256 workgroups at 4096 envs: every CU busy) or NE = 64 EW (EW = 1, 2 env
+//     wavefronts; the large-batch shape of amenv_lane_policy.hpp).  Wavefronts 0..3 run the MLPs, wavefronts 4.. the envs; with NE = 16
+//     lanes 16..63 of the env wavefront only take part in the barriers.  The C ABI picks NE by batch size.
+// NORM: the normaliser's statistics are read ONCE at entry (mean and 1/sqrt(var + eps) in fp64, obsnorm_apply_kernel's arithmetic: the
+// published rows are bit-identical to amenv_obsnorm_apply under the entry statistics) and are FROZEN for the launch: buffer rows 0..T, the
+// MLP input and the terminal rows are normalised with them.  With `update`, the raw rows 1..T of every active env (post-step, post-reset;
+// not row 0, which the previous launch or the initial reset counted; not the terminal rows, as the step-by-step path) are summed per lane in
+// fp64, reduced once per env wavefront at the end and added into the buffer's batch-sum slots; obsnorm_merge_kernel follows the launch.
+#pragma once
+#include "amenv_kernels.hpp"
+#include "amenv_obsnorm.hpp"
+#include "amenv_team_policy.hpp"
+
+namespace amenv_dev {
+
+struct NormArg {
+  double* buf;    // amenv_obsnorm buffer (obsnorm_words(OD) doubles) or null (NORM = false)
+  float clip;
+  double eps;
+  int32_t update;  // != 0: add the raw rows 1..T into the batch-sum slots
+};
+
+template <int NROT, int KW, int VAR, bool NORM, int NE>
+__global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
+                                                                                         const PolicyIO io, unsigned long long* __restrict__ stats,
+                                                                                         const HotParams<float, NROT> P, const ColdParams C, const NormArg N) {
+  constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
+  static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
+  __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
+  __shared__ __attribute__((aligned(16))) __bf16 xlo[NE * kXS];          // the observation's second bf16 part (x - bf16(x))
+  __shared__ __attribute__((aligned(16))) __bf16 h1[2 * NE * kH1S];       // layer-1 activations; layer 3's reuse the front of it
+  __shared__ __attribute__((aligned(16))) __bf16 h2[2 * NE * kH2S];
+  __shared__ __attribute__((aligned(16))) float meanb[NE * 4];
+  __shared__ float valb[NE];
+  __shared__ double md[NORM ? 2 * OD : 1];                                // entry statistics: mean | 1 / sqrt(var + eps)
+  __bf16* h3 = h1;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
+  const int lane = int(threadIdx.x) & 63;
+  if constexpr (NORM) {
+    for (int j = int(threadIdx.x); j < OD; j += int(blockDim.x)) { md[j] = N.buf[j]; md[OD + j] = 1.0 / sqrt(N.buf[OD + j] + N.eps); }
+    __syncthreads();
+  }
+  if (wave < 4) {
+    // ---- MLP wavefronts: this wavefront's neuron subset for every 16-env column tile
+    uint4 wf[kPolFrags], wlo[4];
+    f32x4 bias[kPolBias];
+#pragma unroll
+    for (int k = 0; k < 4; k++) wlo[k] = io.pack[size_t(kPolLoBase) + size_t(4 * wave + k) * 64 + lane];
+    {
+      const uint4* src = io.pack + size_t(wave) * (kPolFrags + kPolBias) * 64 + lane;
+#pragma unroll
+      for (int k = 0; k < kPolFrags; k++) wf[k] = src[k * 64];
+#pragma unroll
+      for (int k = 0; k < kPolBias; k++) { const uint4 b = src[(kPolFrags + k) * 64]; bias[k] = f32x4{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)}; }
+    }
+    const int nrow = lane & 15, kq = lane >> 4;
+    auto load_b = [&](const __bf16* base, int stride, int et, int ks) {   // operand B: 8 consecutive inputs of env 16 et + nrow
+      return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + (16 * et + nrow) * stride + 32 * ks + 8 * kq));
+    };
+    auto store_d = [&](__bf16* base, int stride, int et, int tile16, const f32x4& acc) {   // tanh, 4 consecutive neurons of that env
+      const f32x4 t{fast_tanh(acc[0]), fast_tanh(acc[1]), fast_tanh(acc[2]), fast_tanh(acc[3])};
+      *reinterpret_cast<uint2*>(base + (16 * et + nrow) * stride + 16 * tile16 + 4 * kq) = __builtin_bit_cast(uint2, __builtin_convertvector(t, bf16x4));
+    };
+    const int net23 = wave >> 1;                                  // layers 2, 3: wavefronts 0, 1 the actor, 2, 3 the critic
+    for (int t = 0; t < n_steps; t++) {
+      __syncthreads();                                            // (B0) the observation tile is complete
+#pragma unroll
+      for (int et = 0; et < NT; et++) {                            // layer 1, K = 32: hi.hi + hi.lo + lo.hi (amenv_quad_policy.hpp)
+        const bf16x8 B = load_b(xin, kXS, et, 0), Bl = load_b(xlo, kXS, et, 0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int T = 4 * wave + j, net = T >> 3;
+          f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wlo[j]), B, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), Bl, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), B, acc, 0, 0, 0);
+          store_d(h1 + net * NE * kH1S, kH1S, et, T & 7, acc);
+        }
+      }
+      __syncthreads();                                            // (B1)
+#pragma unroll
+      for (int et = 0; et < NT; et++) {
+        bf16x8 B[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) B[ks] = load_b(h1 + net23 * NE * kH1S, kH1S, et, ks);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          f32x4 acc = bias[j];
+#pragma unroll
+          for (int ks = 0; ks < 4; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[4 + 4 * j + ks]), B[ks], acc, 0, 0, 0);
+          store_d(h2 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
+        }
+      }
+      __syncthreads();                                            // (B2) h1 has been read by everyone: layer 3 may overwrite it
+#pragma unroll
+      for (int et = 0; et < NT; et++) {
+        bf16x8 B[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) B[ks] = load_b(h2 + net23 * NE * kH2S, kH2S, et, ks);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          f32x4 acc = bias[2 + j];
+#pragma unroll
+          for (int ks = 0; ks < 2; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[12 + 2 * j + ks]), B[ks], acc, 0, 0, 0);
+          store_d(h3 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
+        }
+      }
+      __syncthreads();                                            // (B3)
+      if (wave < 2) {   // heads: wavefront 0 the action mean (rows 0..3), wavefront 1 the value (row 0)
+#pragma unroll
+        for (int et = 0; et < NT; et++) {
+          f32x4 acc = bias[4];
+#pragma unroll
+          for (int ks = 0; ks < 2; ks++)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[16 + ks]), load_b(h3 + wave * NE * kH2S, kH2S, et, ks), acc, 0, 0, 0);
+          if (wave == 0) { if (kq == 0) *reinterpret_cast<float4*>(meanb + (16 * et + nrow) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]); }
+          else if (kq == 0) valb[16 * et + nrow] = acc[0];
+        }
+      }
+      __syncthreads();                                            // (B4) means and values are there
+    }
+    return;
+  }
+  // ---- env wavefronts: one lane per env (NE = 16: lanes 0..15; the others only pass the barriers)
+  const int el = (wave - 4) * 64 + lane;                          // env within the workgroup
+  const bool mine = NE >= 64 || el < NE;
+  const int i = int(blockIdx.x) * NE + (mine ? el : 0);
+  const int tl = i & 63;                                          // the env's slot in its 64-env tile
+  const bool active = mine && i < n_envs;
+  const size_t n = size_t(n_envs);
+  char* tile = static_cast<char*>(blob) + size_t(i >> 6) * tile_bytes;
+  const int K = KW == 1 ? 1 : P.K;
+  Env<float, KW> e;
+  float std_a[AD], ls_a[AD];
+  float o[kObsDimMax];
+  double s1[NORM ? OD : 1], s2[NORM ? OD : 1];                    // fp64 column sums / sums of squares of this lane's raw rows 1..T
+#pragma unroll
+  for (int j = 0; j < (NORM ? OD : 1); j++) { s1[j] = 0.0; s2[j] = 0.0; }
+  const bool count = NORM && active && N.update != 0;
+  auto publish_obs = [&](float* grow, bool add) {                 // observation row -> rollout buffer and (two bf16 parts) the MLP input tile
+    float v[OD];
+#pragma unroll
+    for (int j = 0; j < OD; j++) {
+      if constexpr (NORM) {   // obsnorm_apply_kernel's arithmetic
+        float x = float((double(o[j]) - md[j]) * md[OD + j]);
+        v[j] = x < -N.clip ? -N.clip : (x > N.clip ? N.clip : x);
+        if (add) { const double r = double(o[j]); s1[j] += r; s2[j] += r * r; }
+      } else {
+        v[j] = o[j];
+      }
+    }
+    if (active) {
+      if constexpr (OD % 4 == 0) {
+#pragma unroll
+        for (int j = 0; j < OD / 4; j++) reinterpret_cast<float4*>(grow)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < OD; j++) grow[j] = v[j];
+      }
+    }
+    __bf16* xr = xin + el * kXS;
+    __bf16* xl = xlo + el * kXS;
+#pragma unroll
+    for (int j = 0; j < OD; j++) { const __bf16 hi = (__bf16)v[j]; xr[j] = hi; xl[j] = (__bf16)(v[j] - float(hi)); }
+  };
+  if (mine) {
+    load_env<float, KW, 0>(K, tile, tl, e);
+    const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
+#pragma unroll
+    for (int c = 0; c < AD; c++) { const uint4 v = ac[c]; std_a[c] = __uint_as_float(v.x); ls_a[c] = __uint_as_float(v.y); }
+    if constexpr (VAR == VAR_V1) observe_v1<float, KW>(P.raw_obs != 0, e, o); else observe<float, KW>(K, e, o);
+    __bf16* xr = xin + el * kXS;
+    __bf16* xl = xlo + el * kXS;
+#pragma unroll
+    for (int j = OD; j < 32; j++) { xr[j] = (__bf16)(j == OD ? 1.0f : 0.0f); xl[j] = (__bf16)0.0f; }   // bias column, K padding
+    publish_obs(io.obs + size_t(i) * OD, false);
+  }
+  const int64_t gid = C.gid0 + i;
+  const uint32_t g_lo = uint32_t(uint64_t(gid)), g_hi = uint32_t(uint64_t(gid) >> 32);
+  bool any_reset = false;
+  StepIO sio{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stats};
+  const ArmArg<float, 0> AA{0};
+  for (int t = 0; t < n_steps; t++) {
+    __syncthreads();   // (B0) observation tile published
+    __syncthreads();   // (B1)
+    __syncthreads();   // (B2)
+    __syncthreads();   // (B3)
+    __syncthreads();   // (B4) action means and value of this lane's env are in LDS
+    if (!mine) continue;
+    const float4 m = *reinterpret_cast<const float4*>(meanb + el * 4);
+    const float mean[4] = {m.x, m.y, m.z, m.w};
+    const float value = valb[el];
+    // ---- sample: raw = mean + std z, logp, clip; Philox block 0, pairs (w0, w1) -> entries 0 (cos), 1 (sin), (w2, w3) -> 2, 3
+    float z[4];
+    {
+      uint32_t w4[4];
+      philox4x32_10(io.seed_lo ^ 0x5bd1e995u, io.seed_hi ^ 0x27d4eb2fu, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, w4);
+#pragma unroll
+      for (int p = 0; p < 2; p++) {
+        const float u1 = float((w4[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f, u2 = float(w4[2 * p + 1] >> 8) * 5.9604644775390625e-08f;
+        const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1));
+        const float ang = 6.28318530717958647692f * u2;
+        z[2 * p] = rad * __cosf(ang);
+        z[2 * p + 1] = rad * __sinf(ang);
+      }
+    }
+    float act[AD], raw[AD], lp[AD];
+#pragma unroll
+    for (int c = 0; c < AD; c++) {
+      raw[c] = fma_(std_a[c], z[c], mean[c]);
+      lp[c] = fma_(-0.5f * z[c], z[c], -ls_a[c]) - 0.918938533204672742f;
+      act[c] = clamp_(raw[c], c == 0 ? 0.0f : -1.0f, c == 0 ? 2.0f : 1.0f);
+    }
+    const float logp = (lp[0] + lp[1]) + (lp[2] + lp[3]);       // (the quad form's sum4 association)
+    const size_t tn = size_t(t) * n;
+    if (active) {
+      *reinterpret_cast<float4*>(io.actions + (tn + i) * AD) = make_float4(raw[0], raw[1], raw[2], raw[3]);
+      io.logp[tn + i] = logp; io.values[tn + i] = value;
+    }
+    // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
+    sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
+    float reward; bool was_reset; int ep_len; float ep_ret;
+    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len, ep_ret);
+    any_reset |= was_reset;
+    const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
+    accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);
+    if constexpr (NORM) {
+      if (is_done && sio.terminal_obs) {                          // (this lane wrote the row inside step_lane)
+        float* tr = sio.terminal_obs + size_t(i) * OD;
+#pragma unroll
+        for (int j = 0; j < OD; j++) {
+          const float x = float((double(tr[j]) - md[j]) * md[OD + j]);
+          tr[j] = x < -N.clip ? -N.clip : (x > N.clip ? N.clip : x);
+        }
+      }
+    }
+    if (active) {
+      io.rewards[tn + i] = reward;
+      io.dones[tn + i] = is_done ? 1 : 0;
+      if (io.info) io.info[tn + i] = bits;
+    }
+    publish_obs(io.obs + (tn + n + i) * OD, count);              // row t + 1, and the next step's MLP input
+  }
+  if (mine) {
+    store_env_step<float, KW, 0>(tile, tl, e, K);
+    if (any_reset) store_env_episode<float, KW>(K, tile, tl, e);
+  }
+  if constexpr (NORM) {
+    if (N.update != 0) {   // one reduction per env wavefront (lanes without an active env hold zeros), one atomic per column and wavefront
+#pragma unroll
+      for (int j = 0; j < OD; j++) {
+        double a = s1[j], b = s2[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+        if (lane == 0) { atomicAdd(N.buf + 2 * OD + 1 + j, a); atomicAdd(N.buf + 3 * OD + 1 + j, b); }
+      }
+    }
+  }
+}
+
+}  // namespace amenv_dev

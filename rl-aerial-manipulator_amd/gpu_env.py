@@ -166,11 +166,19 @@ class GpuWaypointEnv:
                                            self._stream()), "amenv_rollout")
         return out
 
-    def rollout_policy(self, flat_params, n_steps, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits=None, terminal_obs=None):
+    def rollout_policy(self, flat_params, n_steps, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits=None, terminal_obs=None,
+                       obs_normalizer=None, update_normalizer=True):
         """T closed-loop steps in ONE launch: obs -> actor / critic MLPs (bf16 matrix cores) -> Gaussian sample -> clip -> env step,
         writing SB3's rollout-buffer rows: obs [T+1,N,OD] (row 0 = observation at entry), actions [T,N,A] raw samples, logp / values /
         rewards [T,N] f32, dones [T,N] u8, optionally info_bits [T,N] i32 and terminal_obs [T,N,OD].  Caller-owned contiguous tensors on
-        this env's device.  Built for the fp32 hexacopter + arm (include/amenv.h amenv_rollout_policy)."""
+        this env's device.  Built for fp32 envs: the rigid vehicles with 4 or 6 rotors on every task, and the hexacopter + z,x,x arm on the
+        single-waypoint v2 task (include/amenv.h amenv_rollout_policy).
+
+        obs_normalizer (an `ObsNormalizer` of dim obs_dim on this device; rigid vehicles only): the normaliser runs INSIDE the launch
+        (amenv_rollout_policy_norm) with its clip_obs / epsilon.  Its statistics are FROZEN for the launch: every row written (obs,
+        terminal_obs) and the policy's input are normalised with the statistics at entry, bit-identical to `obs_normalizer.normalize(raw)`.
+        update_normalizer: afterwards the statistics have merged the raw rows 1..T (not row 0, not the terminal rows), as T per-step
+        VecNormalize updates would to fp64 rounding; False (evaluation) leaves them untouched."""
         T, n = int(n_steps), self.num_envs
         want = {"obs": ((T + 1, n, self.obs_dim), torch.float32), "actions": ((T, n, self.act_dim), torch.float32), "logp": ((T, n), torch.float32),
                 "values": ((T, n), torch.float32), "rewards": ((T, n), torch.float32), "dones": ((T, n), torch.uint8)}
@@ -187,8 +195,13 @@ class GpuWaypointEnv:
         fp = flat_params.detach()
         if fp.device != self.device or fp.dtype != torch.float32 or not fp.is_contiguous():
             raise L.AmenvError("rollout_policy: flat_params must be a contiguous fp32 tensor on this env's device")
-        self._check(self.lib.amenv_rollout_policy(self._h, T, p(fp), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFF, p(obs), p(actions), p(logp),
-                                                  p(values), p(rewards), p(dones), p(info_bits), p(terminal_obs), self._stream()), "amenv_rollout_policy")
+        tail = (T, p(fp), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFF, p(obs), p(actions), p(logp), p(values), p(rewards), p(dones),
+                p(info_bits), p(terminal_obs), self._stream())
+        if obs_normalizer is None:
+            self._check(self.lib.amenv_rollout_policy(self._h, *tail), "amenv_rollout_policy")
+        else:
+            self._check(self.lib.amenv_rollout_policy_norm(self._h, obs_normalizer._h, 1 if update_normalizer else 0, float(obs_normalizer.clip_obs),
+                                                           float(obs_normalizer.epsilon), *tail), "amenv_rollout_policy_norm")
 
     def observe(self):
         o = torch.empty(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)

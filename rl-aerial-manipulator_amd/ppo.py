@@ -560,8 +560,9 @@ class PPO:
         # opt-in: the whole rollout (policy MLPs on the bf16 matrix cores, sampling, clip, env step) in ONE launch -- amenv_rollout_policy
         self.fused_rollout = bool(fused_rollout)
         self.fused_rollout_fp32_stats = bool(fused_rollout_fp32_stats)   # fused rollout: store the fp32 policy's log-probs / values (SB3's buffer semantics)
-        if self.fused_rollout and obs_normalizer is not None:
-            raise L.AmenvError("fused_rollout does not go through an observation normaliser")
+        if self.fused_rollout and obs_normalizer is not None and int(env.cfg.vehicle.n_joints) != 0:
+            raise L.AmenvError("fused_rollout with an observation normaliser is built for the rigid vehicles (amenv_rollout_policy_norm); "
+                               "arm vehicles: fused_rollout without a normaliser, or the step-by-step rollout")
         self._term_obs = self._info = None
         self.num_timesteps = 0
         self.log = []
@@ -617,16 +618,24 @@ class PPO:
         kernel.  What stays on the host side of the launch: the time-limit bootstrap reward += gamma V(terminal_observation) (one critic
         call over the truncated entries), V of the last observation, GAE.  The rollout policy is the bf16 rounding of the fp32 policy the
         update differentiates (means differ by ~1e-2 of their scale): PPO's clipped ratio absorbs that; log-probs are those of the
-        samples under the means the kernel used."""
+        samples under the means the kernel used.
+
+        With an observation normaliser (rigid vehicles) it runs inside the launch (amenv_rollout_policy_norm): the statistics are FROZEN for
+        the rollout -- every buffer row, the policy's input and the terminal rows are normalised with the statistics at its start -- and
+        merge the raw rows 1..n_steps once at its end, where SB3's VecNormalize updates them before every step.  The policy and the learner
+        see the same rows; the step-by-step path keeps SB3's order."""
         b, env, pol, T = self.buffer, self.env, self.policy, self.n_steps
+        norm = self.obs_normalizer
         if not self._started:
-            env.reset()
+            obs = env.reset()
+            if norm is not None:   # as _first_obs: the reset rows count once, row 0 of the first launch is not counted again
+                norm.update(obs)
             self._started = True
         if self._term_obs is None:
             self._term_obs = torch.zeros(T, env.num_envs, env.obs_dim, dtype=torch.float32, device=self.device)
             self._info = torch.zeros(T, env.num_envs, dtype=torch.int32, device=self.device)
         env.rollout_policy(pol.flat_param, T, self.seed, self._draw, b.obs, b.actions, b.logp, b.values, b.rewards, b.dones, self._info,
-                           self._term_obs if self.bootstrap_truncated else None)
+                           self._term_obs if self.bootstrap_truncated else None, obs_normalizer=norm)
         self._draw += T
         if self.fused_rollout_fp32_stats:
             # SB3's buffer holds log pi(a|s) and V(s) of the policy the update differentiates: re-evaluate the T*N rows with the fp32 policy (the

@@ -1,7 +1,10 @@
 """Closed-loop rollout rate: policy inference + Gaussian sampling + env step, everything on the GPU (what `PPO.collect_rollouts`
 and `evaluate_policy` do per step).  Compares the one-launch policy forward (`amenv_policy_forward`) with the torch modules.
+--one-launch: PPO's rollout collection instead -- the whole T-step closed loop as ONE launch (amenv_rollout_policy, and with
+--normalize-obs amenv_rollout_policy_norm) next to the step-by-step path (one launch per operation per step), HIP-event time per step.
 
-    python tools/rollout_rate.py [--envs 4096] [--steps 2000] [--vehicle quad]
+    python tools/rollout_rate.py [--envs 4096] [--steps 2000] [--vehicle quad] [--task v2|v1_scaled|v1_raw]
+    python tools/rollout_rate.py --one-launch --task v1_raw [--normalize-obs] [--envs 4096 32768] [--rollout-steps 64]
 """
 import argparse
 import json
@@ -16,12 +19,44 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 32768])
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--vehicle", default="quad")
+    ap.add_argument("--task", default="v2", choices=["v2", "v1_scaled", "v1_raw"])
+    ap.add_argument("--one-launch", action="store_true", help="time PPO.collect_rollouts: one launch per rollout vs the step-by-step path")
+    ap.add_argument("--normalize-obs", action="store_true", help="with --one-launch: an ObsNormalizer in both paths (inside the launch / per step)")
+    ap.add_argument("--rollout-steps", type=int, default=64, help="with --one-launch: T steps per rollout")
+    ap.add_argument("--reps", type=int, default=10, help="with --one-launch: timed rollouts per path")
     a = ap.parse_args()
     import torch
     import rl_aerial_manipulator_amd as amd
     out = {}
+    if a.one_launch:
+        from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
+        from rl_aerial_manipulator_amd.ppo import PPO
+        for n in a.envs:
+            for fused in (True, False):
+                env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0)
+                norm = ObsNormalizer(env.obs_dim) if a.normalize_obs else None
+                algo = PPO(env, obs_normalizer=norm, fused_rollout=fused, n_steps=a.rollout_steps, seed=0)
+                algo.fused_rollout_fp32_stats = False        # time the rollout itself: no fp32 re-evaluation of the buffer behind it
+                algo.bootstrap_truncated = False             # (both paths: no critic call over the terminal rows)
+                for _ in range(3):
+                    algo.collect_rollouts()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                torch.cuda.synchronize()
+                ev[0].record()
+                for _ in range(a.reps):
+                    algo.collect_rollouts()
+                ev[1].record()
+                torch.cuda.synchronize()
+                us = ev[0].elapsed_time(ev[1]) * 1e3 / (a.reps * a.rollout_steps)
+                out[f"{n}_{'one_launch' if fused else 'step_by_step'}"] = {"us_per_step": us, "env_steps_per_s": n / us * 1e6}
+                env.close()
+                if norm is not None:
+                    norm.close()
+        print(json.dumps({"vehicle": a.vehicle, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
+                          "loop": "PPO.collect_rollouts (policy + sample + clip + step [+ normaliser] x T, GAE)", "results": out}))
+        sys.exit(0)
     for n in a.envs:
-        env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, seed=0)
+        env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0)
         pol = amd.ActorCritic(env.obs_dim, env.act_dim).to(env.device).flatten_()
         for mode in ("fused", "torch"):
             obs = env.reset()
@@ -47,4 +82,4 @@ if __name__ == "__main__":
             out[f"{n}_{mode}"] = {"eager_us_per_step": dt / a.steps * 1e6, "graph_us_per_step": dg / (a.steps // 16 * 16) * 1e6,
                                   "graph_env_steps_per_s": n * (a.steps // 16 * 16) / dg}
         env.close()
-    print(json.dumps({"vehicle": a.vehicle, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
+    print(json.dumps({"vehicle": a.vehicle, "task": a.task, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
