@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--resume", default=None, help="SB3 zip / policy.pth to start from (rl_train.py:33-35)")
     ap.add_argument("--save", default="waypoint_controller_gpu")         # rl_train.py:57
     ap.add_argument("--vehicle", default="quad")
+    ap.add_argument("--n-joints", type=int, default=None, help="hexa_arm: the default arm cut to its first 1..3 links (obs 23 + 2 n, actions 4 + n)")
     ap.add_argument("--task", default="v2", choices=["v2", "v1_scaled", "v1_raw"],
                     help="v2: rl_train.py's env; v1_scaled / v1_raw: the v1 env files (rl_train_vecN.py imports rl_env = v1_raw) with rl_train_vecN.py's recipe")
     ap.add_argument("--normalize-obs", action="store_true", help="observation normaliser (VecNormalize(norm_obs=True, norm_reward=False), rl_train_vecN.py:10-11)")
@@ -52,10 +53,11 @@ def main():
     dist = sharding.init_process_group("nccl", torch.device("cuda", local))
     cfg = None
     if a.moment_scale is not None:
-        cfg = amd._lib.default_config(a.vehicle, a.envs, a.task)
+        cfg = amd._lib.default_config(a.vehicle, a.envs, a.task, n_joints=a.n_joints)
         cfg.vehicle.moment_scale = a.moment_scale
         cfg.seed, cfg.env_id_offset = a.seed, sh.env_id_offset
-    env = amd.GpuWaypointEnv(a.envs, device=local, vehicle=a.vehicle, seed=a.seed, env_id_offset=sh.env_id_offset, config=cfg, task=a.task)
+    env = amd.GpuWaypointEnv(a.envs, device=local, vehicle=a.vehicle, seed=a.seed, env_id_offset=sh.env_id_offset, config=cfg, task=a.task,
+                             n_joints=a.n_joints)
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,

@@ -314,20 +314,23 @@ int amenv_gae(const float* rewards, const float* values, const uint8_t* dones, c
               float* returns, int32_t n_steps, int64_t n_envs, float gamma, float gae_lambda, void* stream);
 /* DiagGaussianDistribution.sample + log_prob + the action-space clip of collect_rollouts: raw = mean + exp(log_std) z,
  * clipped = clip(raw, low, high) (bounds v2/rl_env_scaledObs.py:20-24), logp = log N(raw; mean, exp(log_std)) summed over
- * act_dim (4 or 7).  z from Philox4x32-10 keyed by (seed, env_id_offset + i, draw): pass a different `draw` per call. */
+ * act_dim (4; 5, 6 or 7 = 4 + the arm's joints).  z from Philox4x32-10 keyed by (seed, env_id_offset + i, draw): pass a different `draw`
+ * per call.  Entry k draws block k / 4, entry k % 4 of it, whatever act_dim is: for the same key the first 4 + n entries of a 4 + n action
+ * row are bit-identical to those of a 7-entry row with the same mean and log_std prefixes. */
 int amenv_gaussian_act(const float* mean, const float* log_std, const float* low, const float* high, float* raw, float* clipped,
                        float* logp, int64_t n_envs, int32_t act_dim, uint64_t seed, uint32_t draw, int64_t env_id_offset, void* stream);
 /* Forward pass of the reference's policy network (SB3 MlpPolicy, net_arch [128, 64, 64], tanh, separate actor / critic trunks;
  * v2/rl_train.py:27-30) in ONE launch: mean_out [n, act_dim] = action_net(pi trunk(obs)), value_out [n] = value_net(vf trunk(obs));
  * either output may be NULL.  flat_params = the policy's parameters in SB3 state-dict order in one contiguous fp32 buffer
  * (log_std, mlp_extractor.policy_net.{0,2,4}.{weight,bias}, mlp_extractor.value_net.{0,2,4}.{weight,bias}, action_net, value_net:
- * 30,537 floats for 20-D / 4-D).  (obs_dim, act_dim) in {(20,4), (29,7), (17,4)}. */
+ * 30,537 floats for 20-D / 4-D).  (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6)} (v2 | hexacopter + 3-link arm | v1 |
+ * hexacopter + 1- / 2-link arm). */
 int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out,
                          float* value_out, void* stream);
 
 /* amenv_policy_forward for large batches (the rollout buffer's values / log-probabilities, a 32768-env policy step): the same outputs
  * from the training kernel's arithmetic -- fp32 products as six bf16 MFMAs on exactly split operands (see amenv_ppo_mlp_step) -- in two
- * launches (weight packing, forward).  workspace: amenv_ppo_mlp_workspace_bytes() bytes, 16-byte aligned (the same area may serve
+ * launches (weight packing, forward); the (obs_dim, act_dim) pairs of amenv_policy_forward.  workspace: amenv_ppo_mlp_workspace_bytes() bytes, 16-byte aligned (the same area may serve
  * amenv_ppo_mlp_step: both rewrite its weight part from flat_params on every call). */
 int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out,
                               float* value_out, void* workspace, void* stream);
@@ -342,11 +345,13 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
  * with 2..4 waypoints or a set block_size one lane per env runs the arithmetic of the LANE / HELPER step kernels (replay through amenv_step
  * on a handle created with AMENV_KERNEL_LANE is bit for bit); both rigid forms run the first layer on two-part bf16 inputs and weights,
  * which holds the action within 3e-2 of the fp32 policy's on the reference checkpoint, and draw the same noise -- and the 6-rotor vehicle
- * with the z,x,x 3-joint arm on the single-waypoint v2 task (obs_dim 29, act_dim 7); fp64 envs, arms with 2..4 waypoints and arms of 1 or
- * 2 joints return AMENV_ERR_INVALID.  For the arm vehicle the env part is the arithmetic of the kernel amenv_step
- * runs for this env (16 lanes per env where that is the lane-team kernel, else one lane per env with the arithmetic of the LANE / HELPER step
- * kernels: replaying the recorded clipped actions through amenv_step on such a handle reproduces every row bit for bit; a handle whose
- * amenv_step runs the STAGED kernel agrees to rounding); both forms draw the same noise.  An opt-in ROLLOUT mode: bf16
+ * with a 1-, 2- or 3-link arm (obs_dim 23 + 2 n, act_dim 4 + n) on the v2 task with 1..4 waypoints, any joint axes; fp64 envs return
+ * AMENV_ERR_INVALID.  For the 3-link z,x,x arm on one waypoint the env part is the arithmetic of the kernel amenv_step runs for this env
+ * (16 lanes per env where that is the lane-team kernel, else one lane per env with the arithmetic of the LANE / HELPER step kernels:
+ * replaying the recorded clipped actions through amenv_step on such a handle reproduces every row bit for bit; a handle whose amenv_step
+ * runs the STAGED kernel agrees to rounding); every other arm config runs the one-lane-per-env form at every batch size (replay through a
+ * handle created with AMENV_KERNEL_LANE is bit for bit).  A 1- or 2-link arm publishes its own row widths (the columns amenv_step
+ * returns); its phantom joints get 0 commands and no log-probability terms.  All forms draw the same noise.  An opt-in ROLLOUT mode: bf16
  * rounding perturbs the action means by ~1e-2 of their scale; log-probs are those of the samples under the means actually used.
  *   flat_params  fp32 policy parameters in SB3 state-dict order (see amenv_policy_forward)
  *   obs          [n_steps + 1, N, obs_dim] f32: row 0 <- observation at entry, row t + 1 <- after step t (post-reset for done envs)
@@ -375,7 +380,7 @@ int amenv_rollout_policy_norm(amenv* env, amenv_obsnorm* norm, int32_t update, f
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of
  *   L = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
- * with respect to mean [n, act_dim], value [n] and log_std [act_dim] (act_dim 4 or 7).  stats4 = {policy_loss, value_loss,
+ * with respect to mean [n, act_dim], value [n] and log_std [act_dim] (act_dim 4, 5, 6 or 7).  stats4 = {policy_loss, value_loss,
  * entropy_loss, clip_fraction}.  Deterministic (fixed-order reductions, no atomics).  workspace: device buffer of
  * amenv_ppo_workspace_bytes() bytes, 8-byte aligned.  Hyper-parameters of the reference: clip .2, ent 5e-4, vf .5 (v2/rl_train.py:38-53). */
 size_t amenv_ppo_workspace_bytes(void);
@@ -391,7 +396,7 @@ int amenv_ppo_loss_grad(const float* mean, const float* value, const float* log_
  * (v_mfma_f32_32x32x16_bf16, fp32 accumulation; what is dropped is below one fp32 rounding), so the result is as close to the same loss in
  * fp64 as autograd on the fp32 torch modules is (tests/test_gpu_ppo.py).  flat_params / flat_grad: the policy's parameters / their gradients in SB3 state-dict order (see
  * amenv_policy_forward); obs [n, obs_dim], actions [n, act_dim], old_logp / advantages / returns [n] f32; stats4 as amenv_ppo_loss_grad.
- * (obs_dim, act_dim) in {(20,4), (29,7), (17,4)}.  index: NULL, or n row numbers -- minibatch sample s is row index[s] of obs / actions /
+ * (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6)}.  index: NULL, or n row numbers -- minibatch sample s is row index[s] of obs / actions /
  * old_logp / advantages / returns (SB3 draws its minibatches as slices of a permutation of the rollout buffer, RolloutBuffer.get: the
  * gather happens inside the kernel, the rollout tensors stay where they are).  Deterministic: no atomics on the gradient path.
  * workspace: amenv_ppo_mlp_workspace_bytes() bytes, 16-byte aligned. */
@@ -457,11 +462,12 @@ int amenv_minsnap_eval(int32_t n_segments, int64_t n_query, const double* coeff,
  * per episode a ONE-segment rest-to-rest minimum-snap trajectory from where the episode started to the waypoint at `speed` m/s, tracked
  * by the PID; thrust scaled by mass, moments by inertia_ratio (this vehicle's inertia / the reference quadrotor's, per axis) and the
  * moment vector scaled into the action box.  One launch: observation rows in, action rows out.
- *   obs     [n, obs_dim] f32, v2 layout (rl_env_scaledObs.py:98-121), obs_dim >= 20 (29 with the arm)
+ *   obs     [n, obs_dim] f32, v2 layout (rl_env_scaledObs.py:98-121), obs_dim >= 20 (23 + 2 n with an n-link arm)
  *   done    [n] u8 or NULL: envs whose episode ended on the previous step (auto-reset => a new trajectory starts)
  *   pstate  [n, 14] (dtype) in/out: t, start (3), goal (3), integrals (6), fresh; initialise to {0 x 13, 1}
  *   actions [n, act_dim] f32, act_dim >= 4: thrust / (m g) in [0, 2], moments in [-1, 1]; entries 4.. (arm joints) = 0 (home)
- * tool_mode = 1 (arm vehicle with AMENV_EE_TASK_TOOL, obs_dim 29): the position loop tracks the tool point instead of the base. */
+ * tool_mode = 1 (arm vehicle with AMENV_EE_TASK_TOOL, obs_dim >= 23): the position loop tracks the tool point instead of the base; the
+ * tool offset is read from the LAST three columns of the row (26..28 for the 3-link arm, 22..24 / 24..26 for 1 / 2 links). */
 typedef struct amenv_pid_policy_params {
   amenv_pid_params pid;
   double speed;            /* m/s along the segment (runsim.py:27 flies 1.2) */

@@ -137,11 +137,18 @@ def load():
     return _lib
 
 
-def default_config(vehicle="quad", num_envs=1, task="v2"):
+def default_config(vehicle="quad", num_envs=1, task="v2", n_joints=None):
+    """n_joints (hexa_arm only): 1..3, the default arm cut to its first n_joints links; the dropped links' masses leave vehicle.mass."""
+    if n_joints is not None and (vehicle != "hexa_arm" or int(n_joints) not in (1, 2, 3)):
+        raise AmenvError(f"default_config: n_joints={n_joints!r} needs vehicle='hexa_arm' and 1..3 (got vehicle={vehicle!r})")
     cfg = Config()
     rc = load().amenv_default_config(vehicle.encode(), num_envs, C.byref(cfg))
     if rc == 0 and task != "v2":
         rc = load().amenv_config_set_task(C.byref(cfg), TASKS[task])
     if rc != 0:
         raise AmenvError(load().amenv_last_error(None).decode())
+    if n_joints is not None:
+        nj = int(n_joints)
+        cfg.vehicle.mass = cfg.vehicle.mass - sum(cfg.vehicle.link_mass[nj:cfg.vehicle.n_joints])
+        cfg.vehicle.n_joints = nj
     return cfg

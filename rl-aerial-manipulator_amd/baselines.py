@@ -306,7 +306,7 @@ class PidWaypointPolicy:
     def _predict_hip(self, obs, done):
         n, pid = self.pstate.shape[0], self.pid
         obs = obs.contiguous()
-        assert obs.is_cuda and obs.dtype == torch.float32 and obs.shape[0] == n and obs.shape[1] >= (29 if self.tool_mode else 20)
+        assert obs.is_cuda and obs.dtype == torch.float32 and obs.shape[0] == n and obs.shape[1] >= (23 if self.tool_mode else 20)
         if done is not None:
             done = done.to(torch.uint8).contiguous()
         p = _lib.PidPolicyParams(pid=pid.params(), speed=self.speed, moment_scale=self.moment_scale, obs_dim=obs.shape[1], act_dim=self.act_dim,

@@ -243,7 +243,8 @@ __global__ __launch_bounds__(256) void minsnap_eval_kernel(int n, int64_t m, con
 
 // ---- the baseline as an action source for the waypoint environment ------------------------------------------------------------------
 // pst [n][14]: t, start (3), goal (3), integral (6), fresh (1 = the next call starts an episode).  obs rows in the v2 layout
-// (v2/rl_env_scaledObs.py:98-121: p/10, v/5, q, w/5, (waypoint - task point)/2, ...; with the arm obs[26:29] = (tool - base)/0.5).
+// (v2/rl_env_scaledObs.py:98-121: p/10, v/5, q, w/5, (waypoint - task point)/2, ...; with an n-link arm the last three columns
+// obs[obs_dim-3 : obs_dim] = (tool - base)/0.5: columns 26..28 for 3 links, 22..24 / 24..26 for 1 / 2).
 // tool_mode = 1 (arm vehicle whose task measures from the tool point): the position loop tracks the TOOL point.
 template <typename T>
 __global__ __launch_bounds__(256) void pid_policy_kernel(PidPolicyParams P, const float* __restrict__ obs, const uint8_t* __restrict__ done,
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(256) void pid_policy_kernel(PidPolicyParams P, cons
   for (int k = 0; k < 4; k++) q[k] = T(o[6 + k]);
   if (P.tool_mode) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) pos[k] += T(o[26 + k]) * T(0.5);
+    for (int k = 0; k < 3; k++) pos[k] += T(o[P.obs_dim - 3 + k]) * T(0.5);
   }
 #pragma unroll
   for (int k = 0; k < 3; k++) goal[k] = pos[k] + T(o[13 + k]) * T(2);

@@ -360,6 +360,9 @@ bool quad_ok(const amenv_config& c) {
 bool team_ok(const amenv_config& c) { return c.dtype == AMENV_F32 && zxx_arm1(c); }
 // one-lane-per-env closed loop of the rigid vehicles (amenv_rigid_policy.hpp): fp32, 4 or 6 rotors, every task, any workgroup size
 bool rigid_pol_ok(const amenv_config& c) { return c.vehicle.n_joints == 0 && c.dtype == AMENV_F32 && (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6); }
+// closed loop (amenv_rollout_policy) of an fp32 arm vehicle: every one of them -- 1..3 joints (the internal, phantom-padded config has 3),
+// 1..4 waypoints, any joint axes.  The team kernel where the step runs it (team_ok, family Team), the lane form (amenv_lane_policy.hpp) elsewhere
+bool arm_pol_ok(const amenv_config& c) { return c.vehicle.n_joints == 3 && c.dtype == AMENV_F32; }
 
 constexpr int kTeamAutoMax = 6144;    // AUTO: lane-team kernel up to this batch
 constexpr int kArmkAutoMax = 32768;   // AUTO: stage-wave kernel up to this batch
@@ -603,13 +606,38 @@ PolicyIO policy_io(amenv& e, const float* flat_params, uint64_t seed, uint32_t d
                    uint8_t* dones, uint32_t* info_bits, float* terminal_obs, hipStream_t s) {
   // parameters -> bf16 MFMA fragments + per-lane action constants (they change every PPO iteration): a tiny kernel in front, no host sync
   const int pack_threads = 4 * (kPolFrags + kPolBias) * 64 + 64 + 4 * 4 * 64;
-  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, e.obs_dim, e.act_dim, e.pol_pack);
+  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, e.obs_dim, e.act_dim, e.io_act ? e.pub_nj : 0, e.pol_pack);
   PolicyIO io;
   io.pack = reinterpret_cast<const uint4*>(e.pol_pack);
   io.seed_lo = uint32_t(seed); io.seed_hi = uint32_t(seed >> 32); io.draw0 = draw0;
   io.obs = obs; io.actions = actions; io.logp = logp; io.values = values; io.rewards = rewards; io.dones = dones; io.info = info_bits;
   io.terminal_obs = terminal_obs;
   return io;
+}
+
+// amenv_rollout_policy, arm vehicles outside the team kernel's range: one lane per env (amenv_lane_policy.hpp; 64 envs per workgroup up to
+// 16384 envs, 128 above: one workgroup per CU either way).  PNJ: the caller's joints (a 1- / 2-link arm publishes its own row widths)
+template <int KW, int PNJ>
+hipError_t launch_lane_policy_k(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
+  ArmArg<float, 3> AA;
+  AA.p = make_arm<float>(e);
+  const HotParams<float, 6> HP = make_hot<float, 6>(e);
+  const int n = e.cfg.num_envs;
+  if (n <= 16384)
+    hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 1, KW, PNJ>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, make_cold(e), AA, e.io_term);
+  else
+    hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 2, KW, PNJ>), dim3((e.n_tiles + 1) / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, make_cold(e), AA,
+                       e.io_term);
+  return hipGetLastError();
+}
+template <int KW>
+hipError_t launch_lane_policy_kw(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
+  if (e.pub_nj == 1) return launch_lane_policy_k<KW, 1>(e, T, io, s);
+  if (e.pub_nj == 2) return launch_lane_policy_k<KW, 2>(e, T, io, s);
+  return launch_lane_policy_k<KW, 3>(e, T, io, s);
+}
+hipError_t launch_lane_policy(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
+  return e.cfg.task.num_waypoints == 1 ? launch_lane_policy_kw<1>(e, T, io, s) : launch_lane_policy_kw<AMENV_MAX_WAYPOINTS>(e, T, io, s);
 }
 
 template <typename V>
@@ -801,7 +829,7 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
     return alloc_failed("device allocation failed", s);
   // the lane-quad / fp32 lane-team constants (every kernel of theirs: step, rollout, closed-loop rollout) + the packed policy of amenv_rollout_policy
   const bool quad = quad_ok(*cfg), team = team_ok(*cfg);
-  if (quad || team || rigid_pol_ok(*cfg))
+  if (rigid_pol_ok(*cfg) || arm_pol_ok(*cfg))   // (quad_ok implies rigid_pol_ok, team_ok arm_pol_ok)
     if ((s = hipMalloc((void**)&e->pol_pack, size_t(kPolPackWords) * sizeof(uint32_t))) != hipSuccess) return alloc_failed("policy pack", s);
   if ((quad || team) && (s = upload_team_consts<float>(e, team)) != hipSuccess) return alloc_failed(quad ? "quad constants" : "team constants", s);
   if (family == StepFamily::Team && cfg->dtype == AMENV_F64 && (s = upload_team_consts<double>(e, true)) != hipSuccess) return alloc_failed("team constants (fp64)", s);
@@ -940,10 +968,9 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   const bool quad = quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
-  if (!quad && !rigid && !team_ok(e->cfg))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with the "
-                "z,x,x arm on the single-waypoint v2 task");
-  if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: arms with 1 or 2 joints are served through amenv_step");
+  if (!quad && !rigid && !arm_pol_ok(e->cfg))
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
+                "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");
   if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
   if (rigid && (!aligned16(obs) || !aligned16(actions) || (terminal_obs && !aligned16(terminal_obs))))
@@ -959,23 +986,15 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
     else hipLaunchKernelGGL((rollout_policy_kernel_quad<6>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
   } else if (rigid) {   // every other rigid config (v1 tasks, 2..4 waypoints, a set workgroup size): one lane per env (amenv_rigid_policy.hpp)
     AMENV_HIP(e, launch_rigid_policy<false>(*e, (int)n_steps, io, NormArg{nullptr, 0.0f, 0.0, 0}, s));
-  } else if (e->family == StepFamily::Team) {
+  } else if (e->family == StepFamily::Team && !e->io_act) {   // the caller's vehicle is the 3-joint z,x,x arm on one waypoint
     // The env part follows the step kernel's choice: 16 lanes per env where amenv_step runs the lane-team kernel (small batches).  One 16-env
     // workgroup per CU up to 4096 envs (5.15 vs 5.22 us per step there); above that the variant compiled for two wavefronts per SIMD pays
     // (measured on MI355X at 8192 envs: 7.9 vs 10.1 us per step)
     const TeamParams TP = make_team<float>(*e);
     if (n <= 4096) hipLaunchKernelGGL((rollout_policy_kernel_team<6, 1>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
     else hipLaunchKernelGGL((rollout_policy_kernel_team<6, 2>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
-  } else {
-    // every other arm family: one lane per env (amenv_lane_policy.hpp; 64 envs per workgroup up to 16384 envs, 128 above: one workgroup per CU either way)
-    ArmArg<float, 3> AA;
-    AA.p = make_arm<float>(*e);
-    const HotParams<float, 6> HP = make_hot<float, 6>(*e);
-    if (n <= 16384)
-      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 1>), dim3(e->n_tiles), dim3(320), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, HP, make_cold(*e), AA);
-    else
-      hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 2>), dim3((e->n_tiles + 1) / 2), dim3(384), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, HP,
-                         make_cold(*e), AA);
+  } else {   // every other fp32 arm config: one lane per env
+    AMENV_HIP(e, launch_lane_policy(*e, (int)n_steps, io, s));
   }
   AMENV_HIP(e, hipGetLastError());
   e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
@@ -1151,8 +1170,10 @@ int amenv_gaussian_act(const float* mean, const float* log_std, const float* low
   const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
   switch (act_dim) {
     case 4: hipLaunchKernelGGL(gaussian_act_kernel<4>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
+    case 5: hipLaunchKernelGGL(gaussian_act_kernel<5>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
+    case 6: hipLaunchKernelGGL(gaussian_act_kernel<6>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
     case 7: hipLaunchKernelGGL(gaussian_act_kernel<7>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
-    default: return AMENV_ERR_INVALID;   // 4 = quad/hexa, 7 = hexa + 3 joints
+    default: return AMENV_ERR_INVALID;   // 4 = quad/hexa, 4 + n = hexa + n joints
   }
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
@@ -1165,14 +1186,18 @@ int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_
   if (obs_dim == 20 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<20, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 29 && act_dim == 7) hipLaunchKernelGGL((policy_forward_kernel<29, 7>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 17 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<17, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else return AMENV_ERR_INVALID;   // (20,4) v2 | (29,7) hexacopter + arm | (17,4) v1
+  else if (obs_dim == 25 && act_dim == 5) hipLaunchKernelGGL((policy_forward_kernel<25, 5>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 27 && act_dim == 6) hipLaunchKernelGGL((policy_forward_kernel<27, 6>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  else return AMENV_ERR_INVALID;   // (20,4) v2 | (29,7) hexacopter + arm | (17,4) v1 | (25,5) / (27,6) hexacopter + 1- / 2-link arm
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
 int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out, float* value_out,
                               void* workspace, void* stream) {
   if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return AMENV_ERR_INVALID;
-  if (!((obs_dim == 20 && act_dim == 4) || (obs_dim == 29 && act_dim == 7) || (obs_dim == 17 && act_dim == 4))) return AMENV_ERR_INVALID;
+  if (!((obs_dim == 20 && act_dim == 4) || (obs_dim == 29 && act_dim == 7) || (obs_dim == 17 && act_dim == 4) || (obs_dim == 25 && act_dim == 5) ||
+        (obs_dim == 27 && act_dim == 6)))
+    return AMENV_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   uint16_t* WS = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + kMlpWsAdv);   // the split-weight area of amenv_ppo_mlp_step's workspace
   hipLaunchKernelGGL(mlp_pack_kernel, dim3((2 * kMlpPackThreadsPerNet + 255) / 256), dim3(256), 0, s, flat_params, (int)obs_dim, (int)act_dim, WS);
@@ -1182,7 +1207,9 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
   const u32x4* ws = reinterpret_cast<const u32x4*>(WS);
   if (obs_dim == 20) hipLaunchKernelGGL((mlp_forward_kernel<20, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 29) hipLaunchKernelGGL((mlp_forward_kernel<29, 7>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else hipLaunchKernelGGL((mlp_forward_kernel<17, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 17) hipLaunchKernelGGL((mlp_forward_kernel<17, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 25) hipLaunchKernelGGL((mlp_forward_kernel<25, 5>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else hipLaunchKernelGGL((mlp_forward_kernel<27, 6>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
@@ -1204,6 +1231,10 @@ int amenv_ppo_loss_grad(const float* mean, const float* value, const float* log_
     case 4: hipLaunchKernelGGL(ppo_loss_grad<4>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
                                (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
     case 7: hipLaunchKernelGGL(ppo_loss_grad<7>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
+                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
+    case 5: hipLaunchKernelGGL(ppo_loss_grad<5>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
+                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
+    case 6: hipLaunchKernelGGL(ppo_loss_grad<6>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
                                (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
     default: return AMENV_ERR_INVALID;
   }
@@ -1244,6 +1275,8 @@ int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_di
   if (obs_dim == 20 && act_dim == 4) st = launch_mlp_step<20, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else if (obs_dim == 29 && act_dim == 7) st = launch_mlp_step<29, 7>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else if (obs_dim == 17 && act_dim == 4) st = launch_mlp_step<17, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 25 && act_dim == 5) st = launch_mlp_step<25, 5>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 27 && act_dim == 6) st = launch_mlp_step<27, 6>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else return AMENV_ERR_INVALID;
   if (st != hipSuccess) return AMENV_ERR_HIP;
   const int trunk = kH1 * obs_dim + kH1 + kH2 * kH1 + kH2 + kH3 * kH2 + kH3;
@@ -1355,7 +1388,7 @@ int amenv_minsnap_eval(int32_t n_segments, int64_t n_query, const double* coeff,
 int amenv_pid_policy(const amenv_pid_policy_params* p, int32_t dtype, const float* obs, const uint8_t* done, void* pstate, float* actions,
                      int64_t n, void* stream) {
   if (!p || !pid_params_ok(&p->pid) || !obs || !pstate || !actions || n <= 0 || (dtype != AMENV_F32 && dtype != AMENV_F64) || !(p->speed > 0.0) ||
-      !(p->moment_scale > 0.0) || p->obs_dim < 20 || p->act_dim < 4 || p->act_dim > 16 || (p->tool_mode != 0 && p->obs_dim < 29))
+      !(p->moment_scale > 0.0) || p->obs_dim < 20 || p->act_dim < 4 || p->act_dim > 16 || (p->tool_mode != 0 && p->obs_dim < 23))
     return AMENV_ERR_INVALID;
   PidPolicyParams d;
   d.pid = to_dev(p->pid);

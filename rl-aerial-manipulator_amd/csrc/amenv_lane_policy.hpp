@@ -9,18 +9,31 @@
 //     workgroup: EW = 2 covers 32768 envs with one wave of workgroups on the 256 CUs;
 //   * the two halves alternate: five workgroup barriers per step, activations / action means / values through LDS;
 //   * the action noise is drawn with the team kernel's Philox keying and Box-Muller mapping, the log-probability is summed in its order:
-//     for the same observation both kernels produce the same action, bit for bit.
+//     for the same observation both kernels produce the same action, bit for bit;
+//   * KW = 1 (one waypoint) or AMENV_MAX_WAYPOINTS (2..4), any joint axes (step_lane branches on them);
+//   * PNJ = the caller's joints.  A 1- or 2-link arm runs, inside, the 3-joint vehicle with phantom links (amenv_create pad_arm_config),
+//     exactly as amenv_step does; the kernel publishes the CALLER's rows: obs / terminal_obs 23 + 2 PNJ wide in arm_cut_obs_kernel's
+//     column order, actions 4 + PNJ wide.  The MLP keeps its 29-wide input tile and 7-row head: policy_pack_kernel gives the phantom
+//     inputs and rows zero weights, the phantom joint commands are 0.0f (as arm_pad_actions_kernel pads them) and the log-probability
+//     sums the 4 + PNJ real entries.  A terminal row is written 29 wide by step_lane into a per-env staging row (term29) and cut by
+//     the lane that wrote it.
 #pragma once
 #include "amenv_kernels.hpp"
 #include "amenv_team_policy.hpp"
 
 namespace amenv_dev {
 
-template <int NROT, int EW>
+// column of the internal 29-wide row that feeds column j of the caller's row (arm_cut_obs_kernel's map)
+template <int PNJ>
+__device__ constexpr int arm_pub_src(int j) { return j < 20 + PNJ ? j : (j < 20 + 2 * PNJ ? 23 + (j - 20 - PNJ) : 26 + (j - 20 - 2 * PNJ)); }
+
+template <int NROT, int EW, int KW, int PNJ>
 __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps, const PolicyIO io,
                                                                   unsigned long long* __restrict__ stats, const HotParams<float, NROT> P, const ColdParams C,
-                                                                  const ArmArg<float, 3> AA) {
-  constexpr int OD = 29, AD = 7, NE = 64 * EW, NT = 4 * EW, KW = 1, NJ = 3;   // envs / 16-env column tiles per workgroup
+                                                                  const ArmArg<float, 3> AA, float* __restrict__ term29) {
+  constexpr int OD = 29, AD = 7, NE = 64 * EW, NT = 4 * EW, NJ = 3;   // envs / 16-env column tiles per workgroup
+  constexpr int POD = 23 + 2 * PNJ, PAD = 4 + PNJ;                      // the caller's row widths
+  static_assert(PNJ >= 1 && PNJ <= 3, "1..3 public joints");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
   __shared__ __attribute__((aligned(16))) __bf16 h1[2 * NE * kH1S];       // layer-1 activations; layer 3's reuse the front of it (h1 is dead by then)
   __shared__ __attribute__((aligned(16))) __bf16 h2[2 * NE * kH2S];
@@ -112,8 +125,9 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
   const bool active = i < n_envs;
   const size_t n = size_t(n_envs);
   char* tile = static_cast<char*>(blob) + size_t(i >> 6) * tile_bytes;
+  const int K = KW == 1 ? 1 : P.K;
   Env<float, KW> e;
-  load_env<float, KW, NJ>(1, tile, lane, e);
+  load_env<float, KW, NJ>(K, tile, lane, e);
   // per-entry action constants (policy_pack_kernel's last block: lanes 0..3 hold entry c of the wrench and joint min(c, 2))
   float std_a[AD], ls_a[AD];
   {
@@ -122,7 +136,7 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
     for (int c = 0; c < 4; c++) {
       const uint4 v = ac[c];
       std_a[c] = __uint_as_float(v.x); ls_a[c] = __uint_as_float(v.y);
-      if (c < 3) { std_a[4 + c] = __uint_as_float(v.z); ls_a[4 + c] = __uint_as_float(v.w); }
+      if (c < PNJ) { std_a[4 + c] = __uint_as_float(v.z); ls_a[4 + c] = __uint_as_float(v.w); }
     }
   }
   const int64_t gid = C.gid0 + i;
@@ -130,19 +144,19 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
   const bool ee_task = P.ee_task != 0;
   float o[kObsDimMax];
   update_tool_offset<float, KW, false>(AA.p, e);
-  observe<float, KW, true>(1, e, o, ee_task);
+  observe<float, KW, true>(K, e, o, ee_task);
   observe_joints<float, KW>(e, o);
-  auto publish_obs = [&](float* grow) {                          // observation row -> rollout buffer and (bf16) the MLP's input tile
+  auto publish_obs = [&](float* grow) {                          // observation row -> rollout buffer (the caller's columns) and (bf16) the MLP's input tile
     if (active) {
 #pragma unroll
-      for (int j = 0; j < OD; j++) grow[j] = o[j];
+      for (int j = 0; j < POD; j++) grow[j] = o[arm_pub_src<PNJ>(j)];
     }
     __bf16* xr = xin + el * kXS;
 #pragma unroll
     for (int j = 0; j < OD; j++) xr[j] = (__bf16)o[j];
   };
   { __bf16* xr = xin + el * kXS; xr[OD] = (__bf16)1.0f; xr[OD + 1] = (__bf16)0.0f; xr[OD + 2] = (__bf16)0.0f; }   // bias column, K padding
-  publish_obs(io.obs + size_t(i) * OD);
+  publish_obs(io.obs + size_t(i) * POD);
   bool any_reset = false;
   StepIO sio{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stats};
   for (int t = 0; t < n_steps; t++) {
@@ -182,34 +196,56 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      raw[4 + c] = fma_(std_a[4 + c], z[4 + c], mean[4 + c]);
-      lp[c] = lp[c] + (fma_(-0.5f * z[4 + c], z[4 + c], -ls_a[4 + c]) - 0.918938533204672742f);
-      act[4 + c] = clamp_(raw[4 + c], -1.0f, 1.0f);
+      if (c < PNJ) {
+        raw[4 + c] = fma_(std_a[4 + c], z[4 + c], mean[4 + c]);
+        lp[c] = lp[c] + (fma_(-0.5f * z[4 + c], z[4 + c], -ls_a[4 + c]) - 0.918938533204672742f);
+        act[4 + c] = clamp_(raw[4 + c], -1.0f, 1.0f);
+      } else {
+        act[4 + c] = 0.0f;                                        // a phantom joint: no command
+      }
     }
     const float logp = (lp[0] + lp[1]) + (lp[2] + lp[3]);       // (the team kernel's quad sum, same association)
     const size_t tn = size_t(t) * n;
     if (active) {
-      float* ar = io.actions + (tn + i) * AD;
+      float* ar = io.actions + (tn + i) * PAD;
 #pragma unroll
-      for (int c = 0; c < AD; c++) ar[c] = raw[c];
+      for (int c = 0; c < PAD; c++) ar[c] = raw[c];
       io.logp[tn + i] = logp; io.values[tn + i] = value;
     }
-    // ---- env step (amenv_step's lane kernel code)
-    sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
+    // ---- env step (amenv_step's lane kernel code); a shorter arm's terminal row goes 29 wide to its staging row, then cut below
+    sio.terminal_obs = io.terminal_obs ? (PNJ == 3 ? io.terminal_obs + tn * OD : term29) : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
-    const uint32_t bits = step_lane<float, NROT, KW, VAR_V2, NJ>(P, C, AA, e, act, i, active, reward, o, sio, tile, lane, any_reset, was_reset, ep_len, ep_ret);
+    uint32_t bits;
+    if constexpr (KW == 1) {
+      bits = step_lane<float, NROT, KW, VAR_V2, NJ>(P, C, AA, e, act, i, active, reward, o, sio, tile, lane, any_reset, was_reset, ep_len, ep_ret);
+    } else {   // K made opaque per step: the reset path's waypoint fractions k / K stay in it instead of being hoisted out of the loop and
+      HotParams<float, NROT> Pk = P;   // held in registers for the whole rollout (which spills)
+      int k = Pk.K;
+      asm volatile("" : "+s"(k));
+      Pk.K = k;
+      bits = step_lane<float, NROT, KW, VAR_V2, NJ>(Pk, C, AA, e, act, i, active, reward, o, sio, tile, lane, any_reset, was_reset, ep_len, ep_ret);
+    }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);
+    if constexpr (PNJ < 3) {
+      if (is_done && sio.terminal_obs) {                          // (this lane wrote the staging row inside step_lane)
+        const float* src = term29 + size_t(i) * OD;
+        float* dst = io.terminal_obs + (tn + i) * POD;
+#pragma unroll
+        for (int j = 0; j < POD; j++) dst[j] = src[arm_pub_src<PNJ>(j)];
+      }
+    }
     if (active) {
       io.rewards[tn + i] = reward;
       io.dones[tn + i] = is_done ? 1 : 0;
       if (io.info) io.info[tn + i] = bits;
     }
-    publish_obs(io.obs + (tn + n + i) * OD);                     // row t + 1, and the next step's MLP input
+    publish_obs(io.obs + (tn + n + i) * POD);                    // row t + 1, and the next step's MLP input
   }
-  store_env_step<float, KW, NJ>(tile, lane, e);
-  if (any_reset) store_env_episode<float, KW>(1, tile, lane, e);
+  if constexpr (KW > 1) asm volatile("" : "+v"(tile));          // (the joint groups' addresses are formed here, not kept from the load)
+  store_env_step<float, KW, NJ>(tile, lane, e, K);
+  if (any_reset) store_env_episode<float, KW>(K, tile, lane, e);
 }
 
 }  // namespace amenv_dev

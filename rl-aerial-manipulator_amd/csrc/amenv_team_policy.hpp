@@ -39,9 +39,27 @@ struct PolLayout {
 
 __device__ __forceinline__ uint32_t bf16_bits(float x) { return uint32_t(__builtin_bit_cast(unsigned short, (__bf16)x)); }
 
+// Column of the caller's observation row that feeds input k of the first layer (k == the tile's width: the bias column), -1: a zero
+// weight.  pnj = 0: the caller's row IS the tile (D inputs).  pnj = 1, 2: a 1- / 2-link arm whose env runs the 3-joint vehicle: the
+// tile is the internal 29-wide row (20 | th(3) | thd(3) | tool(3)) and the caller's the 23 + 2 pnj of arm_cut_obs_kernel; the phantom
+// links' th / thd inputs get zero weights, so the MLP depends on the caller's columns only.
+__device__ __forceinline__ int pol_in_col(int k, int D, int pnj) {
+  if (pnj == 0) return k <= D ? k : -1;
+  if (k < 20) return k;
+  if (k < 23) return k - 20 < pnj ? k : -1;
+  if (k < 26) return k - 23 < pnj ? 20 + pnj + (k - 23) : -1;
+  if (k < 29) return 20 + 2 * pnj + (k - 26);
+  return k == 29 ? D : -1;
+}
+__device__ __forceinline__ float pol_w1(const float* W1, const float* b1, int neuron, int k, int D, int pnj) {
+  const int c = pol_in_col(k, D, pnj);
+  return c < 0 ? 0.0f : (c < D ? W1[neuron * D + c] : b1[neuron]);
+}
+
 // fp32 parameters -> MFMA A-operand fragments (bf16) + bias quadruples, in the order the rollout kernel's wavefronts consume them.
-// One thread per (wavefront, item, lane); item < 18: fragment, else bias.
-__global__ void policy_pack_kernel(const float* __restrict__ Pm, int D, int A, uint32_t* __restrict__ out) {
+// One thread per (wavefront, item, lane); item < 18: fragment, else bias.  D, A: the caller's dimensions; pnj: see pol_in_col (the
+// action rows 4 + pnj .. 6 of a shorter arm are zero: row < A below).
+__global__ void policy_pack_kernel(const float* __restrict__ Pm, int D, int A, int pnj, uint32_t* __restrict__ out) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int per_wave = (kPolFrags + kPolBias) * 64;
   if (tid >= 4 * per_wave + 64 + 4 * 4 * 64) return;
@@ -55,7 +73,7 @@ __global__ void policy_pack_kernel(const float* __restrict__ Pm, int D, int A, u
       uint32_t two[2];
       for (int h = 0; h < 2; h++) {
         const int k = 8 * kq + 2 * q + h;
-        const float v = k < D ? W1[neuron * D + k] : (k == D ? b1[neuron] : 0.0f);
+        const float v = pol_w1(W1, b1, neuron, k, D, pnj);
         two[h] = bf16_bits(v - float((__bf16)v));
       }
       o[q] = two[0] | (two[1] << 16);
@@ -68,7 +86,8 @@ __global__ void policy_pack_kernel(const float* __restrict__ Pm, int D, int A, u
     const int l = tid - 4 * per_wave, cc = l & 3, cj = cc < 3 ? cc : 2;
     uint32_t* dst = out + size_t(4 * per_wave + l) * 4;
     dst[0] = __float_as_uint(expf(Pm[cc])); dst[1] = __float_as_uint(Pm[cc]);
-    dst[2] = A > 4 ? __float_as_uint(expf(Pm[4 + cj])) : 0u; dst[3] = A > 4 ? __float_as_uint(Pm[4 + cj]) : 0u;   // (a rigid vehicle has no joint actions)
+    // (a rigid vehicle has no joint actions; a shorter arm's phantom joints have none either: zeros, nothing read past log_std[A - 1])
+    dst[2] = 4 + cj < A ? __float_as_uint(expf(Pm[4 + cj])) : 0u; dst[3] = 4 + cj < A ? __float_as_uint(Pm[4 + cj]) : 0u;
     return;
   }
   const int w = tid / per_wave, item = (tid % per_wave) / 64, l = tid & 63;
@@ -83,7 +102,7 @@ __global__ void policy_pack_kernel(const float* __restrict__ Pm, int D, int A, u
     if (item < 4) {                                   // layer 1: combined tile 4w + item, K = D inputs + the bias column (obs column D = 1)
       const int T = 4 * w + item, net = T >> 3, neuron = 16 * (T & 7) + row;
       const float* W1 = trunk_ptr(net); const float* b1 = W1 + 128 * D;
-      for (int j = 0; j < 8; j++) { const int k = 8 * kq + j; v[j] = k < D ? W1[neuron * D + k] : (k == D ? b1[neuron] : 0.0f); }
+      for (int j = 0; j < 8; j++) v[j] = pol_w1(W1, b1, neuron, 8 * kq + j, D, pnj);
     } else if (item < 12) {                           // layer 2: tile 2w + j, k-step ks
       const int j2 = (item - 4) >> 2, ks = (item - 4) & 3, T = 2 * w + j2, net = T >> 2, neuron = 16 * (T & 3) + row;
       const float* W2 = trunk_ptr(net) + 128 * D + 128;

@@ -32,12 +32,13 @@ class GpuWaypointEnv:
 
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
-                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None):
+                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None):
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
         if config is None:
-            cfg = L.default_config(vehicle, num_envs, task)   # task: "v2" | "v1_scaled" | "v1_raw" (which reference env file)
+            # task: "v2" | "v1_scaled" | "v1_raw" (which reference env file); n_joints (hexa_arm): 1..3 links of the default arm
+            cfg = L.default_config(vehicle, num_envs, task, n_joints=n_joints)
             cfg.seed = seed
             cfg.dtype = L.F64 if dtype in ("f64", torch.float64) else L.F32
             cfg.flags = (L.FLAG_AUTO_RESET if auto_reset else 0) | (L.FLAG_NAN_GUARD if nan_guard else 0)
@@ -171,8 +172,9 @@ class GpuWaypointEnv:
         """T closed-loop steps in ONE launch: obs -> actor / critic MLPs (bf16 matrix cores) -> Gaussian sample -> clip -> env step,
         writing SB3's rollout-buffer rows: obs [T+1,N,OD] (row 0 = observation at entry), actions [T,N,A] raw samples, logp / values /
         rewards [T,N] f32, dones [T,N] u8, optionally info_bits [T,N] i32 and terminal_obs [T,N,OD].  Caller-owned contiguous tensors on
-        this env's device.  Built for fp32 envs: the rigid vehicles with 4 or 6 rotors on every task, and the hexacopter + z,x,x arm on the
-        single-waypoint v2 task (include/amenv.h amenv_rollout_policy).
+        this env's device.  Built for fp32 envs: the rigid vehicles with 4 or 6 rotors on every task, and the hexacopter with a 1-, 2- or
+        3-link arm (any joint axes) on the v2 task with 1..4 waypoints (include/amenv.h amenv_rollout_policy).  OD and A are this env's
+        obs_dim / act_dim: a shorter arm's rows are as amenv_step publishes them (23 + 2 n / 4 + n wide).
 
         obs_normalizer (an `ObsNormalizer` of dim obs_dim on this device; rigid vehicles only): the normaliser runs INSIDE the launch
         (amenv_rollout_policy_norm) with its clip_obs / epsilon.  Its statistics are FROZEN for the launch: every row written (obs,

@@ -109,7 +109,7 @@ class ActorCritic(nn.Module):
         self.flat_param = self.flat_grad = None
 
     # ---- forward pieces -----------------------------------------------------------------------
-    _FUSED_DIMS = {(20, 4), (29, 7), (17, 4)}
+    _FUSED_DIMS = {(20, 4), (29, 7), (17, 4), (25, 5), (27, 6)}   # v2 | hexacopter + 3-link arm | v1 | + 1- / 2-link arm
     MFMA_FORWARD_ROWS = 8192   # batches from here on take amenv_policy_forward_mfma (below: the VALU kernel's shorter latency wins)
 
     def fused_ok(self, obs):
@@ -273,7 +273,7 @@ def gaussian_act(mean, log_std, low, high, raw_out, clipped_out, logp_out, seed,
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, int(env_id_offset),
                                      C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
     if rc != 0:
-        raise L.AmenvError(f"amenv_gaussian_act failed ({rc}): act_dim must be 4 or 7")
+        raise L.AmenvError(f"amenv_gaussian_act failed ({rc}): act_dim must be 4..7")
 
 
 class MinibatchStep:

@@ -5,6 +5,7 @@ and `evaluate_policy` do per step).  Compares the one-launch policy forward (`am
 
     python tools/rollout_rate.py [--envs 4096] [--steps 2000] [--vehicle quad] [--task v2|v1_scaled|v1_raw]
     python tools/rollout_rate.py --one-launch --task v1_raw [--normalize-obs] [--envs 4096 32768] [--rollout-steps 64]
+    python tools/rollout_rate.py --one-launch --vehicle hexa_arm --n-joints 2 [--waypoints 4]
 """
 import argparse
 import json
@@ -20,6 +21,8 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--vehicle", default="quad")
     ap.add_argument("--task", default="v2", choices=["v2", "v1_scaled", "v1_raw"])
+    ap.add_argument("--n-joints", type=int, default=None, help="hexa_arm: the default arm cut to its first 1..3 links")
+    ap.add_argument("--waypoints", type=int, default=1, help="v2 task: waypoints per episode (1..4)")
     ap.add_argument("--one-launch", action="store_true", help="time PPO.collect_rollouts: one launch per rollout vs the step-by-step path")
     ap.add_argument("--normalize-obs", action="store_true", help="with --one-launch: an ObsNormalizer in both paths (inside the launch / per step)")
     ap.add_argument("--rollout-steps", type=int, default=64, help="with --one-launch: T steps per rollout")
@@ -33,7 +36,7 @@ if __name__ == "__main__":
         from rl_aerial_manipulator_amd.ppo import PPO
         for n in a.envs:
             for fused in (True, False):
-                env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0)
+                env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints)
                 norm = ObsNormalizer(env.obs_dim) if a.normalize_obs else None
                 algo = PPO(env, obs_normalizer=norm, fused_rollout=fused, n_steps=a.rollout_steps, seed=0)
                 algo.fused_rollout_fp32_stats = False        # time the rollout itself: no fp32 re-evaluation of the buffer behind it
@@ -52,11 +55,11 @@ if __name__ == "__main__":
                 env.close()
                 if norm is not None:
                     norm.close()
-        print(json.dumps({"vehicle": a.vehicle, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
+        print(json.dumps({"vehicle": a.vehicle, "n_joints": a.n_joints, "waypoints": a.waypoints, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
                           "loop": "PPO.collect_rollouts (policy + sample + clip + step [+ normaliser] x T, GAE)", "results": out}))
         sys.exit(0)
     for n in a.envs:
-        env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0)
+        env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints)
         pol = amd.ActorCritic(env.obs_dim, env.act_dim).to(env.device).flatten_()
         for mode in ("fused", "torch"):
             obs = env.reset()
