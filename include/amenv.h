@@ -376,6 +376,38 @@ int amenv_rollout_policy_norm(amenv* env, amenv_obsnorm* norm, int32_t update, f
                               uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards, uint8_t* dones,
                               uint32_t* info_bits, float* terminal_obs, void* stream);
 
+/* ---- per-episode dynamics randomisation --------------------------------------------------------------------
+ * For every env and every episode the rigid vehicle's mass, inertia and rotor thrusts are scaled by factors drawn uniformly:
+ *   km  mass factor: the body's mass is km * m.  Action scaling keeps the NOMINAL mass (F = a0 * m * g in fp32, as without), so the
+ *       policy's "1.0 = hover" is off by km, as on a real vehicle carrying a different payload;
+ *   kI  inertia factor: the body's inertia is kI * I;
+ *   s_r thrust factor of rotor r, one draw per rotor: the rotor delivers s_r * clamp(t_r, t_min_r, t_max_r) (commands still saturate at
+ *       the nominal limits).
+ * Dynamics: F = sum_r s_r t_r, M = mix[1..3] (s . t); translational acceleration F / (km m); rotational J (M / kI - w x I w), which is
+ * (kI I)^-1 (M - w x (kI I) w).  Gravity, task, reward, observation, reset draws and the Monitor totals are unchanged; the factors are
+ * not observed.
+ * Draw: ONE Philox4x32-10 block, key = the config seed (amenv_set_seed re-keys it), counter = (global env id lo, hi, episode,
+ * 0x44520000), cut into eight 16-bit uniforms u[2k] = (w[k] & 0xffff) * 2^-16, u[2k+1] = (w[k] >> 16) * 2^-16; u[0] -> km, u[1] -> kI,
+ * u[2 + r] -> s_r; factor = lo + (hi - lo) * u in fp32 (a multiply, then an add).  The factors are a pure function of (seed, global env
+ * id, episode, ranges): no state is stored (state layout, get / set_state and sharding are unaffected), and a change of ranges applies
+ * from the next launch ON, to episodes already running too (curricula rely on this).
+ * Served: rigid vehicles with 4 or 6 rotors, fp32 and fp64, by amenv_step / amenv_step_timed / amenv_rollout (lane and helper-wave
+ * kernels) and amenv_rollout_policy / amenv_rollout_policy_norm (one lane per env: a config the lane-quad closed loop would serve runs
+ * the one-lane-per-env form instead while randomisation is on).  Refused with AMENV_ERR_INVALID, before anything is launched: arm
+ * vehicles, other rotor counts, a handle whose step kernel is the lane-quad one (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle), a
+ * bad struct_size, ranges that are not finite with 0.25 <= lo <= hi <= 4. */
+typedef struct amenv_randomization {
+  uint32_t struct_size;  /* = sizeof(amenv_randomization): guard */
+  uint32_t reserved;
+  float mass_scale[2];   /* [lo, hi]; {1, 1} = fixed */
+  float inertia_scale[2];
+  float thrust_scale[2]; /* drawn independently per rotor */
+} amenv_randomization;
+/* r NULL = off (the nominal vehicle). */
+int amenv_set_randomization(amenv* env, const amenv_randomization* r);
+/* out [N, 2 + n_rotors] f32 (device): km, kI, s_0 .. s_{n_rotors-1} of every env's current episode; all 1 when off. */
+int amenv_dynamics_factors(amenv* env, float* out, void* stream);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

@@ -10,10 +10,11 @@ from . import _lib, sharding
 from ._lib import AmenvError
 from . import vec_env
 from .gpu_env import GpuWaypointEnv
+from .randomization import DynamicsRandomization
 from .vec_env import GpuVecEnv
 from .obs_norm import GpuVecNormalize, ObsNormalizer
 from . import baselines, ppo
 from .baselines import MinSnapTrajectory, PidController, PidWaypointPolicy
 from .ppo import PPO, ActorCritic, evaluate_policy, clone_pid_policy
 
-__all__ = ["GpuWaypointEnv", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]
+__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]

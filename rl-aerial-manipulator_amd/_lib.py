@@ -66,6 +66,11 @@ class PidPolicyParams(C.Structure):
                 ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("tool_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Randomization(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("mass_scale", C.c_float * 2), ("inertia_scale", C.c_float * 2),
+                ("thrust_scale", C.c_float * 2)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -82,6 +87,8 @@ SYMBOLS = {
     "amenv_destroy": (C.c_int, [_P]),
     "amenv_last_error": (C.c_char_p, [_P]),
     "amenv_set_seed": (C.c_int, [_P, C.c_uint64]),
+    "amenv_set_randomization": (C.c_int, [_P, C.POINTER(Randomization)]),
+    "amenv_dynamics_factors": (C.c_int, [_P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

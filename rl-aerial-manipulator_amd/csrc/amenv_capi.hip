@@ -62,6 +62,8 @@ struct amenv {
   float* io_obs = nullptr;         // [N][29]  internal observation rows
   float* io_term = nullptr;        // [N][29]  internal terminal-observation rows
   uint64_t steps = 0;
+  bool dr = false;                 // amenv_set_randomization: per-episode dynamics randomisation on
+  DrRanges dr_r = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};   // its ranges (lo, hi - lo); {1, 1} = the nominal vehicle
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
   std::string kname;
@@ -311,6 +313,10 @@ ColdParams make_cold(const amenv& e) {
   return C;
 }
 
+template <bool DR> DrArg<DR> make_dr(const amenv& e);
+template <> DrArg<false> make_dr<false>(const amenv&) { return DrArg<false>{0}; }
+template <> DrArg<true> make_dr<true>(const amenv& e) { return DrArg<true>{e.dr_r}; }
+
 bool is_v1(const amenv_config* c) { return c->task.variant == AMENV_TASK_V1_SCALED17 || c->task.variant == AMENV_TASK_V1_RAW17; }
 int obs_dim_of(const amenv_config* c) { return is_v1(c) ? 17 : 20 + 2 * c->vehicle.n_joints + (c->vehicle.n_joints ? 3 : 0); }
 int act_dim_of(const amenv_config* c) { return kActDim + c->vehicle.n_joints; }
@@ -424,6 +430,7 @@ std::string kernel_name(const amenv& e) {
       std::snprintf(buf, sizeof(buf), "step_kernel_arm2w<float,NROT=6> block=128 (2 waves per 64-env tile)"); break;
   }
   std::string name = buf;
+  if (e.dr) name += " +dr";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -438,7 +445,7 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 
 // amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
 // runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ>
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR>
 hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const ColdParams C = make_cold(e);
@@ -446,12 +453,12 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   const int32_t n = e.cfg.num_envs;
   switch (e.family) {
     case StepFamily::Team:   // one wave per 4 envs; the fp64 build is a logic gate of amenv_step only (amenv_rollout refuses it)
-      if constexpr (NJ == 3 && sizeof(T) == 4)
+      if constexpr (NJ == 3 && sizeof(T) == 4 && !DR)
         return launch(e, false, rollout_kernel_team<NROT>, dim3(e.n_tiles * 16), dim3(64), 0, s, e.blob, tb, n, reinterpret_cast<const float*>(io.actions), io.obs,
                       static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, make_team<T>(e));
       return hipErrorInvalidValue;
     case StepFamily::Quad:   // one wave per 16 envs
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6))
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && !DR)
         return launch(e, false, rollout_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(64), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
                       io.info, T_steps, tl, C, make_quad(e));
       return hipErrorInvalidValue;
@@ -461,15 +468,15 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s, e.blob,
-                tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA);
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dr<DR>(e));
 }
 
 // amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
 // if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0>
+template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ>(e, io, T_steps, s);
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
@@ -479,14 +486,14 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
   const int32_t n = e.cfg.num_envs;
   switch (e.family) {
     case StepFamily::Team:   // 16 lanes per env, 4 envs per workgroup: main wave + episode-end helper wave
-      if constexpr (NJ == 3) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
+      if constexpr (NJ == 3 && !DR) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
         const TeamParamsT<T> TP = make_team<T>(e);
         return launch(e, timed, step_kernel_team<T, NROT>, dim3(e.n_tiles * 16), dim3(128), 0, s, e.blob, n, int32_t(e.n_tiles * 16),
                       reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
       }
       break;
     case StepFamily::Staged:   // one tile per 320-thread workgroup: four stage waves + main wave
-      if constexpr (NJ == 3) {
+      if constexpr (NJ == 3 && !DR) {
         if constexpr (sizeof(T) == 8) {   // the fp64 logic-gate build exchanges its aggregates in fp64: > 64 KB of dynamic LDS needs the attribute
           hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel_armk<T, NROT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
           if (ea != hipSuccess) return ea;
@@ -496,37 +503,37 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
       }
       break;
     case StepFamily::TwoWave:   // one tile per 128-thread workgroup: main + helper wave
-      if constexpr (NJ == 3 && sizeof(T) == 4) {
+      if constexpr (NJ == 3 && sizeof(T) == 4 && !DR) {
         const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + (kArmXchgSlots + 12) * 64) * sizeof(float);   // obs rows | RK4 exchange | reset words
         return launch(e, timed, step_kernel_arm2w<T, NROT>, dim3(e.n_tiles), dim3(128), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
       }
       break;
     case StepFamily::Quad:   // 4 lanes per env, 16 envs per workgroup: main wave + episode-end helper wave
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6))
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && !DR)
         return launch(e, timed, step_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(128), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
                       io.info, tl, C, make_quad(e));
       break;
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
         const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions, io.obs,
-                      io.reward, io.done, io.info, tl, P, C);
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
+                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dr<DR>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dr<DR>(e));
     }
   }
   return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
-template <typename T, int NROT>
+template <typename T, int NROT, bool DR = false>
 hipError_t dispatch_k(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2>(e, io, T_steps, s, timed);
-  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2>(e, io, T_steps, s, timed);
+  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
+  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR>(e, io, T_steps, s, timed);
+  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR>(e, io, T_steps, s, timed);
 }
 
 template <typename T>
@@ -535,6 +542,11 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
   if (e.cfg.vehicle.n_joints == 3) {
     if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
+  }
+  if (e.dr) {   // amenv_set_randomization admits rigid vehicles with 4 or 6 rotors on the lane and helper-wave families only
+    if (nr == 4) return dispatch_k<T, 4, true>(e, io, T_steps, s, timed);
+    if (nr == 6) return dispatch_k<T, 6, true>(e, io, T_steps, s, timed);
+    return hipErrorInvalidValue;
   }
   if (nr == 4) return dispatch_k<T, 4>(e, io, T_steps, s, timed);
   if (nr == 6) return dispatch_k<T, 6>(e, io, T_steps, s, timed);
@@ -578,27 +590,45 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifndef AMENV_RIGID_WG64_MAX
 #define AMENV_RIGID_WG64_MAX 24576
 #endif
-template <int NROT, int KW, int VAR, bool NORM>
+template <int NROT, int KW, int VAR, bool NORM, bool DR>
 hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
   const ColdParams C = make_cold(e);
+  const DrArg<DR> R = make_dr<DR>(e);
   const int n = e.cfg.num_envs;
   if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   return hipGetLastError();
+}
+template <bool NORM, bool DR>
+hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  const bool four = e.cfg.vehicle.n_rotors == 4;
+  if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
+    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR>(e, T, io, N, s);
+  if (e.cfg.task.num_waypoints == 1)
+    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR>(e, T, io, N, s);
+  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR>(e, T, io, N, s)
+              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR>(e, T, io, N, s);
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  const bool four = e.cfg.vehicle.n_rotors == 4;
-  if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
-    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM>(e, T, io, N, s);
-  if (e.cfg.task.num_waypoints == 1)
-    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM>(e, T, io, N, s);
-  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM>(e, T, io, N, s) : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM>(e, T, io, N, s);
+  return e.dr ? launch_rigid_policy_dr<NORM, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, false>(e, T, io, N, s);
+}
+
+// amenv_dynamics_factors: [N][2 + NROT] = km, kI, s_0.. of every env's current episode (dr_draw: the kernels' own arithmetic)
+template <int NROT>
+__global__ void dr_factors_kernel(int n, uint32_t tile_bytes, const void* __restrict__ blob, const ColdParams C, const DrRanges R, float* __restrict__ out) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int32_t episode = iptr4(const_cast<char*>(tile_base(blob, tile_bytes, i)), i & 63)->w;
+  float f[2 + NROT];
+  dr_draw<NROT>(C, R, C.gid0 + i, episode, f);
+#pragma unroll
+  for (int k = 0; k < 2 + NROT; k++) out[size_t(i) * (2 + NROT) + k] = f[k];
 }
 
 // amenv_rollout_policy[_norm] after the entry checks: pack the parameters, fill the kernel's I/O block
@@ -882,6 +912,51 @@ int amenv_set_seed(amenv* e, uint64_t seed) {
   return AMENV_OK;
 }
 
+int amenv_set_randomization(amenv* e, const amenv_randomization* r) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!r) {
+    e->dr = false;
+    e->dr_r = DrRanges{{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
+    e->kname = kernel_name(*e);
+    return AMENV_OK;
+  }
+  if (r->struct_size != sizeof(amenv_randomization)) return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: struct_size must be sizeof(amenv_randomization)");
+  if (e->cfg.vehicle.n_joints > 0)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: built for rigid vehicles (an arm vehicle's mass and inertia are not one scalar scale)");
+  if (e->cfg.vehicle.n_rotors != 4 && e->cfg.vehicle.n_rotors != 6)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: built for rigid vehicles with 4 or 6 rotors");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  const float* rg[3] = {r->mass_scale, r->inertia_scale, r->thrust_scale};
+  const char* nm[3] = {"mass_scale", "inertia_scale", "thrust_scale"};
+  for (int q = 0; q < 3; q++) {
+    const float lo = rg[q][0], hi = rg[q][1];
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo >= 0.25f) || !(lo <= hi) || !(hi <= 4.0f))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_randomization: ") + nm[q] + " must be finite with 0.25 <= lo <= hi <= 4");
+  }
+  DrRanges R;
+  for (int q = 0; q < 3; q++) { R.lo[q] = rg[q][0]; R.span[q] = rg[q][1] - rg[q][0]; }
+  e->dr = true;
+  e->dr_r = R;
+  e->kname = kernel_name(*e);
+  return AMENV_OK;
+}
+
+int amenv_dynamics_factors(amenv* e, float* out, void* stream) {
+  if (!e || !out) return fail(e, AMENV_ERR_INVALID, "amenv_dynamics_factors: NULL argument");
+  const int nr = e->cfg.vehicle.n_rotors, n = e->cfg.num_envs;
+  if (e->cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6))
+    return fail(e, AMENV_ERR_INVALID, "amenv_dynamics_factors: built for rigid vehicles with 4 or 6 rotors");
+  DeviceGuard g(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((n + 255) / 256), block(256);
+  if (nr == 4) hipLaunchKernelGGL(dr_factors_kernel<4>, grid, block, 0, s, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->dr_r, out);
+  else hipLaunchKernelGGL(dr_factors_kernel<6>, grid, block, 0, s, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->dr_r, out);
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
 int amenv_reset(amenv* e, const uint8_t* mask, float* obs_out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
@@ -967,7 +1042,8 @@ int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, v
 int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp,
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
-  const bool quad = quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
+  const bool quad = !e->dr && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");

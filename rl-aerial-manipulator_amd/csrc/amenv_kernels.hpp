@@ -275,10 +275,11 @@ __device__ __forceinline__ void observe_reset(const Env<T, KW>& e, bool ee_task,
   }
 }
 
-template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg>
+template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false>
 __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const ColdParams& C, const ArmArg<T, NJ>& AA, Env<T, KW>& e, const float* act, int i,
                                               bool active, T& reward, float* o, const StepIO& io, char* tile, int lane,
-                                              bool have_episode, bool& was_reset, int& ep_len_out, float& ep_ret_out, const X& x = X{}) {
+                                              bool have_episode, bool& was_reset, int& ep_len_out, float& ep_ret_out, const X& x = X{},
+                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}) {
   constexpr int OD = ObsDim<VAR, NJ>::value;
   const int K = KW == 1 ? 1 : P.K;
   if constexpr (NJ > 0) {
@@ -286,7 +287,7 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
     else if constexpr (ROLE == ARM_ROLE_STAGED) dynamics_arm_staged<T, NROT, KW>(P, AA.p, e, act, x);                                   // stage-wave kernel: z,x,x arm only
     else if (AA.p.generic_axes) dynamics_arm<T, NROT, KW, AxesAny>(P, AA.p, e, act);   // wave-uniform: one of the two bodies runs
     else dynamics_arm<T, NROT, KW, AxesZXX>(P, AA.p, e, act);
-  } else { dynamics<T, NROT, KW>(P, e, act[0], act[1], act[2], act[3]); }
+  } else { dynamics<T, NROT, KW, DR>(P, e, act[0], act[1], act[2], act[3], df); }
   constexpr bool EE = NJ > 0;   // arm: forward kinematics of the post-step state feed the task point and the observation
   if constexpr (EE) update_tool_offset<T, KW, ROLE == ARM_ROLE_MAIN || ROLE == ARM_ROLE_HELPER || ROLE == ARM_ROLE_STAGED>(AA.p, e);
   const bool ee_task = EE && P.ee_task != 0;
@@ -385,11 +386,13 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 #ifndef AMENV_STEP_WAVES_ATTR
 #define AMENV_STEP_WAVES_ATTR
 #endif
-template <typename T, int NROT, int KW, int VAR, int NJ>
+// DR: per-episode dynamics randomisation, rigid vehicles only; the factors are drawn once per launch from the loaded episode.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA) {
+                                                   const ArmArg<T, NJ> AA, const DrArg<DR> R) {
+  static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -419,7 +422,10 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(2);          // loads landed
   T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret);
+  DynFac<T, NROT, DR> df;
+  if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
+  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret,
+                                                                 NoXchg{}, df);
   const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
   AMENV_STAMP(3);          // dynamics + task + obs computed
   accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
@@ -473,10 +479,12 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 //             LDS; after the barrier it writes waypoint and observation row of the lanes that were reset;
 //      wave 0 (main) integrates, runs the task step, publishes a flag word per lane (and info bits / length / return of the lanes that
 //             ended), passes the barrier, takes the reset position of reset lanes from LDS and stores the state of every lane.
-template <typename T, int NROT, int KW, int VAR>
+// DR: the waves that integrate (main, observation) draw the factors of the loaded episode.
+template <typename T, int NROT, int KW, int VAR, bool DR = false>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
-                                                      uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C) {
+                                                      uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
+                                                      const DrArg<DR> R) {
   constexpr int OD = ObsDim<VAR, 0>::value;
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
@@ -564,12 +572,14 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     float act[kActDim];
     const float4 a = io.actions[min(i, hd.n - 1)];
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
+    DynFac<T, NROT, DR> df;
+    if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
     if (role == 2) {
 #ifdef AMENV_STAMPS
       AMENV_STAMP_DRAIN();
 #endif
       AMENV_STAMP(1);
-      dynamics<T, NROT, KW>(P, e, act[0], act[1], act[2], act[3]);
+      dynamics<T, NROT, KW, DR>(P, e, act[0], act[1], act[2], act[3], df);
       AMENV_STAMP(2);
       float ho[kObsDimMax];
       observe<T, KW>(1, e, ho);
@@ -600,7 +610,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
 #endif
     AMENV_STAMP(1);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_FLAGS>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_FLAGS, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len,
+                                                                               ep_ret, NoXchg{}, df);
     AMENV_STAMP(2);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     flag[lane] = (is_done ? 1u : 0u) | (was_reset ? 2u : 0u);
@@ -643,9 +654,11 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     const float4 a = io.actions[min(i, hd.n - 1)];
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     const LdsXchg x{lds, lane, words};
+    DynFac<T, NROT, DR> df;
+    if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len,
-                                                                           ep_ret, x);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len,
+                                                                               ep_ret, x, df);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int(blockIdx.x), bits, is_done, ep_len, ep_ret);
     store_env_step<T, KW>(tile, lane, e);
@@ -844,11 +857,13 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
 
 // n_steps control steps per launch with open-loop actions [T][N][4]; per-step outputs [T][N]...
 // State stays in registers across steps: HBM traffic per env-step drops to action + outputs.
-template <typename T, int NROT, int KW, int VAR, int NJ>
+// DR: factors drawn at entry and again for a lane after its auto-reset.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false>
 __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, int n_steps, const StepTail tl, const HotParams<T, NROT> P,
-                                                      const ColdParams C, const ArmArg<T, NJ> AA) {
+                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DrArg<DR> R) {
+  static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, nullptr, nullptr, nullptr, tl.stats};
@@ -864,6 +879,8 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   const int K = KW == 1 ? 1 : P.K;
   Env<T, KW> e;
   load_env<T, KW, NJ>(K, tile, lane, e);
+  DynFac<T, NROT, DR> df;
+  if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
   bool any_reset = false;
   StepIO io_t = io; io_t.terminal_obs = nullptr; io_t.ep_return = nullptr; io_t.ep_len = nullptr;
   for (int t = 0; t < n_steps; t++) {
@@ -877,7 +894,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
       }
     }
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset, ep_len, ep_ret);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset, ep_len, ep_ret,
+                                                                   NoXchg{}, df);
+    if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);

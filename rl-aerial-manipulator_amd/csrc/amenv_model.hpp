@@ -157,9 +157,25 @@ __device__ __forceinline__ Deriv<T> rhs(const PT& P, T vx, T vy, T vz, T qw, T q
   return d;
 }
 
+// ---- per-episode dynamics randomisation (include/amenv.h amenv_set_randomization) ------------------------------
+// Ranges travel as a kernel argument of their own, in the DR instantiations only (HotParams is at its SGPR budget).  A factor is
+// lo + span * u, span = hi - lo, all in fp32 (the library is built with -ffp-contract=off: a multiply, then an add).
+struct DrRanges { float lo[3], span[3]; };   // [0] mass, [1] inertia, [2] thrust (one draw per rotor)
+template <bool DR> struct DrArg { DrRanges r; };
+template <> struct DrArg<false> { int unused; };
+// Per-lane factors of the lane's current episode, drawn once per launch (and again after an auto-reset inside a rollout); empty when off.
+// F = sum s_r t_r and M = mixm (s . t); translational acceleration F / (km m); rotational J (M / kI - w x I w).
+template <typename T, int NROT, bool DR> struct DynFac {};
+template <typename T, int NROT> struct DynFac<T, NROT, true> {
+  T s[NROT];        // thrust factor per rotor
+  T inv_mass;       // 1 / (km m)
+  T inv_ki;         // 1 / kI
+};
+
 // Quadcopter.update (quadcopter.py:105-114) with RK4 in place of odeint.
-template <typename T, int NROT, int KW>
-__device__ __forceinline__ void dynamics(const HotParams<T, NROT>& P, Env<T, KW>& e, float a0, float a1, float a2, float a3) {
+template <typename T, int NROT, int KW, bool DR = false>
+__device__ __forceinline__ void dynamics(const HotParams<T, NROT>& P, Env<T, KW>& e, float a0, float a1, float a2, float a3,
+                                         const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}) {
   // action scaling in fp32, left to right (rl_env_scaledObs.py:125-126)
   const float Ff = (a0 * P.mass_f) * P.g_f;
   const T u0 = T(Ff), u1 = T(a1 * P.mscale_f), u2 = T(a2 * P.mscale_f), u3 = T(a3 * P.mscale_f);
@@ -170,9 +186,12 @@ __device__ __forceinline__ void dynamics(const HotParams<T, NROT>& P, Env<T, KW>
     if (NROT == AMENV_MAX_ROTORS && r >= P.n_rotors) break;  // generic instantiation: runtime rotor count
     T t = fma_(P.alloc[r][0], u0, fma_(P.alloc[r][1], u1, fma_(P.alloc[r][2], u2, P.alloc[r][3] * u3)));
     t = clamp_(t, P.tmin[r], P.tmax[r]);   // np.maximum(np.minimum(t, max), min), quadcopter.py:110
+    if constexpr (DR) t = t * df.s[r];     // the rotor delivers s_r of its (nominally saturated) command
     F = F + t; Mx = fma_(P.mixm[0][r], t, Mx); My = fma_(P.mixm[1][r], t, My); Mz = fma_(P.mixm[2][r], t, Mz);
   }
-  const T Fm = F * P.inv_mass;
+  T Fm;
+  if constexpr (DR) { Fm = F * df.inv_mass; Mx = Mx * df.inv_ki; My = My * df.inv_ki; Mz = Mz * df.inv_ki; }
+  else Fm = F * P.inv_mass;
   const T h = P.h, hh = T(0.5) * h, h6 = h * T(1.0 / 6.0);
   int it = 0;
   do {  // substeps >= 1 (validated at create): no loop guard in front of the first stage
@@ -446,6 +465,34 @@ __device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+
+// The dynamics factors of (env, episode): ONE Philox block, counter (gid, episode, kDrBlock) -- a block index no other draw uses (resets
+// 0..2, the quad / team / stage-wave kernels up to 4) -- cut into eight 16-bit uniforms u = w16 * 2^-16: u0 -> km, u1 -> kI, u2.. -> s_r.
+// A pure function of (seed, gid, episode, ranges): no state is stored, a change of ranges applies from the next launch.
+constexpr uint32_t kDrBlock = 0x44520000u;
+template <int NROT>
+__device__ __forceinline__ void dr_draw(const ColdParams& C, const DrRanges& R, int64_t gid, int32_t episode, float* f /*[2 + NROT]*/) {
+  static_assert(NROT <= 6, "eight 16-bit uniforms per block: km, kI and up to six rotors");
+  uint32_t w[4];
+  philox4x32_10(C.seed_lo, C.seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), kDrBlock, w);
+#pragma unroll
+  for (int k = 0; k < 2 + NROT; k++) {
+    const uint32_t v = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
+    const int q = k < 2 ? k : 2;
+    f[k] = R.lo[q] + R.span[q] * (float(v) * 1.52587890625e-05f);
+  }
+}
+template <typename T, int NROT>
+__device__ __forceinline__ DynFac<T, NROT, true> dr_factors(const HotParams<T, NROT>& P, const ColdParams& C, const DrRanges& R, int64_t gid, int32_t episode) {
+  float f[2 + NROT];
+  dr_draw<NROT>(C, R, gid, episode, f);
+  DynFac<T, NROT, true> d;
+#pragma unroll
+  for (int r = 0; r < NROT; r++) d.s[r] = T(f[2 + r]);
+  d.inv_mass = P.inv_mass * rcp_(T(f[0]));
+  d.inv_ki = rcp_(T(f[1]));
+  return d;
+}
 
 // WaypointQuadEnv.reset (rl_env_scaledObs.py:40-79) with the DESIGN.md draw table.  All draws
 // are formed in fp32 with explicit fmaf so the CPU oracle reproduces them bit for bit.

@@ -31,10 +31,12 @@ struct NormArg {
   int32_t update;  // != 0: add the raw rows 1..T into the batch-sum slots
 };
 
-template <int NROT, int KW, int VAR, bool NORM, int NE>
+// DR: per-episode dynamics randomisation: factors drawn at entry and again for a lane after its auto-reset.
+template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
-                                                                                         const HotParams<float, NROT> P, const ColdParams C, const NormArg N) {
+                                                                                         const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
+                                                                                         const DrArg<DR> R) {
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -142,6 +144,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   char* tile = static_cast<char*>(blob) + size_t(i >> 6) * tile_bytes;
   const int K = KW == 1 ? 1 : P.K;
   Env<float, KW> e;
+  DynFac<float, NROT, DR> df;
   float std_a[AD], ls_a[AD];
   float o[kObsDimMax];
   double s1[NORM ? OD : 1], s2[NORM ? OD : 1];                    // fp64 column sums / sums of squares of this lane's raw rows 1..T
@@ -176,6 +179,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   };
   if (mine) {
     load_env<float, KW, 0>(K, tile, tl, e);
+    if constexpr (DR) df = dr_factors<float, NROT>(P, C, R.r, C.gid0 + i, e.episode);
     const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
 #pragma unroll
     for (int c = 0; c < AD; c++) { const uint4 v = ac[c]; std_a[c] = __uint_as_float(v.x); ls_a[c] = __uint_as_float(v.y); }
@@ -231,7 +235,9 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
     sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
-    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len, ep_ret);
+    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
+                                                                           ep_ret, NoXchg{}, df);
+    if constexpr (DR) { if (was_reset) df = dr_factors<float, NROT>(P, C, R.r, gid, e.episode); }   // the new episode's vehicle
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);

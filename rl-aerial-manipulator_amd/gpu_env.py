@@ -32,7 +32,7 @@ class GpuWaypointEnv:
 
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
-                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None):
+                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None):
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -82,6 +82,10 @@ class GpuWaypointEnv:
         self.ep_return = torch.zeros(n, dtype=torch.float32, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
         self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+        self.n_rotors = int(cfg.vehicle.n_rotors)
+        self.randomization = None
+        if randomization is not None:
+            self.set_randomization(randomization)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -103,6 +107,24 @@ class GpuWaypointEnv:
         """Re-key the reset RNG for episodes started from now on."""
         self._check(self.lib.amenv_set_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF), "amenv_set_seed")
         self.cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def set_randomization(self, r):
+        """Per-episode dynamics randomisation (a `DynamicsRandomization`, or None = the nominal vehicle; rigid vehicles with 4 or 6 rotors,
+        not with kernel="team").  The factors are a pure function of (seed, env id, episode, ranges): new ranges apply from the next
+        launch on, to the episodes already running too."""
+        from .randomization import DynamicsRandomization
+        if r is not None and not isinstance(r, DynamicsRandomization):
+            raise L.AmenvError(f"set_randomization: expected a DynamicsRandomization or None, got {type(r).__name__}")
+        c = None if r is None else r.to_c()
+        self._check(self.lib.amenv_set_randomization(self._h, None if c is None else C.byref(c)), "amenv_set_randomization")
+        self.randomization = r
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
+    def dynamics_factors(self):
+        """[N, 2 + n_rotors] f32 on this env's device: km, kI, s_0.. of every env's current episode (all 1 without randomisation)."""
+        out = torch.empty(self.num_envs, 2 + self.n_rotors, dtype=torch.float32, device=self.device)
+        self._check(self.lib.amenv_dynamics_factors(self._h, C.c_void_p(out.data_ptr()), self._stream()), "amenv_dynamics_factors")
+        return out
 
     def reset(self, mask=None):
         """WaypointQuadEnv.reset (v2/rl_env_scaledObs.py:40-79) for all envs, or those with mask != 0."""

@@ -1,0 +1,338 @@
+"""Per-episode dynamics randomisation of the rigid vehicles (amenv_set_randomization) on the GPU:
+{1, 1} ranges change no output bit; the factors are the numpy restatement's (tests/dr_ref.py) and change exactly when an episode does;
+the fp64 kernels match the UNCHANGED fp64 oracle given each env's factors as its vehicle; one-launch rollouts and closed loops replay
+bit for bit through amenv_step; sharding by env_id_offset and re-keying; refusals leave the state untouched; PPO trains with it."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import rl_aerial_manipulator_amd as amd
+from oracle import oracle as O
+from rl_aerial_manipulator_amd import _lib as L
+from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
+from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic
+from tests import dr_ref
+
+pytestmark = pytest.mark.gpu
+
+DR = amd.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.7, 1.3), thrust=(0.9, 1.1))
+ONE = amd.DynamicsRandomization()
+# (vehicle, task, waypoints): the lane / helper-wave instantiations (KW = 1 v2, KW = 4 v2, KW = 2 v1)
+CONFIGS = [("quad", "v2", 1), ("hexa", "v2", 1), ("hexa", "v2", 3), ("quad", "v1_raw", 1)]
+
+
+def _env(vehicle, task, nwp, n, seed=4, **kw):
+    kw.setdefault("max_episode_steps", 25)
+    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
+
+
+def _actions(T, n, seed, dev, wide=False):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    if wide:   # near +-1 (and 0 / 2 on the collective): rotors saturate at both limits
+        a = torch.rand(T, n, 4, generator=g)
+        a = torch.where(a < 0.5, -1.0 + 0.2 * a, 0.8 + 0.4 * a)
+        a[..., 0] = torch.where(a[..., 0] < 0, 1.5 + a[..., 0], a[..., 0] + 0.7)
+    else:
+        a = torch.rand(T, n, 4, generator=g) * torch.tensor([0.6, 0.4, 0.4, 0.4]) + torch.tensor([0.7, -0.2, -0.2, -0.2])
+    return a.to(dev).contiguous()
+
+
+def _policy(od):
+    torch.manual_seed(7)
+    pol = ActorCritic(od, 4).cuda().flatten_()
+    with torch.no_grad():
+        pol.log_std.data.fill_(-1.2)
+        pol.action_net.weight.mul_(30.0)
+    return pol
+
+
+def _buffers(T, n, od, dev):
+    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
+                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
+
+
+def _step_all(env, a):
+    o, r, d, i = env.step(a)
+    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
+
+
+# ---- 1. {1, 1} ranges are the identity ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("vehicle,task,nwp", CONFIGS)
+@pytest.mark.parametrize("kernel", ["auto", "lane"])
+def test_unit_ranges_are_bit_identical_step_and_rollout(vehicle, task, nwp, dtype, kernel):
+    n, T = 300, 40
+    a = _env(vehicle, task, nwp, n, dtype=dtype, kernel=kernel)
+    b = _env(vehicle, task, nwp, n, dtype=dtype, kernel=kernel, randomization=ONE)
+    assert "+dr" in b.kernel_name and "+dr" not in a.kernel_name
+    assert torch.equal(a.reset(), b.reset())
+    assert torch.equal(b.dynamics_factors(), torch.ones(n, 2 + b.n_rotors, device=b.device))
+    acts = _actions(T, n, 1, a.device)
+    for t in range(T):
+        ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
+        for x, y in zip(ra[:4], rb[:4]):
+            assert torch.equal(x, y), t
+        for x, y in zip(ra[4:], rb[4:]):
+            assert torch.equal(x[da], y[db]), t
+    ra, rb = a.rollout(acts), b.rollout(acts)
+    for k in ra:
+        assert torch.equal(ra[k], rb[k]), k
+    fa, ia = a.get_state(); fb, ib = b.get_state()
+    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("vehicle,task,nwp,n", [("quad", "v2", 1, 300), ("hexa", "v2", 2, 4096), ("quad", "v1_raw", 1, 12000),
+                                                ("hexa", "v1_scaled", 1, 40000)])
+def test_unit_ranges_are_bit_identical_closed_loop(vehicle, task, nwp, n):
+    """amenv_rollout_policy and amenv_rollout_policy_norm with {1, 1}: the same rows as the one-lane-per-env form without randomisation
+    (block_size = 64 keeps the lane-quad form out of the reference handle); 16-, 64- and 128-env workgroups."""
+    T = 48
+    a = _env(vehicle, task, nwp, n, block_size=64)
+    b = _env(vehicle, task, nwp, n, randomization=ONE)
+    a.reset(); b.reset()
+    od, dev = a.obs_dim, a.device
+    pol = _policy(od)
+    for norm in (False, True):
+        ba, bb = _buffers(T, n, od, dev), _buffers(T, n, od, dev)
+        ia, ib = (torch.zeros(T, n, dtype=torch.int32, device=dev) for _ in range(2))
+        kw_a, kw_b = {}, {}
+        if norm:   # the same entry statistics in both (the normaliser's fp64 sums are atomics: their rounding is not reproducible bit for bit)
+            na, nb = ObsNormalizer(od), ObsNormalizer(od)
+            na.update(a.observe()); nb.set(*na.get())
+            kw_a, kw_b = dict(obs_normalizer=na), dict(obs_normalizer=nb)
+        a.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ia, **ba, **kw_a)
+        b.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ib, **bb, **kw_b)
+        torch.cuda.synchronize()
+        for k in ba:
+            assert torch.equal(ba[k], bb[k]), (norm, k)
+        assert torch.equal(ia, ib) and int(ba["dones"].sum()) > 0
+        if norm:
+            (ma, va, ca), (mb, vb, cb) = na.get(), nb.get()
+            assert ca == cb
+            np.testing.assert_allclose(ma, mb, rtol=1e-10, atol=1e-12); np.testing.assert_allclose(va, vb, rtol=1e-10, atol=1e-12)
+            na.close(); nb.close()
+    fa, sa = a.get_state(); fb, sb = b.get_state()
+    assert torch.equal(fa, fb) and torch.equal(sa, sb)
+    a.close(); b.close()
+
+
+# ---- 2. the factors are the restatement's ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vehicle,dtype", [("quad", "f32"), ("hexa", "f64")])
+def test_factors_match_restatement_and_follow_episodes(vehicle, dtype):
+    n, T = 512, 300
+    env = _env(vehicle, "v2", 1, n, seed=21, dtype=dtype, max_episode_steps=40, randomization=DR)
+    env.reset()
+    nr = env.n_rotors
+
+    def check():
+        f = env.dynamics_factors().cpu().numpy()
+        ep = env.get_state()[1][L.I_EPISODE].cpu().numpy()
+        assert np.array_equal(f, dr_ref.factors_all(21, 0, ep, nr, DR)), "factors differ from the restatement"
+        return f, ep
+
+    f0, ep0 = check()
+    assert f0.shape == (n, 2 + nr) and len(np.unique(f0[:, 0])) > n // 2
+    acts = _actions(T, n, 5, env.device)
+    prev_f, prev_ep = f0, ep0
+    changed = 0
+    for t in range(T):
+        env.step(acts[t])
+        f = env.dynamics_factors().cpu().numpy()
+        ep = env.get_state()[1][L.I_EPISODE].cpu().numpy()
+        same = ep == prev_ep
+        assert np.array_equal(f[same], prev_f[same]), t                      # constant within an episode
+        assert np.all(np.any(f[~same] != prev_f[~same], axis=1)), t           # a new episode, a new vehicle
+        changed += int((~same).sum())
+        prev_f, prev_ep = f, ep
+    assert changed > n
+    check()
+    env.close()
+
+
+# ---- 3. fp64 (and fp32) kernels against the per-env oracle ----------------------------------------------------------------------
+@pytest.mark.parametrize("vehicle,task,nwp,dtype,kernel", [("quad", "v2", 1, "f64", "lane"), ("quad", "v2", 1, "f64", "helper"),
+                                                           ("hexa", "v2", 3, "f64", "lane"), ("hexa", "v2", 3, "f64", "helper"),
+                                                           ("quad", "v1_raw", 1, "f64", "lane"), ("quad", "v1_raw", 1, "f64", "helper"),
+                                                           ("quad", "v2", 1, "f32", "auto"), ("hexa", "v2", 3, "f32", "lane")])
+def test_kernels_match_the_oracle_with_per_env_vehicles(vehicle, task, nwp, dtype, kernel):
+    """Teacher-forced per step: env i's oracle is the unchanged fp64 oracle on dr_ref.oracle_config(cfg, factors of env i's episode);
+    actions near +-1 saturate rotors.  fp64 <= 1e-12, fp32 <= 1e-5 relative to max(1, |x|); reset states bit for bit."""
+    n, T = 64, 30
+    wide = amd.DynamicsRandomization(mass=(0.6, 1.6), inertia=(0.5, 2.0), thrust=(0.8, 1.2))
+    env = _env(vehicle, task, nwp, n, seed=8, dtype=dtype, kernel=kernel, max_episode_steps=12, randomization=wide)
+    env.reset()
+    base = O.Config.from_buffer_copy(env.cfg)
+    acts = _actions(T, n, 6, env.device, wide=True)
+    tol = 1e-12 if dtype == "f64" else 1e-5
+    worst, ended = 0.0, 0
+    for t in range(T):
+        f_prev, i_prev = (x.cpu().numpy() for x in env.get_state())
+        fac = env.dynamics_factors().cpu().numpy()
+        env.step(acts[t])
+        f_new, i_new = (x.cpu().numpy().astype(np.float64) for x in env.get_state())
+        done = env.done.cpu().numpy()
+        a = acts[t].cpu().numpy()
+        for i in range(n):
+            orc = O.OracleEnv(dr_ref.oracle_config(base, fac[i], gid=i))
+            orc.fstate[:, 0] = f_prev[:, i]
+            orc.istate[:, 0] = i_prev[:, i]
+            out = orc.step(a[i:i + 1])
+            if done[i]:
+                ended += 1
+                if dtype == "f64":
+                    assert out["done"][0] == 1 and np.array_equal(orc.fstate[:, 0], f_new[:, i]) and np.array_equal(orc.istate[:, 0], i_new[:, i]), (t, i)
+                continue
+            if dtype == "f64":
+                assert out["done"][0] == 0 and np.array_equal(orc.istate[:, 0], i_new[:, i]), (t, i)
+            err = np.abs(orc.fstate[:13, 0] - f_new[:13, i]) / np.maximum(1.0, np.abs(orc.fstate[:13, 0]))
+            worst = max(worst, float(err.max()))
+    assert worst <= tol, worst
+    assert ended > 0
+    env.close()
+
+
+# ---- 4. one-launch rollout = T steps -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vehicle,task,nwp,dtype", [("quad", "v2", 1, "f32"), ("hexa", "v2", 3, "f64"), ("quad", "v1_raw", 1, "f32"),
+                                                    ("hexa", "v1_scaled", 1, "f64")])
+def test_rollout_equals_steps(vehicle, task, nwp, dtype):
+    n, T = 1000, 80
+    a = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, randomization=DR)
+    b = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, randomization=DR)
+    a.reset(); b.reset()
+    acts = _actions(T, n, 2, a.device)
+    ro = a.rollout(acts)
+    for t in range(T):
+        o, r, d, i = b.step(acts[t])
+        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
+    assert int(ro["done"].sum()) > n
+    fa, ia = a.get_state(); fb, ib = b.get_state()
+    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
+    assert torch.equal(a.dynamics_factors(), b.dynamics_factors())
+    a.close(); b.close()
+
+
+# ---- 5. the closed loop replays bit for bit -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vehicle,task,nwp,n,norm", [("quad", "v2", 1, 4096, False), ("hexa", "v2", 2, 4096, False),
+                                                     ("quad", "v1_raw", 1, 4096, True), ("quad", "v2", 1, 40000, False)])
+def test_closed_loop_replays_bit_for_bit(vehicle, task, nwp, n, norm):
+    T = 64
+    env = _env(vehicle, task, nwp, n, randomization=DR)
+    ref = _env(vehicle, task, nwp, n, kernel="lane", randomization=DR)
+    od, dev = env.obs_dim, env.device
+    pol = _policy(od)
+    env.reset(); ref.reset()
+    kw = {}
+    if norm:
+        nrm = ObsNormalizer(od)
+        nrm.update(env.observe())
+        entry = ObsNormalizer(od); entry.set(*nrm.get())
+        kw = dict(obs_normalizer=nrm)
+    b = _buffers(T, n, od, dev)
+    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
+    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b, **kw)
+    torch.cuda.synchronize()
+    tr = (lambda x: entry.normalize(x)) if norm else (lambda x: x)
+    lo, hi = pol.action_low, pol.action_high
+    for t in range(T):
+        o, r, d, i = ref.step(torch.max(torch.min(b["actions"][t], hi), lo))
+        assert torch.equal(tr(o), b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
+        dn = d.bool()
+        if bool(dn.any()):
+            assert torch.equal(tr(ref.terminal_obs[dn]), tobs[t][dn]), t
+    f1, i1 = env.get_state(); f2, i2 = ref.get_state()
+    assert torch.equal(f1, f2) and torch.equal(i1, i2) and env.stats() == ref.stats()
+    assert int(b["dones"].sum()) > 0
+    env.close(); ref.close()
+    if norm:
+        nrm.close(); entry.close()
+
+
+# ---- 6. sharding and re-keying --------------------------------------------------------------------------------------------------
+def test_sharding_and_reseed():
+    n, T = 512, 60
+    whole = _env("hexa", "v2", 1, n, seed=13, max_episode_steps=20, randomization=DR)
+    h0 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, randomization=DR)
+    h1 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, randomization=DR, env_id_offset=n // 2)
+    ow = whole.reset().clone(); o0 = h0.reset().clone(); o1 = h1.reset().clone()
+    assert torch.equal(ow, torch.cat([o0, o1]))
+    assert torch.equal(whole.dynamics_factors(), torch.cat([h0.dynamics_factors(), h1.dynamics_factors()]))
+    acts = _actions(T, n, 4, whole.device)
+    for t in range(T):
+        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
+        p0 = [x.clone() for x in h0.step(acts[t, :n // 2])]
+        p1 = [x.clone() for x in h1.step(acts[t, n // 2:])]
+        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
+            assert torch.equal(x, torch.cat([y, z])), t
+    assert torch.equal(whole.dynamics_factors(), torch.cat([h0.dynamics_factors(), h1.dynamics_factors()]))
+    before = whole.dynamics_factors().clone()
+    whole.reseed(14)
+    after = whole.dynamics_factors()
+    ep = whole.get_state()[1][L.I_EPISODE].cpu().numpy()
+    assert not torch.equal(before, after)
+    assert np.array_equal(after.cpu().numpy(), dr_ref.factors_all(14, 0, ep, 6, DR))
+    for e in (whole, h0, h1):
+        e.close()
+
+
+# ---- 7. refusals ----------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_state_untouched():
+    arm = _env("hexa_arm", "v2", 1, 64)
+    arm.reset()
+    f0, i0 = arm.get_state()
+    with pytest.raises(L.AmenvError):
+        arm.set_randomization(DR)
+    with pytest.raises(L.AmenvError):
+        arm.dynamics_factors()
+    f1, i1 = arm.get_state()
+    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+dr" not in arm.kernel_name
+    arm.close()
+    with pytest.raises(L.AmenvError):
+        _env("hexa_arm", "v2", 1, 64, n_joints=2, randomization=DR)
+    team = _env("quad", "v2", 1, 64, kernel="team")
+    team.reset()
+    f0, i0 = team.get_state()
+    with pytest.raises(L.AmenvError):
+        team.set_randomization(DR)
+    f1, i1 = team.get_state()
+    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+dr" not in team.kernel_name
+    team.close()
+    env = _env("quad", "v2", 1, 64, randomization=DR)
+    env.reset()
+    f0, i0 = env.get_state(); k0 = env.dynamics_factors().clone()
+    bad = DR.to_c()
+    bad.struct_size = 16
+    assert env.lib.amenv_set_randomization(env._h, C.byref(bad)) == -1
+    assert b"struct_size" in env.lib.amenv_last_error(env._h)
+    for lo, hi in [(0.2, 1.0), (1.0, 4.5), (1.2, 1.1), (float("nan"), 1.0)]:
+        r = DR.to_c()
+        r.thrust_scale[0], r.thrust_scale[1] = lo, hi
+        assert env.lib.amenv_set_randomization(env._h, C.byref(r)) == -1, (lo, hi)
+    f1, i1 = env.get_state()
+    assert torch.equal(f0, f1) and torch.equal(i0, i1) and torch.equal(env.dynamics_factors(), k0)   # the earlier ranges still hold
+    env.set_randomization(None)
+    assert torch.equal(env.dynamics_factors(), torch.ones_like(k0)) and "+dr" not in env.kernel_name
+    env.close()
+
+
+# ---- 8. PPO ---------------------------------------------------------------------------------------------------------------------
+def test_ppo_fused_rollout_with_randomisation():
+    n, T = 4096, 64
+    env = amd.GpuWaypointEnv(n, vehicle="hexa", seed=2, max_episode_steps=60, randomization=DR)
+    algo = PPO(env, fused_rollout=True, n_steps=T, n_epochs=2, batch_size=8192, seed=1)
+    algo.learn(2 * T * n)
+    assert len(algo.log) == 2 and all(math.isfinite(x) for rec in algo.log for x in rec.values())
+    assert int(algo.buffer.dones.sum()) > 0
+    env.close()
+    venv = amd.GpuVecEnv(num_envs=256, vehicle="quad", task="v1_raw", randomization=DR)   # passed through **env_kwargs
+    assert "+dr" in venv.backend.kernel_name and venv.backend.randomization is DR
+    venv.backend.close()
+    norm = ObsNormalizer(17)
+    algo = PPO(amd.GpuWaypointEnv(n, task="v1_raw", seed=3, randomization=DR), obs_normalizer=norm, fused_rollout=True, n_steps=T,
+               n_epochs=1, batch_size=8192, seed=1)
+    algo.learn(2 * T * n)
+    assert all(math.isfinite(x) for rec in algo.log for x in rec.values())
+    norm.close()
