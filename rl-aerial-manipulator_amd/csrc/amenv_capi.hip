@@ -407,6 +407,20 @@ const char* select_step_family(const amenv_config& c, StepFamily* out) {
   return nullptr;
 }
 
+// Lane-team step kernel: four integrating waves + one helper per workgroup while every workgroup gets a CU to itself, else one + one
+// (amenv_team.hpp, step_kernel_team).
+static bool team_wide(const amenv& e) {
+  static std::mutex m;
+  static int cus[64] = {0};
+  const int d = e.device >= 0 && e.device < 64 ? e.device : 0;
+  std::lock_guard<std::mutex> g(m);
+  if (cus[d] == 0) {
+    int v = 0;
+    cus[d] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && v > 0 ? v : 1;
+  }
+  return e.n_tiles * 4 <= cus[d];
+}
+
 // amenv_kernel_name: tests, tools/ and bench.py match substrings of it
 std::string kernel_name(const amenv& e) {
   const amenv_config& c = e.cfg;
@@ -423,7 +437,8 @@ std::string kernel_name(const amenv& e) {
     case StepFamily::Quad:
       std::snprintf(buf, sizeof(buf), "step_kernel_quad<NROT=%d,v2> (4 lanes per env, 16 envs per wave + episode-end helper wave)", c.vehicle.n_rotors); break;
     case StepFamily::Team:
-      std::snprintf(buf, sizeof(buf), "step_kernel_team<%s,NROT=6,v2+arm3> (16 lanes per env: 4 RK4 stages x 4 components, 4 envs per wave + episode-end helper wave)", t); break;
+      std::snprintf(buf, sizeof(buf), "step_kernel_team<%s,NROT=6,v2+arm3> (16 lanes per env: 4 RK4 stages x 4 components, 4 envs per wave + %s)", t,
+                    team_wide(e) ? "one episode-end helper wave per 4" : "episode-end helper wave"); break;
     case StepFamily::Staged:
       std::snprintf(buf, sizeof(buf), "step_kernel_armk<%s,NROT=6> block=320 (4 RK4 stage waves + main wave per 64-env tile)", t); break;
     case StepFamily::TwoWave:
@@ -485,10 +500,13 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
   const uint32_t tb = e.tile_bytes;
   const int32_t n = e.cfg.num_envs;
   switch (e.family) {
-    case StepFamily::Team:   // 16 lanes per env, 4 envs per workgroup: main wave + episode-end helper wave
+    case StepFamily::Team:   // 16 lanes per env; 16 envs per workgroup (four main waves + one episode-end helper wave) while each workgroup has a CU to itself, else 4 (one + one)
       if constexpr (NJ == 3 && !DR) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
         const TeamParamsT<T> TP = make_team<T>(e);
-        return launch(e, timed, step_kernel_team<T, NROT>, dim3(e.n_tiles * 16), dim3(128), 0, s, e.blob, n, int32_t(e.n_tiles * 16),
+        if (team_wide(e))
+          return launch(e, timed, step_kernel_team<T, NROT, 4>, dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, n, int32_t(e.n_tiles * 4),
+                        reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
+        return launch(e, timed, step_kernel_team<T, NROT, 1>, dim3(e.n_tiles * 16), dim3(128), 0, s, e.blob, n, int32_t(e.n_tiles * 16),
                       reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
       }
       break;

@@ -71,6 +71,10 @@ using TeamState = TeamStateT<float>;
 // Blocks that share an XCD therefore take CONSECUTIVE 4-env groups (speed only: any mapping is correct).  gridDim.x is a multiple of 64.
 __device__ __forceinline__ int team_group_of_block(int b, int nblocks) { return (b & 7) * (nblocks >> 3) + (b >> 3); }
 
+// The same for the step kernel's workgroups of four integrating waves = 16 consecutive envs (a quarter of a tile).  A grid that is not a
+// multiple of 8 workgroups (an odd number of tiles) keeps the identity mapping.
+__device__ __forceinline__ int team_group16_of_block(int b, int nblocks) { return (nblocks & 7) ? b : (b & 7) * (nblocks >> 3) + (b >> 3); }
+
 // ---- one env row's registers, and the per-lane role of a lane in its team -------------------------------------------------------------
 template <typename X>
 struct TeamEnvT {
@@ -165,13 +169,14 @@ using TeamOut = TeamOutT<float>;
 // What a reset leaves in this lane's registers: position / waypoint component, final yaw, and the three observation values of the reset
 // state (at rest, level, arm at home).  Lane c < 3 of every quad computes Philox block c; the 12 words are then broadcast inside the quad.
 // Pure function of (seed, global env id, episode): the step kernel's helper wave evaluates it while the main wave integrates.
+// team_reset_draw: the random part (P, WP, final_yaw; the same in the four quads of a row -- it reads the lane's component, never its
+// quad, so the step kernel's helper wave runs it with one QUAD per env); team_reset_obs: the reset observation of this lane from it.
 template <typename X> struct TeamResetT { X P, WP, final_yaw, vA, vB, vC; };
 template <typename X>
-__device__ __forceinline__ TeamResetT<X> team_reset(const TeamParamsT<X>& P, const ColdParams& C, const TeamLaneT<X>& L, int32_t episode, int i) {
-  const X* c = L.c;
+__device__ __forceinline__ TeamResetT<X> team_reset_draw(const ColdParams& C, const X* c, int cc, int32_t episode, int i) {
   uint32_t wds[4];
   const int64_t gid = C.gid0 + i;
-  philox4x32_10(C.seed_lo, C.seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), uint32_t(L.cc), wds);
+  philox4x32_10(C.seed_lo, C.seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), uint32_t(cc), wds);
   uint32_t r[12];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -185,6 +190,13 @@ __device__ __forceinline__ TeamResetT<X> team_reset(const TeamParamsT<X>& P, con
   R.P = fma_(e0, e.px, fma_(e1, e.py, e2 * e.pz));
   R.WP = fma_(e0, e.wp[0][0], fma_(e1, e.wp[0][1], e2 * e.wp[0][2]));
   R.final_yaw = e.final_yaw;
+  R.vA = R.vB = R.vC = X(0);
+  return R;
+}
+template <typename X>
+__device__ __forceinline__ TeamResetT<X> team_reset_obs(const TeamParamsT<X>& P, const TeamLaneT<X>& L, TeamResetT<X> R) {
+  const X* c = L.c;
+  const X e0 = c[TC_E0], e1 = c[TC_E1], e2 = c[TC_E2];
   const X eo = fma_(e0, P.ee_home[0], fma_(e1, P.ee_home[1], e2 * P.ee_home[2]));
   const X zero = X(0), Q = L.cc == 0 ? X(1) : X(0);
   R.vA = (L.q0 ? R.P : (L.q1 ? zero : (L.q2 ? Q : zero))) * c[TC_OBS_A];
@@ -192,6 +204,10 @@ __device__ __forceinline__ TeamResetT<X> team_reset(const TeamParamsT<X>& P, con
   R.vB = (L.q0 ? R.WP - tp : (L.q1 ? zero : (L.q2 ? R.final_yaw : zero))) * c[TC_OBS_B];
   R.vC = (L.q0 ? zero : eo) * c[TC_OBS_C];
   return R;
+}
+template <typename X>
+__device__ __forceinline__ TeamResetT<X> team_reset(const TeamParamsT<X>& P, const ColdParams& C, const TeamLaneT<X>& L, int32_t episode, int i) {
+  return team_reset_obs(P, L, team_reset_draw<X>(C, L.c, L.cc, episode, i));
 }
 
 // A reset row's registers from team_reset's values; the rest of WaypointQuadEnv.reset's result is constant (at rest, level, arm at home,
@@ -309,20 +325,26 @@ template <typename A, typename... R> __device__ __forceinline__ void team_arg(A 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t team_rsrc(void* p, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(bytes), 0x00020000); }
 constexpr uint32_t kOob = 0xFFFFFFFFu;
 
-// One control step of 4 envs per main wavefront.  grid = n_tiles * 16 workgroups of 128 threads: wave 0 integrates, wave 1 helps with
-// episode ends.  At 4096 envs ~10 of the 1024 main waves see an episode end in every launch, the launch is as slow as its slowest wave,
+// One control step of 4 envs per main wavefront.  A workgroup is MW integrating waves and ONE helper wave for their episode ends; the helper
+// holds one QUAD per env (its tests and team_reset_draw read the lane's component, never its quad), so it can serve up to 16 rows.
+//   MW = 4: grid = n_tiles * 4 workgroups of 320 threads, the four integrating waves on the four SIMDs of a CU.  A launch carries a quarter
+//           of the helper waves, helper loads and helper issue slots: 4.45 -> 4.22 us at 4096 envs.  Only while every workgroup has a CU
+//           to itself (at most 16 envs per CU: a second workgroup on a CU puts two integrating waves on EVERY one of its SIMDs -- 6.84
+//           against 5.47 us at 5120 envs); launch_step chooses.
+//   MW = 1: grid = n_tiles * 16 workgroups of 128 threads, one helper per integrating wave (its lanes 16..63 idle), for larger batches.
+// At 4096 envs ~10 of the 1024 main waves see an episode end in every launch, the launch is as slow as its slowest wave,
 // and episode-end code (rarely run on any one CU) costs ~7 clocks per instruction: with everything inline those waves ran 2,100 clocks
 // (0.9 us of 5.8) longer than the rest (tools/stamp_team.py).  So the helper wave evaluates team_reset while the main wave integrates and
-// leaves the values in LDS; after the kernel's ONE barrier the main wave's episode-end path is six LDS reads (+ three terminal-observation
-// stores after its regular stores), and the helper writes Monitor's return / length and adds the ended episodes to its replica of the
+// leaves the values in LDS; after the kernel's ONE barrier the main wave's episode-end path is three LDS reads and the reset observation
+// (+ three terminal-observation stores after its regular stores), and the helper writes Monitor's return / length and adds the ended episodes to its replica of the
 // totals (owned for the launch when the grid has at most kStatsReplicas workgroups: plain read-modify-write; otherwise atomics).
 // Round 3: the helper shares every SIMD with some main wave, so it only spends the reset's ~200 instructions on rows that CAN end their
 // episode in this step -- a conservative test on the loaded state (time limit: exact; hold counter at its limit; height / range within one
 // step's travel of the crash / bounds thresholds).  A row that ends without having been announced (no such case is known) is reset by the
 // main wave itself, so the test only decides who does the work, never the result.  The totals replica is read only when an episode ended.
 // The first 8 dwords of the arguments are what the first loads need; the tile size is a constant of this kernel (one waypoint group, two joint groups).
-template <typename X, int NROT>
-__global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob, int32_t n_envs, int32_t n_blocks, const float* __restrict__ actions,
+template <typename X, int NROT, int MW>
+__global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restrict__ blob, int32_t n_envs, int32_t n_blocks, const float* __restrict__ actions,
                                                         const void* __restrict__ lane_consts, float* __restrict__ obs, X* __restrict__ reward_out,
                                                         uint8_t* __restrict__ done, uint32_t* __restrict__ info, const StepTail tl, const ColdParams C) {
   constexpr uint32_t tile_bytes = kIntBytes + 7u * 64u * 4u * uint32_t(sizeof(X));
@@ -338,14 +360,17 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
   }
   static_assert(NROT == 6, "team kernel: 6-rotor airframe");
   constexpr int AD = 7, OD = 29;
-  __shared__ X rst[6][64];                         // team_reset's values, lane for lane
-  __shared__ uint32_t fl[4][4];                    // per row: bit 0 ended on a real env, bit 1 reset | info bits | length | return
-  __shared__ uint32_t have[4];                     // per row: the helper has left reset values
+  __shared__ X rst[3][64];                         // team_reset_draw's values (position, waypoint, final yaw), helper lane for lane: [4 row + component]
+  static_assert(MW == 1 || MW == 4, "one helper wave of 64 lanes = 16 quads serves at most four integrating waves");
+  constexpr int ROWS = 4 * MW;                     // envs of a workgroup
+  __shared__ uint32_t fl[ROWS][4];                   // per row: bit 0 ended on a real env, bit 1 reset | info bits | length | return
+  __shared__ uint32_t have[ROWS];                   // per row: the helper has left reset values
   __shared__ unsigned long long acc[S_COUNT];      // this launch's additions to the Monitor totals
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-  const int role = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
+  const int role = wave == MW ? 1 : 0;             // waves 0..MW-1 integrate four envs each, the last wave helps all of them
   team_arg(blob, n_envs, n_blocks, actions, lane_consts);   // what the first loads need: ONE small batch of argument loads, nothing else in front of it
   AMENV_STAMP(0);
   // Both waves of the workgroup start the same way -- constants, state, actions: ONE batch of kernel-argument loads and the vector loads
@@ -353,9 +378,9 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
   // first load was issued).  The helper needs the state for its episode-end test anyway; its copies of the lines come from the L1 / L2.
   TeamLaneT<X> L;
   L.init(lane_consts);
-  const int row = L.lane >> 4;
-  const int i0 = team_group_of_block(int(blockIdx.x), n_blocks) * 4;   // first env of this workgroup (wave-uniform; its 4 envs share a tile)
-  const int i = i0 + row;                                                    // env of this row
+  const int row = role ? L.lane >> 2 : wave * 4 + (L.lane >> 4);        // of the workgroup's 16: an integrating wave has 16 lanes per row, the helper one quad
+  const int i0 = (MW == 1 ? team_group_of_block(int(blockIdx.x), n_blocks) : team_group16_of_block(int(blockIdx.x), n_blocks)) * ROWS;   // first env of this workgroup (wave-uniform; its envs share a tile)
+  const int i = i0 + row;                                                      // env of this row
   const bool active = i < n_envs;
   char* tile = static_cast<char*>(blob) + size_t(i0 >> 6) * tile_bytes;
   const int ia = active ? i : n_envs - 1;                   // rows past the end redo the last env's arithmetic (their outputs are masked)
@@ -386,9 +411,11 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
 #else
     constexpr bool kPredict = true;
 #endif
-    const bool may = kPredict && (((mm >> (L.lane & 48)) & 0xFFFFull) != 0ull || E.step >= P.max_steps || ((E.flags & AMENV_FLAGBIT_FWR) && E.counter >= P.counter_limit) ||
+    const bool serve = row < ROWS;                   // (MW = 1: the helper's lanes 16..63 have no row)
+    const bool hlead = serve && L.cc == 0;           // one lane per row of the helper
+    const bool may = kPredict && serve && (((mm >> (L.lane & 60)) & 0xFull) != 0ull || E.step >= P.max_steps || ((E.flags & AMENV_FLAGBIT_FWR) && E.counter >= P.counter_limit) ||
                                   (P.flags & AMENV_FLAG_NAN_GUARD));
-    if (L.lead) have[row] = may ? 1u : 0u;
+    if (hlead) have[row] = may ? 1u : 0u;
     unsigned long long* totals = tl.stats + size_t(blockIdx.x & (kStatsReplicas - 1)) * kStatsStride;
     unsigned long long mine = 0ull;
     bool fetched = false;                           // wave-uniform
@@ -396,20 +423,19 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
       if (owned && L.lane < S_COUNT) mine = totals[L.lane];   // an episode end is likely: the replica's line, in flight during the barrier
       fetched = true;
       if (may) {
-        const TeamResetT<X> R = team_reset(P, C, L, E.episode, i);
+        const TeamResetT<X> R = team_reset_draw<X>(C, L.c, L.cc, E.episode, i);
         rst[0][L.lane] = R.P; rst[1][L.lane] = R.WP; rst[2][L.lane] = R.final_yaw;
-        rst[3][L.lane] = R.vA; rst[4][L.lane] = R.vB; rst[5][L.lane] = R.vC;
       }
     }
     __syncthreads();
 #ifdef AMENV_TEAM_DIAG_NOPOST   // diagnostic build: the helper leaves after the barrier (no Monitor service: timing only)
     return;
 #endif
-    const bool ended = (fl[row][0] & 1u) != 0 && L.lead;   // one lane per ended row
+    const bool ended = hlead && (fl[hlead ? row : 0][0] & 1u) != 0;   // one lane per ended row
     if (__ballot(ended) != 0ull) {   // wave-uniform
       if (!fetched && owned && L.lane < S_COUNT) mine = totals[L.lane];
       if (ended) {
-        const uint32_t bits = fl[row][1];
+        const uint32_t bits = fl[row][1];          // (ended: row < ROWS)
         const int ep_len = int(fl[row][2]);
         const float ep_ret = __uint_as_float(fl[row][3]);
         if (tl.ep_return) tl.ep_return[i] = ep_ret;
@@ -437,6 +463,17 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
   uint32_t voA = L.okA ? rowb + L.offA * 4u : kOob, voB = L.okB ? rowb + L.offB * 4u : kOob, voC = L.okC ? rowb + L.offC * 4u : kOob;
   asm volatile("" : "+v"(voA), "+v"(voB), "+v"(voC));
   const __amdgpu_buffer_rsrc_t r_obs = team_rsrc(obs, obs_bytes), r_term = team_rsrc(tl.terminal_obs, tl.terminal_obs ? obs_bytes : 0u);
+  // the same for the state stores and the per-env outputs of the fp32 build: team_store's offsets depend on the lane and the env only (byte
+  // offsets into this workgroup's tile; the lead lane's slot in reward / info / done, out of range for every other lane)
+  uint32_t so1 = 0, so2 = 0, voR = kOob, voD = kOob;
+  if constexpr (sizeof(X) == 4) {
+    constexpr uint32_t GB = 64u * 4u * 4u;
+    const uint32_t eoff = (uint32_t(i & 63) * 4u + uint32_t(L.cc)) * 4u;
+    so1 = kIntBytes + uint32_t(L.bb) * GB + eoff;                                        // quad b writes group b
+    so2 = L.q2 ? eoff : kIntBytes + (L.q0 ? 5u : (L.q1 ? 6u : 4u)) * GB + eoff;         // joint angles | joint rates | int plane | waypoint
+    voR = active && L.lead ? uint32_t(i) * 4u : kOob; voD = active && L.lead ? uint32_t(i) : kOob;
+    asm volatile("" : "+v"(so1), "+v"(so2), "+v"(voR), "+v"(voD));
+  }
   AMENV_STAMP(1);          // loads issued
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(2);          // loads landed
@@ -455,16 +492,35 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
   const X tA = o.vA, tB = o.vB, tC = o.vC;                  // the terminal observation of a row that ended
   if (any_end && resets) {
     TeamResetT<X> R;
-    if (have[row]) R = TeamResetT<X>{rst[0][L.lane], rst[1][L.lane], rst[2][L.lane], rst[3][L.lane], rst[4][L.lane], rst[5][L.lane]};
-    else R = team_reset(P, C, L, E.episode, i);             // not announced by the helper's test (never observed): same values, computed here
-    team_apply_reset(L, R, E, o);
+    const int hl = row * 4 + L.cc;                          // the helper's lane for this row and component
+    if (have[row]) R = TeamResetT<X>{rst[0][hl], rst[1][hl], rst[2][hl], X(0), X(0), X(0)};
+    else R = team_reset_draw<X>(C, L.c, L.cc, E.episode, i);   // not announced by the helper's test (never observed): same values, computed here
+    team_apply_reset(L, team_reset_obs(P, L, R), E, o);
   }
   AMENV_STAMP(5);          // barrier + reset values
-  team_store(tile, i, L, E, resets);
+  if constexpr (sizeof(X) == 4) {   // team_store with the offsets formed above; the waypoint group (quad 3) is written at a reset only
+    const __amdgpu_buffer_rsrc_t r_tile = team_rsrc(tile, tile_bytes);
+    const bool l3 = L.cc == 3;
+    const X g0 = sel(l3, E.final_yaw, E.y.P), g1 = sel(l3, E.last_distance, E.y.V), g3 = sel(l3, E.ep_return, E.y.W);
+    const X sv = sel(L.q0, g0, sel(L.q1, g1, sel(L.q2, E.y.Q, g3)));
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(sv), r_tile, int(so1), 0, 0);
+    const int ival = sel(L.cc == 0, E.step, sel(L.cc == 1, E.counter, sel(L.cc == 2, E.flags, E.episode)));
+    const float s2 = sel(L.q0, E.y.TH, sel(L.q1, E.y.THD, sel(L.q2, __int_as_float(ival), E.WP)));
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(s2), r_tile, int(L.bb == 3 && !resets ? kOob : so2), 0, 0);
+  } else {
+    team_store(tile, i, L, E, resets);
+  }
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vA)), r_obs, int(voA), 0, 0);
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vB)), r_obs, int(voB), 0, 0);
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vC)), r_obs, int(voC), 0, 0);
-  if (active && L.lead) { reward_out[uint32_t(i)] = o.reward; done[uint32_t(i)] = o.ended ? 1 : 0; info[uint32_t(i)] = o.bits; }
+  if constexpr (sizeof(X) == 4) {   // lead lane of a real env; every other lane's offset is out of range
+    const uint32_t nb = uint32_t(n_envs);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.reward), team_rsrc(reward_out, nb * 4u), int(voR), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b8(uint8_t(o.ended ? 1 : 0), team_rsrc(done, nb), int(voD), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(int(o.bits), team_rsrc(info, nb * 4u), int(voR), 0, 0);
+  } else {
+    if (active && L.lead) { reward_out[uint32_t(i)] = o.reward; done[uint32_t(i)] = o.ended ? 1 : 0; info[uint32_t(i)] = o.bits; }
+  }
   if (any_end) {           // wave-uniform; rows that did not end store nowhere
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tA)), r_term, int(o.ended ? voA : kOob), 0, 0);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tB)), r_term, int(o.ended ? voB : kOob), 0, 0);
@@ -474,8 +530,8 @@ __global__ __launch_bounds__(128) void step_kernel_team(void* __restrict__ blob,
 #ifdef AMENV_STAMPS
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(7);          // stores acknowledged
-  if (L.lane == 0 && blockIdx.x < kStampWaves)
-    for (int kk = 0; kk < kStampSlots; kk++) tl.stats[kStampBase + blockIdx.x * kStampSlots + kk] = stamps_[kk];
+  if (L.lane == 0 && blockIdx.x * MW + wave < kStampWaves)   // the integrating waves of the first workgroups
+    for (int kk = 0; kk < kStampSlots; kk++) tl.stats[kStampBase + (blockIdx.x * MW + wave) * kStampSlots + kk] = stamps_[kk];
 #endif
 }
 

@@ -100,7 +100,10 @@ template <typename X> struct X3 { X v, r1, r2; };   // a 3-vector (component per
 template <typename X> AMENV_FN X3<X> x3(X v) { return X3<X>{v, rot1(v), rot2(v)}; }
 template <typename X> AMENV_FN X cross(const X3<X>& a, const X3<X>& b) { return fma_(a.r1, b.r2, -(a.r2 * b.r1)); }
 // cross product a x b when only `a` has its rotations cached: the other operand's rotations ride as DPP modifiers of the two
-// multiplies (v_mul_f32_dpp; an FMA cannot carry one), so no v_mov_b32_dpp is spent on `b`
+// multiplies (v_mul_f32_dpp), so no v_mov_b32_dpp is spent on `b`.  (The hardware has a DPP form of the two-operand FMA, v_fmac_f32_dpp,
+// but the compiler never forms it: it selects the three-operand v_fma_f32 and shrinks it to v_fmac_f32 only after register allocation,
+// behind the pass that folds DPP moves.  Inline assembly is no way round that: the compiler pads the "VALU writes a VGPR, DPP reads it"
+// hazard for its own DPP instructions only, and an s_nop written into the asm string costs the slot the fold would save.)
 template <typename X> AMENV_FN X cross_c(const X3<X>& a, X b) { return a.r1 * rot2(b) - a.r2 * rot1(b); }
 template <typename X> struct TM { X c0, c1, c2; };  // 3x3 matrix: lane i holds row i, one register per column
 template <typename X> AMENV_FN X matvec(const TM<X>& M, X v) { return fma_(M.c0, bc<0>(v), fma_(M.c1, bc<1>(v), M.c2 * bc<2>(v))); }
@@ -138,9 +141,11 @@ AMENV_FN TeamStage<X> team_kin_stage(const PT& P, const X* c, X TH, X THD, X thd
   X sIO = T(0), sG = T(0);                               // the isotropic parts m |r|^2 and 2 m (u . r): added to the diagonals once, after the links
   TM<X> R;
   X p, pd, pdd, w, al;
+  // joint k sits in lane k, so sin(bc<k>(TH)) = bc<k>(sin(TH)): ONE sine and cosine per register, their results broadcast per joint
+  X sT, cT;
+  sincos_t(TH, sT, cT);
   {   // joint 1 about z at the start of the chain and link 1 behind it: R = Rz(th), w = thd e_z, al = thdd e_z, the frame origin at rest
-    X s, co;
-    sincos_t(bc<0>(TH), s, co);
+    const X s = bc<0>(sT), co = bc<0>(cT);
     const X td = bc<0>(THD), tdd = bc<0>(thdd);
     const X cov = fma_(co, c[TC_E01], e2), sv = s * c[TC_ZX];
     auto zrot = [&](X v) { return fma_(cov, v, sv * qp<1, 0, 2, 3>(v)); };   // Rz v
@@ -168,8 +173,7 @@ AMENV_FN TeamStage<X> team_kin_stage(const PT& P, const X* c, X TH, X THD, X thd
       Tn = fma_(m, cross_c(x3(r), a_), fma_(tdd, J.c2, (td * td) * zx(J.c2)));   // m r x a + J al + w x (J w)
     }
     {   // across joint 2 (about link 1's x axis = column 0 of R) with the parent at w = thd e_z
-      X s2, co2;
-      sincos_t(bc<1>(TH), s2, co2);
+      const X s2 = bc<1>(sT), co2 = bc<1>(cT);
       const X td1 = bc<1>(THD), tdd1 = bc<1>(thdd);
       const X Ro = zrot(c[TC_O1]), zRo = zx(Ro);
       pd = td * zRo;
@@ -208,9 +212,7 @@ AMENV_FN TeamStage<X> team_kin_stage(const PT& P, const X* c, X TH, X THD, X thd
     const X Jw = matvec(J, w);
     Tn = Tn + (fma_(m, cross_c(x3(r), a_), matvec(J, al)) + cross_c(xw, Jw));
   };
-  auto advance_x = [&](X th, X td, X tdd, const T* o) {   // across a joint about its frame's x axis (column 0 of R)
-    X s, co;
-    sincos_t(th, s, co);
+  auto advance_x = [&](X s, X co, X td, X tdd, const T* o) {   // across a joint about its frame's x axis (column 0 of R); s, co: of its angle
     const X Ro = fma_(R.c0, o[0], fma_(R.c1, o[1], R.c2 * o[2]));
     const X3<X> xRo = x3(Ro), xw = x3(w);
     const X wRo = cross(xw, xRo);
@@ -224,7 +226,7 @@ AMENV_FN TeamStage<X> team_kin_stage(const PT& P, const X* c, X TH, X THD, X thd
     rotate_cols<0>(R, s, co);
   };
   link(1);
-  advance_x(bc<2>(TH), bc<2>(THD), bc<2>(thdd), P.o2);
+  advance_x(bc<2>(sT), bc<2>(cT), bc<2>(THD), bc<2>(thdd), P.o2);
   link(2);
   TeamStage<X> k;
   // composite inertia about the system CoM, I_c = I_O - (|S|^2 1 - S S^T) / mtot, its inverse = adjugate (columns = cross products of columns) / det
@@ -286,15 +288,16 @@ template <typename X, typename PT> AMENV_FN X team_vdot(const PT& P, const X* c,
 template <typename X, typename PT> AMENV_FN X team_tool_offset(const PT& P, const X* c, const TeamStateT<X>& y) {
   using T = typename LaneTraits<X>::T;
   const X e0 = c[TC_E0], e1 = c[TC_E1], e2 = c[TC_E2];
-  X s, co;
-  sincos_t(bc<0>(y.TH), s, co);
+  X sT, cT;
+  sincos_t(y.TH, sT, cT);       // one sine and cosine for the three joints (joint k in lane k), broadcast per joint
+  X s = bc<0>(sT), co = bc<0>(cT);
   TM<X> R{fma_(co, e0, s * e1), fma_(co, e1, -(s * e0)), e2};
   X p = c[TC_O0];
   p = p + fma_(R.c0, P.o1[0], fma_(R.c1, P.o1[1], R.c2 * P.o1[2]));
-  sincos_t(bc<1>(y.TH), s, co);
+  s = bc<1>(sT); co = bc<1>(cT);
   rotate_cols<0>(R, s, co);
   p = p + fma_(R.c0, P.o2[0], fma_(R.c1, P.o2[1], R.c2 * P.o2[2]));
-  sincos_t(bc<2>(y.TH), s, co);
+  s = bc<2>(sT); co = bc<2>(cT);
   rotate_cols<0>(R, s, co);
   p = p + fma_(R.c0, P.tool[0], fma_(R.c1, P.tool[1], R.c2 * P.tool[2]));
   // world = Rq^T body (|q| = 1)

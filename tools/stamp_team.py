@@ -40,3 +40,12 @@ t = R - R[:, :, 0:1]
 print(f"{int(ended.sum())} wave-launches with an episode end, {int((~ended).sum())} without (64 of {a.envs // 4} waves sampled)")
 for k, n_ in ((1, "loads issued"), (2, "loads landed"), (4, "advance done (RK4, task, episode end)"), (5, "barrier passed, reset values taken"), (6, "stores issued"), (7, "drained")):
     print(f"   {n_:40s} {np.median(t[:, :, k][~ended]):8.0f} {np.median(t[:, :, k][ended]):8.0f}")
+# The sampled waves are the four integrating waves of the first 16 workgroups (wave w of workgroup b at index 4 b + w).  Two of them on
+# one SIMD would share its issue slots and show up as a doubled compute span (loads landed -> advance done) in a fixed wave position.
+span = (t[:, :, 4] - t[:, :, 2])[:, :, None].reshape(t.shape[0], 16, 4)
+print("compute span (loads landed -> advance done) by wave position in its workgroup: median / 99th percentile / max")
+for w in range(4):
+    s = span[:, :, w]
+    print(f"   wave {w}: {np.median(s):8.0f} {np.percentile(s, 99):8.0f} {s.max():8.0f}")
+start = (R[:, :, 0].reshape(R.shape[0], 16, 4) - R[:, :, 0].reshape(R.shape[0], 16, 4).min(axis=2, keepdims=True))
+print("start of wave w after the first wave of its workgroup (clocks, median):", " ".join(f"{np.median(start[:, :, w]):.0f}" for w in range(4)))
