@@ -22,6 +22,8 @@
 // agree with the one-lane kernel to rounding (tests: <= 3e-6 rel per step against the fp64 oracle for the fp32 build, <= 1e-12 for the fp64
 // build), not bit for bit.
 #pragma once
+#include <type_traits>
+
 #include "amenv_kernels.hpp"
 
 #define AMENV_FN __device__ __forceinline__
@@ -93,15 +95,21 @@ struct TeamLaneT {
   bool okA, okB, okC;
   X c[((kTeamConsts + 3) / 4) * 4];              // this lane's constants
   __device__ __forceinline__ void init(const TeamParamsT<X>& P) { init(P.consts); }
-  __device__ __forceinline__ void init(const void* table) {
+  __device__ __forceinline__ void init_lane() {  // what addresses need: the step kernel issues its loads right behind this
     lane = int(threadIdx.x) & 63; cc = lane & 3; bb = (lane >> 2) & 3;
     q0 = bb == 0; q1 = bb == 1; q2 = bb == 2; lead = (lane & 15) == 0;
+  }
+  __device__ __forceinline__ void init_obs_cols() {   // (init_lane done)
     // A = [p/10 | v/5 | q | w/5] by quad, B = [(wp - task point)/2 | 0 | yaw/pi | th/pi], C = [thd/5 | tool offset*2]
     // (arithmetic, not nested selects: the compiler turned those into EXEC-masked branches in front of the first load)
     offA = uint32_t(cc + 3 * bb + (bb == 3 ? 1 : 0));                       // 0 + c | 3 + c | 6 + c | 10 + c
     offB = uint32_t(13 + 3 * bb - (bb == 3 ? 2 : 0) + (q2 ? 0 : cc));       // 13 + c | 16 + c | 19 | 20 + c
     offC = uint32_t(23 + cc + (bb > 0 ? 3 : 0));                            // 23 + c | 26 + c
     okA = cc < 3 || q2; okB = q2 ? cc == 0 : cc < 3; okC = cc < 3 && bb < 2;
+  }
+  __device__ __forceinline__ void init(const void* table) { init_lane(); init_obs_cols(); load_table(table); }
+  // c[] from the per-lane table (init_lane done): one load per 16-byte piece
+  __device__ __forceinline__ void load_table(const void* table) {
     constexpr int NC4 = (kTeamConsts + 3) / 4;
     if constexpr (sizeof(X) == 4) {              // float4 pieces [k / 4][lane][k % 4]
       const float4* tab = static_cast<const float4*>(table);
@@ -306,14 +314,6 @@ __device__ __forceinline__ void team_store_outputs(const TeamLaneT<X>& L, const 
   }
 }
 
-// "This wave reads these registers here": an empty asm per value.  The helper wave of the step kernel starts with it, so that the loads both
-// waves issue in front of the role branch stay there -- the compiler otherwise sinks every load only the main wave consumes into the main
-// wave's branch, behind that branch's own (second) batch of kernel-argument loads.
-template <typename X> __device__ __forceinline__ void team_touch(X v) {
-  if constexpr (sizeof(X) == 4) asm volatile("" ::"v"(v));
-  else asm volatile("" ::"v"(__double2loint(v)), "v"(__double2hiint(v)));
-}
-
 // "These kernel arguments are read here": an empty asm per wave-uniform value.  The step kernel starts with the arguments its first vector
 // loads need, so that they arrive in ONE batch of scalar loads issued at wave start; left to itself the compiler batches arguments by
 // basic block, and every batch in front of the first vector load is a full (dependent) trip to the kernel-argument segment.
@@ -324,6 +324,55 @@ template <typename A, typename... R> __device__ __forceinline__ void team_arg(A 
 // last env) are masked by their OFFSET instead of by EXEC, so the store tail of the step kernel has no branches
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t team_rsrc(void* p, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(bytes), 0x00020000); }
 constexpr uint32_t kOob = 0xFFFFFFFFu;
+
+// The wave-uniform parameters of the step kernel: scalar loads from the device block behind the per-lane table (see team_block_bytes).
+// Each role reads them inside its branch through a pointer it has passed through an empty asm (team_launder): loads the compiler can tell
+// to be the same in both roles it issues in front of the role branch, where their registers -- spilled at once, the kernel runs at the
+// SGPR limit -- put a wait for the whole batch in front of the integrating wave's first vector load.
+template <typename S> __device__ __forceinline__ S team_scalar_load(const void* p) {   // p: wave-uniform
+  typedef const __attribute__((address_space(4))) uint32_t ConstWord;   // constant address space: uniform loads from it are scalar loads
+  ConstWord* src = (ConstWord*)p;
+  S v;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&v);
+  static_assert(sizeof(S) % 4 == 0, "copied word by word");
+#pragma unroll
+  for (int k = 0; k < int(sizeof(S) / 4); k++) dst[k] = src[k];
+  return v;
+}
+template <typename X> __device__ __forceinline__ TeamParamsT<X> team_load_params(const void* block) {
+  return team_scalar_load<TeamParamsT<X>>(static_cast<const char*>(block) + team_table_bytes<X>());
+}
+__device__ __forceinline__ const void* team_launder(const void* p) { asm volatile("" : "+s"(p)); return p; }
+
+// The step kernel's arguments behind the first 32 bytes, as they lie in its kernel-argument segment (parameters in order, each at its
+// natural alignment, structs by value in place).  The integrating wave reads them from the segment itself, behind its vector loads
+// (team_late_args): taken from the parameters, the compiler loads what both roles use in front of the role branch and, short of
+// registers, copies or spills it at the top of the integrating branch -- a wait for a whole trip to the argument segment in front of
+// the first vector load.  The helper wave uses the parameters.
+template <typename X> struct TeamStepLateArgs { float* obs; X* reward_out; uint8_t* done; uint32_t* info; StepTail tl; ColdParams C; };
+struct TeamStepFirstArgs { void* blob; int32_t n_envs, n_blocks; const float* actions; const void* lane_consts; };
+// The kernel's type as these two structs spell it: step_kernel_team's real parameter list is held to it below the kernel, so a parameter
+// inserted, moved or retyped without the structs following does not compile.
+template <typename X> using TeamStepKernelFn = void (*)(decltype(TeamStepFirstArgs::blob), decltype(TeamStepFirstArgs::n_envs), decltype(TeamStepFirstArgs::n_blocks),
+                                                        decltype(TeamStepFirstArgs::actions), decltype(TeamStepFirstArgs::lane_consts), decltype(TeamStepLateArgs<X>::obs),
+                                                        decltype(TeamStepLateArgs<X>::reward_out), decltype(TeamStepLateArgs<X>::done), decltype(TeamStepLateArgs<X>::info),
+                                                        decltype(TeamStepLateArgs<X>::tl), decltype(TeamStepLateArgs<X>::C));
+template <typename X> __device__ __forceinline__ TeamStepLateArgs<X> team_late_args() {
+  static_assert(sizeof(TeamStepFirstArgs) == 32 && alignof(TeamStepLateArgs<X>) == 8 && alignof(StepTail) == 8 && alignof(ColdParams) == 8,
+                "TeamStepLateArgs mirrors the argument segment from byte 32 on");
+  const void* ka = team_launder((const void*)__builtin_amdgcn_kernarg_segment_ptr());
+  struct Head { float* obs; X* reward_out; uint8_t* done; uint32_t* info; StepTail tl; };   // (C: team_late_cold)
+  static_assert(sizeof(Head) == offsetof(TeamStepLateArgs<X>, C), "the arguments in front of ColdParams");
+  const Head h = team_scalar_load<Head>(static_cast<const char*>(ka) + sizeof(TeamStepFirstArgs));
+  TeamStepLateArgs<X> a;
+  a.obs = h.obs; a.reward_out = h.reward_out; a.done = h.done; a.info = h.info; a.tl = h.tl;
+  return a;
+}
+// ... and ColdParams alone, where the integrating wave needs it: on the path that computes a reset the helper did not announce
+template <typename X> __device__ __forceinline__ ColdParams team_late_cold() {
+  const void* ka = team_launder((const void*)__builtin_amdgcn_kernarg_segment_ptr());
+  return team_scalar_load<ColdParams>(static_cast<const char*>(ka) + sizeof(TeamStepFirstArgs) + offsetof(TeamStepLateArgs<X>, C));
+}
 
 // One control step of 4 envs per main wavefront.  A workgroup is MW integrating waves and ONE helper wave for their episode ends; the helper
 // holds one QUAD per env (its tests and team_reset_draw read the lane's component, never its quad), so it can serve up to 16 rows.
@@ -343,21 +392,13 @@ constexpr uint32_t kOob = 0xFFFFFFFFu;
 // step's travel of the crash / bounds thresholds).  A row that ends without having been announced (no such case is known) is reset by the
 // main wave itself, so the test only decides who does the work, never the result.  The totals replica is read only when an episode ended.
 // The first 8 dwords of the arguments are what the first loads need; the tile size is a constant of this kernel (one waypoint group, two joint groups).
+// The ORDER AND TYPES of the parameters are read by team_late_args through TeamStepFirstArgs / TeamStepLateArgs (the integrating wave takes
+// everything behind lane_consts from the argument segment): change them there too -- the static_assert below the kernel insists.
 template <typename X, int NROT, int MW>
 __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restrict__ blob, int32_t n_envs, int32_t n_blocks, const float* __restrict__ actions,
                                                         const void* __restrict__ lane_consts, float* __restrict__ obs, X* __restrict__ reward_out,
                                                         uint8_t* __restrict__ done, uint32_t* __restrict__ info, const StepTail tl, const ColdParams C) {
   constexpr uint32_t tile_bytes = kIntBytes + 7u * 64u * 4u * uint32_t(sizeof(X));
-  // wave-uniform parameters: scalar loads from the device block behind the per-lane table (see team_block_bytes)
-  TeamParamsT<X> P;
-  {
-    typedef const __attribute__((address_space(4))) uint32_t ConstWord;   // constant address space: uniform loads from it are scalar loads
-    ConstWord* src = (ConstWord*)(static_cast<const char*>(lane_consts) + team_table_bytes<X>());
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&P);
-    static_assert(sizeof(TeamParamsT<X>) % 4 == 0, "copied word by word");
-#pragma unroll
-    for (int k = 0; k < int(sizeof(TeamParamsT<X>) / 4); k++) dst[k] = src[k];
-  }
   static_assert(NROT == 6, "team kernel: 6-rotor airframe");
   constexpr int AD = 7, OD = 29;
   __shared__ X rst[3][64];                         // team_reset_draw's values (position, waypoint, final yaw), helper lane for lane: [4 row + component]
@@ -373,30 +414,34 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   const int role = wave == MW ? 1 : 0;             // waves 0..MW-1 integrate four envs each, the last wave helps all of them
   team_arg(blob, n_envs, n_blocks, actions, lane_consts);   // what the first loads need: ONE small batch of argument loads, nothing else in front of it
   AMENV_STAMP(0);
-  // Both waves of the workgroup start the same way -- constants, state, actions: ONE batch of kernel-argument loads and the vector loads
-  // right behind it (with the role branch first, the main wave's arguments arrived in a second, dependent batch: +370 clocks before its
-  // first load was issued).  The helper needs the state for its episode-end test anyway; its copies of the lines come from the L1 / L2.
+  // The arguments of the first loads arrive in ONE batch of scalar loads issued at wave start (team_arg above); the role branch follows at
+  // once, and each role issues only the loads it uses.  An integrating wave: state, actions, then the per-lane table (vector loads
+  // return in order: the state stands in front).  The scheduling fence behind its loads keeps them in front of the (second, dependent)
+  // batch of scalar loads that the rest of the branch needs.  The helper: P, V and the int plane for its episode-end test, nothing of
+  // the table.
   TeamLaneT<X> L;
-  L.init(lane_consts);
+  L.init_lane();
   const int row = role ? L.lane >> 2 : wave * 4 + (L.lane >> 4);        // of the workgroup's 16: an integrating wave has 16 lanes per row, the helper one quad
   const int i0 = (MW == 1 ? team_group_of_block(int(blockIdx.x), n_blocks) : team_group16_of_block(int(blockIdx.x), n_blocks)) * ROWS;   // first env of this workgroup (wave-uniform; its envs share a tile)
   const int i = i0 + row;                                                      // env of this row
   const bool active = i < n_envs;
   char* tile = static_cast<char*>(blob) + size_t(i0 >> 6) * tile_bytes;
-  const int ia = active ? i : n_envs - 1;                   // rows past the end redo the last env's arithmetic (their outputs are masked)
   TeamEnvT<X> E;
-  team_load_issue(tile, i, L, E);
-  const float act_f = actions[size_t(ia) * AD + L.cc];                                    // a0..a3: one per lane
-  const float actj_f = actions[size_t(ia) * AD + 4 + (L.cc < 3 ? L.cc : 2)];               // joint commands a4..a6
 #ifdef AMENV_TEAM_DIAG_NOHELPER   // diagnostic build: the helper wave leaves at once (no episode-end service: timing only)
   if (role == 1) { __syncthreads(); return; }
 #endif
   if (role == 1) {
-    // (the helper "reads" everything the main wave loaded -- see team_touch -- and drops it at once: its own work needs few registers)
-#pragma unroll
-    for (int k = 0; k < kTeamConsts; k++)
-      if (k < TC_ALLOC0 || k >= TC_GV1) team_touch(L.c[k]);
-    team_touch(E.y.Q); team_touch(E.y.W); team_touch(E.y.TH); team_touch(E.y.THD); team_touch(E.WP); team_touch(act_f); team_touch(actj_f);
+    {   // the helper's three loads
+      constexpr uint32_t GB = 64u * 4u * sizeof(X);
+      const uint32_t eoff = (uint32_t(i & 63) * 4u + uint32_t(L.cc)) * uint32_t(sizeof(X));
+      E.y.P = *reinterpret_cast<const X*>(tile + kIntBytes + eoff);
+      E.y.V = *reinterpret_cast<const X*>(tile + kIntBytes + GB + eoff);
+      const int4 iv = *(reinterpret_cast<const int4*>(tile) + (i & 63));
+      E.step = iv.x; E.counter = iv.y; E.flags = iv.z; E.episode = iv.w;
+    }
+    const TeamParamsT<X> P = team_load_params<X>(team_launder(lane_consts));
+    const X ce[3] = {L.cc == 0 ? X(1) : X(0), L.cc == 1 ? X(1) : X(0), L.cc == 2 ? X(1) : X(0)};   // TC_E0..E2 of this lane (team_reset_draw reads nothing else)
+    static_assert(TC_E0 == 0 && TC_E1 == 1 && TC_E2 == 2, "ce[] stands in for c[] in team_reset_draw");
     const bool owned = n_blocks <= kStatsReplicas;   // wave-uniform
     if (L.lane < S_COUNT) acc[L.lane] = 0ull;
     // Can this row's episode end in this step?  Lane-local tests + one ballot (the helper shares its SIMD with an integrating wave: no DPP,
@@ -423,7 +468,7 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
       if (owned && L.lane < S_COUNT) mine = totals[L.lane];   // an episode end is likely: the replica's line, in flight during the barrier
       fetched = true;
       if (may) {
-        const TeamResetT<X> R = team_reset_draw<X>(C, L.c, L.cc, E.episode, i);
+        const TeamResetT<X> R = team_reset_draw<X>(C, ce, L.cc, E.episode, i);
         rst[0][L.lane] = R.P; rst[1][L.lane] = R.WP; rst[2][L.lane] = R.final_yaw;
       }
     }
@@ -454,6 +499,17 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
 #ifndef AMENV_TEAM_DIAG_NOPRIO
   __builtin_amdgcn_s_setprio(3);   // every SIMD also holds some workgroup's helper wave: the integrating wave goes first whenever both can issue
 #endif
+  const int ia = active ? i : n_envs - 1;                   // rows past the end redo the last env's arithmetic (their outputs are masked)
+  team_load_issue(tile, i, L, E);
+  const float act_f = actions[size_t(ia) * AD + L.cc];                                    // a0..a3: one per lane
+  const float actj_f = actions[size_t(ia) * AD + 4 + (L.cc < 3 ? L.cc : 2)];               // joint commands a4..a6
+  L.load_table(lane_consts);
+  __builtin_amdgcn_sched_barrier(0);   // every vector load of this wave is issued before its parameters are asked for
+  const TeamParamsT<X> P = team_load_params<X>(team_launder(lane_consts));
+  const TeamStepLateArgs<X> A = team_late_args<X>();   // (this branch names no parameter behind lane_consts)
+  __builtin_amdgcn_sched_barrier(0);   // ... and ALL its scalar loads in front of the first wait for one: one trip, not one per batch the scheduler forms
+  L.init_obs_cols();
+  const ColdParams Cm{};   // (team_advance<HELPED> reads none of it)
   team_load_unpack(E);
   const X act = X(act_f), actj = X(actj_f);
   // store plumbing, formed while the loads are in flight (pinned there: the scheduler would otherwise sink it into the tail, which the
@@ -462,7 +518,7 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   const uint32_t rowb = uint32_t(i) * uint32_t(OD * 4);
   uint32_t voA = L.okA ? rowb + L.offA * 4u : kOob, voB = L.okB ? rowb + L.offB * 4u : kOob, voC = L.okC ? rowb + L.offC * 4u : kOob;
   asm volatile("" : "+v"(voA), "+v"(voB), "+v"(voC));
-  const __amdgpu_buffer_rsrc_t r_obs = team_rsrc(obs, obs_bytes), r_term = team_rsrc(tl.terminal_obs, tl.terminal_obs ? obs_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t r_obs = team_rsrc(A.obs, obs_bytes), r_term = team_rsrc(A.tl.terminal_obs, A.tl.terminal_obs ? obs_bytes : 0u);
   // the same for the state stores and the per-env outputs of the fp32 build: team_store's offsets depend on the lane and the env only (byte
   // offsets into this workgroup's tile; the lead lane's slot in reward / info / done, out of range for every other lane)
   uint32_t so1 = 0, so2 = 0, voR = kOob, voD = kOob;
@@ -477,7 +533,7 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   AMENV_STAMP(1);          // loads issued
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(2);          // loads landed
-  TeamOutT<X> o = team_advance<NROT, true>(P, C, L, E, act, actj, i, active, nullptr, nullptr, nullptr);
+  TeamOutT<X> o = team_advance<NROT, true>(P, Cm, L, E, act, actj, i, active, nullptr, nullptr, nullptr);
   const bool resets = o.ended && (P.flags & AMENV_FLAG_AUTO_RESET);
   if (L.lead) {
     fl[row][0] = (o.ended && active ? 1u : 0u) | (resets ? 2u : 0u);
@@ -494,7 +550,7 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
     TeamResetT<X> R;
     const int hl = row * 4 + L.cc;                          // the helper's lane for this row and component
     if (have[row]) R = TeamResetT<X>{rst[0][hl], rst[1][hl], rst[2][hl], X(0), X(0), X(0)};
-    else R = team_reset_draw<X>(C, L.c, L.cc, E.episode, i);   // not announced by the helper's test (never observed): same values, computed here
+    else R = team_reset_draw<X>(team_late_cold<X>(), L.c, L.cc, E.episode, i);   // not announced by the helper's test (never observed): same values, computed here
     team_apply_reset(L, team_reset_obs(P, L, R), E, o);
   }
   AMENV_STAMP(5);          // barrier + reset values
@@ -515,11 +571,11 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vC)), r_obs, int(voC), 0, 0);
   if constexpr (sizeof(X) == 4) {   // lead lane of a real env; every other lane's offset is out of range
     const uint32_t nb = uint32_t(n_envs);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.reward), team_rsrc(reward_out, nb * 4u), int(voR), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b8(uint8_t(o.ended ? 1 : 0), team_rsrc(done, nb), int(voD), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(int(o.bits), team_rsrc(info, nb * 4u), int(voR), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.reward), team_rsrc(A.reward_out, nb * 4u), int(voR), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b8(uint8_t(o.ended ? 1 : 0), team_rsrc(A.done, nb), int(voD), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(int(o.bits), team_rsrc(A.info, nb * 4u), int(voR), 0, 0);
   } else {
-    if (active && L.lead) { reward_out[uint32_t(i)] = o.reward; done[uint32_t(i)] = o.ended ? 1 : 0; info[uint32_t(i)] = o.bits; }
+    if (active && L.lead) { A.reward_out[uint32_t(i)] = o.reward; A.done[uint32_t(i)] = o.ended ? 1 : 0; A.info[uint32_t(i)] = o.bits; }
   }
   if (any_end) {           // wave-uniform; rows that did not end store nowhere
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tA)), r_term, int(o.ended ? voA : kOob), 0, 0);
@@ -531,9 +587,14 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(7);          // stores acknowledged
   if (L.lane == 0 && blockIdx.x * MW + wave < kStampWaves)   // the integrating waves of the first workgroups
-    for (int kk = 0; kk < kStampSlots; kk++) tl.stats[kStampBase + (blockIdx.x * MW + wave) * kStampSlots + kk] = stamps_[kk];
+    for (int kk = 0; kk < kStampSlots; kk++) A.tl.stats[kStampBase + (blockIdx.x * MW + wave) * kStampSlots + kk] = stamps_[kk];
 #endif
 }
+
+// team_late_args reads the argument segment by TeamStepFirstArgs / TeamStepLateArgs: the parameter list above and the two structs are one thing
+static_assert(std::is_same<decltype(&step_kernel_team<float, 6, 4>), TeamStepKernelFn<float>>::value && std::is_same<decltype(&step_kernel_team<float, 6, 1>), TeamStepKernelFn<float>>::value &&
+                  std::is_same<decltype(&step_kernel_team<double, 6, 4>), TeamStepKernelFn<double>>::value && std::is_same<decltype(&step_kernel_team<double, 6, 1>), TeamStepKernelFn<double>>::value,
+              "step_kernel_team's parameters and TeamStepFirstArgs / TeamStepLateArgs have come apart");
 
 // n_steps control steps per launch with open-loop actions [T][N][7]; per-step outputs [T][N]... (any of them may be null).  State and
 // constants stay in registers across steps: no launch boundary, no prologue, no state traffic between steps.

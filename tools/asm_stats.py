@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of the gfx950 kernels: hipcc -S the library and count per kernel.
-Usage: python tools/asm_stats.py [filter-substring]"""
+Usage: python tools/asm_stats.py [filter-substring] [--asm FILE]   (--asm: count an assembly file made before instead of compiling)"""
 import collections
 import os
 import re
@@ -8,10 +8,17 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rl-aerial-manipulator_amd", "csrc")
+sys.path.insert(0, ROOT)
+import rl_aerial_manipulator_amd.build as B
+
 out = "/tmp/amenv.s"
-subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc", "-S",
-                       "--cuda-device-only", "-o", out, "amenv_capi.hip"], cwd=CSRC)
+if "--asm" in sys.argv:
+    k = sys.argv.index("--asm")
+    out = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
+else:   # the library's own flags (build.FLAGS), assembly instead of a shared object
+    subprocess.check_call([B.hipcc()] + [f for f in B.FLAGS if f not in ("-shared", "-fPIC", "-Wall")] +
+                          ["-S", "--cuda-device-only", "-Wno-unused-command-line-argument", "-o", out, "amenv_capi.hip"], cwd=B.CSRC)
 filt = sys.argv[1] if len(sys.argv) > 1 else "step_kernelIf"
 lines = open(out).read().split("\n")
 starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if l.startswith("_ZN9amenv_dev") and ":" in l]

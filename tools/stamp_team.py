@@ -38,7 +38,7 @@ R = np.stack(recs, 0)                                   # [launch, wave (first 6
 ended = R[:, :, 3] != 0
 t = R - R[:, :, 0:1]
 print(f"{int(ended.sum())} wave-launches with an episode end, {int((~ended).sum())} without (64 of {a.envs // 4} waves sampled)")
-for k, n_ in ((1, "loads issued"), (2, "loads landed"), (4, "advance done (RK4, task, episode end)"), (5, "barrier passed, reset values taken"), (6, "stores issued"), (7, "drained")):
+for k, n_ in ((1, "loads issued, store offsets formed"), (2, "loads landed"), (4, "advance done (RK4, task, episode end)"), (5, "barrier passed, reset values taken"), (6, "stores issued"), (7, "drained")):
     print(f"   {n_:40s} {np.median(t[:, :, k][~ended]):8.0f} {np.median(t[:, :, k][ended]):8.0f}")
 # The sampled waves are the four integrating waves of the first 16 workgroups (wave w of workgroup b at index 4 b + w).  Two of them on
 # one SIMD would share its issue slots and show up as a doubled compute span (loads landed -> advance done) in a fixed wave position.
