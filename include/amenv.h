@@ -408,6 +408,39 @@ int amenv_set_randomization(amenv* env, const amenv_randomization* r);
 /* out [N, 2 + n_rotors] f32 (device): km, kI, s_0 .. s_{n_rotors-1} of every env's current episode; all 1 when off. */
 int amenv_dynamics_factors(amenv* env, float* out, void* stream);
 
+/* ---- first-order rotor lag ---------------------------------------------------------------------------------
+ * Opt-in, per handle.  Per env and rotor there is one more state number w_r >= 0, the square root of the thrust the rotor delivers
+ * (thrust = k_f speed^2: w_r is the rotor speed up to the constant sqrt(k_f)).  Once per control step, in place of "use the clamped thrust":
+ *   t_c  = clamp(alloc[r] . u, t_min[r], t_max[r])      exactly as without the lag
+ *   c    = sqrt(t_c);   a = c > w_r ? a_up : a_down;   w_r' = fma(a, c - w_r, w_r);   the rotor delivers t_r = w_r' * w_r'
+ * then t_r *= s_r if randomisation is on, and the mix / RK4 as without.  t_r is held over the whole control step (every RK4 stage and
+ * sub-step); w_r' is the new state.  a_up = -expm1(-dt / tau_up), a_down = -expm1(-dt / tau_down), formed in fp64 from task.dt (the
+ * control period) and rounded once to the handle's dtype.  fp32 handles take the square root with v_sqrt_f32 (1 ulp).
+ * Episode start: w0_r = sqrt(clamp(alloc[r] . (mass g, 0, 0, 0), t_min[r], t_max[r])) with the NOMINAL mass, fp64 rounded once: the rotors
+ * spin at the nominal hover command.  An env gets w <- w0 when its episode starts (auto-reset inside a step or rollout, amenv_reset for the
+ * masked envs); with auto-reset off an env that ended keeps its rotor state like the rest of its state.  Turning the lag on where it was
+ * off sets every env's rotor state to w0; new time constants on a handle where it is on keep the states and apply from the next launch.
+ * The rotor state is not observed and is no part of amenv_get_state / amenv_set_state, whose layout does not change; it draws nothing, so
+ * sharding by global env id is unaffected.  Reward, task, reset draws and Monitor totals are unchanged.
+ * Served: what amenv_set_randomization serves, and composable with it (rigid vehicles with 4 or 6 rotors, fp32 and fp64, lane and
+ * helper-wave step kernels, amenv_rollout, amenv_rollout_policy[_norm] in the one-lane-per-env form).  Refused with AMENV_ERR_INVALID before
+ * anything is launched or changed: arm vehicles, other rotor counts, a handle whose step kernel is the lane-quad one, any t_min[r] < 0, a
+ * bad struct_size, a time constant that is not finite with 0 < tau <= 10.
+ * amenv_set_rotor_lag is a configuration call: it is the only one of the three that may allocate (the side buffer of rotor states, on the
+ * first enable) and it may synchronise the device; do not call it inside a stream capture.  amenv_get / set_rotor_state only enqueue, as
+ * step, rollout and reset do with the lag on. */
+typedef struct amenv_rotor_lag {
+  uint32_t struct_size;   /* = sizeof(amenv_rotor_lag): guard */
+  uint32_t reserved;
+  double tau_up, tau_down;  /* seconds; model.sdf timeConstantUp / timeConstantDown: 0.015 */
+} amenv_rotor_lag;
+/* lag NULL = off: the handle launches exactly the kernels it launched before. */
+int amenv_set_rotor_lag(amenv* env, const amenv_rotor_lag* lag);
+/* [N, n_rotors] of the handle's dtype, row-major (device): w_r of every env.  Refused while the lag is off. */
+int amenv_get_rotor_state(amenv* env, void* out, void* stream);
+/* the inverse: parity injection, checkpoint / restore.  Refused while the lag is off. */
+int amenv_set_rotor_state(amenv* env, const void* in, void* stream);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

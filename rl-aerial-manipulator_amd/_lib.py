@@ -71,6 +71,10 @@ class Randomization(C.Structure):
                 ("thrust_scale", C.c_float * 2)]
 
 
+class RotorLagC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("tau_up", C.c_double), ("tau_down", C.c_double)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -89,6 +93,9 @@ SYMBOLS = {
     "amenv_set_seed": (C.c_int, [_P, C.c_uint64]),
     "amenv_set_randomization": (C.c_int, [_P, C.POINTER(Randomization)]),
     "amenv_dynamics_factors": (C.c_int, [_P, _P, _P]),
+    "amenv_set_rotor_lag": (C.c_int, [_P, C.POINTER(RotorLagC)]),
+    "amenv_get_rotor_state": (C.c_int, [_P, _P, _P]),
+    "amenv_set_rotor_state": (C.c_int, [_P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

@@ -64,6 +64,9 @@ struct amenv {
   uint64_t steps = 0;
   bool dr = false;                 // amenv_set_randomization: per-episode dynamics randomisation on
   DrRanges dr_r = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};   // its ranges (lo, hi - lo); {1, 1} = the nominal vehicle
+  bool lag = false;                // amenv_set_rotor_lag: first-order rotor lag on
+  double lag_a[2] = {1.0, 1.0};    // its coefficients -expm1(-dt / tau_up), -expm1(-dt / tau_down), fp64
+  void* lag_w = nullptr;           // [n_tiles][n_rotors][64] rotor states | [n_rotors] w0, of the handle's dtype; allocated when the lag is first enabled
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
   std::string kname;
@@ -317,6 +320,23 @@ template <bool DR> DrArg<DR> make_dr(const amenv& e);
 template <> DrArg<false> make_dr<false>(const amenv&) { return DrArg<false>{0}; }
 template <> DrArg<true> make_dr<true>(const amenv& e) { return DrArg<true>{e.dr_r}; }
 
+// episode-start rotor state: the rotors spin at the NOMINAL hover command, sqrt(clamp(alloc[r] . (m g, 0, 0, 0))), fp64
+double lag_w0(const amenv_vehicle& v, int r) {
+  const double t = v.alloc[r * 4] * (v.mass * v.g);
+  return std::sqrt(std::fmax(std::fmin(t, v.t_max[r]), v.t_min[r]));
+}
+template <typename T, int NROT> LagArg<T, NROT, true> make_lag(const amenv& e) {
+  LagArg<T, NROT, true> L;
+  L.w = static_cast<T*>(e.lag_w); L.n_pad = uint32_t(e.n_tiles) * 64u;
+  L.a_up = T(e.lag_a[0]); L.a_down = T(e.lag_a[1]);
+  return L;
+}
+// the kernels' last argument: the randomisation ranges, and behind them the lag block in the LAG instantiations
+template <typename T, int NROT, bool DR, bool LAG> DynArg<T, NROT, DR, LAG> make_dyn(const amenv& e) {
+  if constexpr (LAG) return DynArg<T, NROT, true, true>{make_dr<true>(e), make_lag<T, NROT>(e)};
+  else return DynArg<T, NROT, DR, false>{make_dr<DR>(e)};
+}
+
 bool is_v1(const amenv_config* c) { return c->task.variant == AMENV_TASK_V1_SCALED17 || c->task.variant == AMENV_TASK_V1_RAW17; }
 int obs_dim_of(const amenv_config* c) { return is_v1(c) ? 17 : 20 + 2 * c->vehicle.n_joints + (c->vehicle.n_joints ? 3 : 0); }
 int act_dim_of(const amenv_config* c) { return kActDim + c->vehicle.n_joints; }
@@ -446,6 +466,7 @@ std::string kernel_name(const amenv& e) {
   }
   std::string name = buf;
   if (e.dr) name += " +dr";
+  if (e.lag) name += " +lag";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -460,7 +481,7 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 
 // amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
 // runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR>
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG>
 hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const ColdParams C = make_cold(e);
@@ -483,15 +504,15 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dr<DR>(e));
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG>(e));
 }
 
 // amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
 // if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false>
+template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR>(e, io, T_steps, s);
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
@@ -534,24 +555,24 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
         const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
-                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dr<DR>(e));
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
+                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dr<DR>(e));
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG>(e));
     }
   }
   return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
-template <typename T, int NROT, bool DR = false>
+template <typename T, int NROT, bool DR = false, bool LAG = false>
 hipError_t dispatch_k(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR>(e, io, T_steps, s, timed);
-  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR>(e, io, T_steps, s, timed);
+  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
+  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG>(e, io, T_steps, s, timed);
+  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG>(e, io, T_steps, s, timed);
 }
 
 template <typename T>
@@ -560,6 +581,11 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
   if (e.cfg.vehicle.n_joints == 3) {
     if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
+  }
+  if (e.lag) {  // amenv_set_rotor_lag admits what amenv_set_randomization admits; the LAG kernels are the DR ones (unit ranges when that is off)
+    if (nr == 4) return dispatch_k<T, 4, true, true>(e, io, T_steps, s, timed);
+    if (nr == 6) return dispatch_k<T, 6, true, true>(e, io, T_steps, s, timed);
+    return hipErrorInvalidValue;
   }
   if (e.dr) {   // amenv_set_randomization admits rigid vehicles with 4 or 6 rotors on the lane and helper-wave families only
     if (nr == 4) return dispatch_k<T, 4, true>(e, io, T_steps, s, timed);
@@ -608,32 +634,33 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifndef AMENV_RIGID_WG64_MAX
 #define AMENV_RIGID_WG64_MAX 24576
 #endif
-template <int NROT, int KW, int VAR, bool NORM, bool DR>
+template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG>
 hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
   const ColdParams C = make_cold(e);
-  const DrArg<DR> R = make_dr<DR>(e);
+  const DynArg<float, NROT, DR, LAG> R = make_dyn<float, NROT, DR, LAG>(e);
   const int n = e.cfg.num_envs;
   if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   return hipGetLastError();
 }
-template <bool NORM, bool DR>
+template <bool NORM, bool DR, bool LAG = false>
 hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const bool four = e.cfg.vehicle.n_rotors == 4;
   if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
-    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG>(e, T, io, N, s);
   if (e.cfg.task.num_waypoints == 1)
-    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR>(e, T, io, N, s);
-  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR>(e, T, io, N, s)
-              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG>(e, T, io, N, s);
+  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG>(e, T, io, N, s)
+              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG>(e, T, io, N, s);
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  if (e.lag) return launch_rigid_policy_dr<NORM, true, true>(e, T, io, N, s);   // (unit ranges when randomisation is off)
   return e.dr ? launch_rigid_policy_dr<NORM, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, false>(e, T, io, N, s);
 }
 
@@ -647,6 +674,42 @@ __global__ void dr_factors_kernel(int n, uint32_t tile_bytes, const void* __rest
   dr_draw<NROT>(C, R, C.gid0 + i, episode, f);
 #pragma unroll
   for (int k = 0; k < 2 + NROT; k++) out[size_t(i) * (2 + NROT) + k] = f[k];
+}
+
+// amenv_set_rotor_lag / amenv_reset: w <- w0 for the masked envs (mask null = all; padding lanes always, as reset_kernel does)
+template <typename T, int NROT>
+__global__ void lag_reset_kernel(int n, const LagArg<T, NROT, true> L, const uint8_t* __restrict__ mask) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= int(L.n_pad)) return;
+  if (i < n && mask && !mask[i]) return;
+#pragma unroll
+  for (int r = 0; r < NROT; r++) L.w[lag_slot<NROT>(i) + r * 64] = L.w[size_t(NROT) * L.n_pad + r];
+}
+// amenv_get_rotor_state (to_api) / amenv_set_rotor_state: [N][NROT] row-major <-> the side buffer's [tile][NROT][64]
+template <typename T>
+__global__ void lag_transpose_kernel(int n, int nr, T* __restrict__ w, T* __restrict__ api, int to_api) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  T* p = w + size_t(i >> 6) * (nr * 64) + size_t(i & 63);
+  for (int r = 0; r < nr; r++) {
+    if (to_api) api[size_t(i) * nr + r] = p[r * 64];
+    else p[r * 64] = api[size_t(i) * nr + r];
+  }
+}
+template <typename T>
+hipError_t launch_lag_reset(const amenv& e, const uint8_t* mask, hipStream_t s) {
+  const int n = e.cfg.num_envs;
+  const dim3 grid(e.n_tiles / 4), block(256);
+  if (e.cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((lag_reset_kernel<T, 4>), grid, block, 0, s, n, make_lag<T, 4>(e), mask);
+  else hipLaunchKernelGGL((lag_reset_kernel<T, 6>), grid, block, 0, s, n, make_lag<T, 6>(e), mask);
+  return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_lag_transpose(const amenv& e, void* api, int to_api, hipStream_t s) {
+  const int n = e.cfg.num_envs;
+  hipLaunchKernelGGL(lag_transpose_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, int(e.cfg.vehicle.n_rotors), static_cast<T*>(e.lag_w),
+                     static_cast<T*>(api), to_api);
+  return hipGetLastError();
 }
 
 // amenv_rollout_policy[_norm] after the entry checks: pack the parameters, fill the kernel's I/O block
@@ -898,6 +961,7 @@ int amenv_destroy(amenv* e) {
     if (e->stats) (void)hipFree(e->stats);
     if (e->team_consts) (void)hipFree(e->team_consts);
     if (e->pol_pack) (void)hipFree(e->pol_pack);
+    if (e->lag_w) (void)hipFree(e->lag_w);
     if (e->io_act) (void)hipFree(e->io_act);
     if (e->io_obs) (void)hipFree(e->io_obs);
     if (e->io_term) (void)hipFree(e->io_term);
@@ -975,12 +1039,77 @@ int amenv_dynamics_factors(amenv* e, float* out, void* stream) {
   return AMENV_OK;
 }
 
+int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!lag) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused)
+    e->lag = false;
+    e->kname = kernel_name(*e);
+    return AMENV_OK;
+  }
+  const amenv_vehicle& v = e->cfg.vehicle;
+  if (lag->struct_size != sizeof(amenv_rotor_lag)) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: struct_size must be sizeof(amenv_rotor_lag)");
+  if (v.n_joints > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: built for rigid vehicles (the arm kernels are not built with it)");
+  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: built for rigid vehicles with 4 or 6 rotors");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  for (int r = 0; r < v.n_rotors; r++)
+    if (!(v.t_min[r] >= 0.0)) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: every t_min must be >= 0 (the rotor state is the square root of a thrust)");
+  const double tau[2] = {lag->tau_up, lag->tau_down};
+  for (int q = 0; q < 2; q++)
+    if (!std::isfinite(tau[q]) || !(tau[q] > 0.0) || !(tau[q] <= 10.0))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_rotor_lag: ") + (q ? "tau_down" : "tau_up") + " must be finite with 0 < tau <= 10 (seconds)");
+  DeviceGuard g(e->device);
+  if (!e->lag_w) {   // first enable: the one allocation, and w0 (a function of the config alone) behind the states
+    const bool f64 = e->cfg.dtype == AMENV_F64;
+    const size_t ts = f64 ? 8 : 4, states = size_t(v.n_rotors) * size_t(e->n_tiles) * 64;
+    double w0d[AMENV_MAX_ROTORS]; float w0f[AMENV_MAX_ROTORS];
+    for (int r = 0; r < v.n_rotors; r++) { w0d[r] = lag_w0(v, r); w0f[r] = float(w0d[r]); }
+    void* buf = nullptr;
+    hipError_t st = hipMalloc(&buf, (states + size_t(v.n_rotors)) * ts);
+    if (st != hipSuccess) return fail(e, AMENV_ERR_ALLOC, std::string("amenv_set_rotor_lag: hipMalloc: ") + hipGetErrorString(st));
+    st = hipMemcpy(static_cast<char*>(buf) + states * ts, f64 ? static_cast<const void*>(w0d) : static_cast<const void*>(w0f), size_t(v.n_rotors) * ts, hipMemcpyHostToDevice);
+    if (st != hipSuccess) { (void)hipFree(buf); return fail(e, AMENV_ERR_HIP, std::string("amenv_set_rotor_lag: hipMemcpy: ") + hipGetErrorString(st)); }
+    e->lag_w = buf;
+  }
+  const bool was_on = e->lag;
+  for (int q = 0; q < 2; q++) e->lag_a[q] = -std::expm1(-e->cfg.task.dt / tau[q]);
+  e->lag = true;
+  e->kname = kernel_name(*e);
+  if (!was_on) {     // off -> on: every rotor at the nominal hover command; on -> on keeps the states (curricula)
+    AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, nullptr, nullptr) : launch_lag_reset<float>(*e, nullptr, nullptr));
+    AMENV_HIP(e, hipDeviceSynchronize());
+  }
+  return AMENV_OK;
+}
+
+int amenv_get_rotor_state(amenv* e, void* out, void* stream) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!out) return fail(e, AMENV_ERR_INVALID, "amenv_get_rotor_state: NULL argument");
+  if (!e->lag) return fail(e, AMENV_ERR_INVALID, "amenv_get_rotor_state: the rotor lag is off (amenv_set_rotor_lag)");
+  DeviceGuard g(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_transpose<double>(*e, out, 1, s) : launch_lag_transpose<float>(*e, out, 1, s));
+  return AMENV_OK;
+}
+
+int amenv_set_rotor_state(amenv* e, const void* in, void* stream) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!in) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_state: NULL argument");
+  if (!e->lag) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_state: the rotor lag is off (amenv_set_rotor_lag)");
+  DeviceGuard g(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_transpose<double>(*e, const_cast<void*>(in), 0, s) : launch_lag_transpose<float>(*e, const_cast<void*>(in), 0, s));
+  return AMENV_OK;
+}
+
 int amenv_reset(amenv* e, const uint8_t* mask, float* obs_out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
   float* o = (e->io_obs && obs_out) ? e->io_obs : obs_out;
   AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_reset<double>(*e, mask, o, 0, s) : launch_reset<float>(*e, mask, o, 0, s));
+  if (e->lag) AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, mask, s) : launch_lag_reset<float>(*e, mask, s));
   if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
   return AMENV_OK;
 }
@@ -1061,7 +1190,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  const bool quad = !e->dr && !e->lag && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");

@@ -275,11 +275,11 @@ __device__ __forceinline__ void observe_reset(const Env<T, KW>& e, bool ee_task,
   }
 }
 
-template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false>
+template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false, typename LG = LagLane<T, NROT, false>>
 __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const ColdParams& C, const ArmArg<T, NJ>& AA, Env<T, KW>& e, const float* act, int i,
                                               bool active, T& reward, float* o, const StepIO& io, char* tile, int lane,
                                               bool have_episode, bool& was_reset, int& ep_len_out, float& ep_ret_out, const X& x = X{},
-                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}) {
+                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr) {
   constexpr int OD = ObsDim<VAR, NJ>::value;
   const int K = KW == 1 ? 1 : P.K;
   if constexpr (NJ > 0) {
@@ -287,7 +287,7 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
     else if constexpr (ROLE == ARM_ROLE_STAGED) dynamics_arm_staged<T, NROT, KW>(P, AA.p, e, act, x);                                   // stage-wave kernel: z,x,x arm only
     else if (AA.p.generic_axes) dynamics_arm<T, NROT, KW, AxesAny>(P, AA.p, e, act);   // wave-uniform: one of the two bodies runs
     else dynamics_arm<T, NROT, KW, AxesZXX>(P, AA.p, e, act);
-  } else { dynamics<T, NROT, KW, DR>(P, e, act[0], act[1], act[2], act[3], df); }
+  } else { dynamics<T, NROT, KW, DR, LG>(P, e, act[0], act[1], act[2], act[3], df, lg); }
   constexpr bool EE = NJ > 0;   // arm: forward kinematics of the post-step state feed the task point and the observation
   if constexpr (EE) update_tool_offset<T, KW, ROLE == ARM_ROLE_MAIN || ROLE == ARM_ROLE_HELPER || ROLE == ARM_ROLE_STAGED>(AA.p, e);
   const bool ee_task = EE && P.ee_task != 0;
@@ -387,12 +387,14 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 #define AMENV_STEP_WAVES_ATTR
 #endif
 // DR: per-episode dynamics randomisation, rigid vehicles only; the factors are drawn once per launch from the loaded episode.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false>
+// LAG: first-order rotor lag, built together with DR only; the rotor states are loaded from and stored to the handle's side buffer.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA, const DrArg<DR> R) {
+                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
+  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -409,6 +411,8 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   const int K = KW == 1 ? 1 : P.K;
   Env<T, KW> e;
   load_env<T, KW, NJ>(K, tile, lane, e);
+  LagLane<T, NROT, LAG> lg;
+  if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);   // (padding lanes own valid slots of the side buffer as of the blob)
   float act[AD];
   if constexpr (NJ == 0) {
     const float4 a = io.actions[min(i, hd.n - 1)];  // padding lanes re-read the last env's action: no exec branch in the prologue
@@ -423,14 +427,15 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   AMENV_STAMP(2);          // loads landed
   T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
   DynFac<T, NROT, DR> df;
-  if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
-  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret,
-                                                                 NoXchg{}, df);
+  if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret,
+                                                                      NoXchg{}, df, &lg);
   const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
   AMENV_STAMP(3);          // dynamics + task + obs computed
   accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
   store_env_step<T, KW, NJ>(tile, lane, e, K);
   if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
+  if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
   if (active) {
     reinterpret_cast<T*>(io.reward)[i] = reward;
     io.done[i] = is_done ? 1 : 0;
@@ -480,11 +485,13 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 //      wave 0 (main) integrates, runs the task step, publishes a flag word per lane (and info bits / length / return of the lanes that
 //             ended), passes the barrier, takes the reset position of reset lanes from LDS and stores the state of every lane.
 // DR: the waves that integrate (main, observation) draw the factors of the loaded episode.
-template <typename T, int NROT, int KW, int VAR, bool DR = false>
+// LAG: both of them load the same rotor states and filter them; the main wave alone stores, after the barrier.
+template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                      const DrArg<DR> R) {
+                                                      const DynArg<T, NROT, DR, LAG> DA) {
+  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, 0>::value;
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
@@ -573,13 +580,15 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     const float4 a = io.actions[min(i, hd.n - 1)];
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     DynFac<T, NROT, DR> df;
-    if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
+    if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    LagLane<T, NROT, LAG> lg;
+    if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     if (role == 2) {
 #ifdef AMENV_STAMPS
       AMENV_STAMP_DRAIN();
 #endif
       AMENV_STAMP(1);
-      dynamics<T, NROT, KW, DR>(P, e, act[0], act[1], act[2], act[3], df);
+      dynamics<T, NROT, KW, DR, LagLane<T, NROT, LAG>>(P, e, act[0], act[1], act[2], act[3], df, &lg);
       AMENV_STAMP(2);
       float ho[kObsDimMax];
       observe<T, KW>(1, e, ho);
@@ -610,8 +619,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
 #endif
     AMENV_STAMP(1);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_FLAGS, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len,
-                                                                               ep_ret, NoXchg{}, df);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_FLAGS, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
+                                                                                    ep_len, ep_ret, NoXchg{}, df, &lg);
     AMENV_STAMP(2);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     flag[lane] = (is_done ? 1u : 0u) | (was_reset ? 2u : 0u);
@@ -624,8 +633,10 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       e.vx = e.vy = e.vz = T(0); e.qw = T(1); e.qx = e.qy = e.qz = T(0); e.wx = e.wy = e.wz = T(0);
       e.last_distance = T(-1); e.ep_return = T(0);
       e.step = 0; e.counter = 0; e.flags = 0; e.episode += 1;
+      if constexpr (LAG) lag_restart<T, NROT>(DA.L, lg);
     }
     store_env_step<T, KW>(tile, lane, e);
+    if constexpr (LAG) lag_store<T, NROT>(DA.L, i, lg);   // (the observation wave loaded its copy before the barrier)
     if (active) {
       reinterpret_cast<T*>(io.reward)[i] = reward;
       io.done[i] = is_done ? 1 : 0;
@@ -655,14 +666,17 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     const LdsXchg x{lds, lane, words};
     DynFac<T, NROT, DR> df;
-    if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
+    if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    LagLane<T, NROT, LAG> lg;
+    if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len,
-                                                                               ep_ret, x, df);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
+                                                                                    ep_len, ep_ret, x, df, &lg);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int(blockIdx.x), bits, is_done, ep_len, ep_ret);
     store_env_step<T, KW>(tile, lane, e);
     if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
+    if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
     if (active) {
       reinterpret_cast<T*>(io.reward)[i] = reward;
       io.done[i] = is_done ? 1 : 0;
@@ -858,12 +872,14 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
 // n_steps control steps per launch with open-loop actions [T][N][4]; per-step outputs [T][N]...
 // State stays in registers across steps: HBM traffic per env-step drops to action + outputs.
 // DR: factors drawn at entry and again for a lane after its auto-reset.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false>
+// LAG: the rotor states stay in registers over the steps, restart at w0 after an auto-reset and are stored once at the end.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false>
 __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, int n_steps, const StepTail tl, const HotParams<T, NROT> P,
-                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DrArg<DR> R) {
+                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
+  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, nullptr, nullptr, nullptr, tl.stats};
@@ -880,7 +896,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   Env<T, KW> e;
   load_env<T, KW, NJ>(K, tile, lane, e);
   DynFac<T, NROT, DR> df;
-  if constexpr (DR) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode);
+  if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+  LagLane<T, NROT, LAG> lg;
+  if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
   bool any_reset = false;
   StepIO io_t = io; io_t.terminal_obs = nullptr; io_t.ep_return = nullptr; io_t.ep_len = nullptr;
   for (int t = 0; t < n_steps; t++) {
@@ -894,9 +912,10 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
       }
     }
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset, ep_len, ep_ret,
-                                                                   NoXchg{}, df);
-    if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
+    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset, ep_len,
+                                                                        ep_ret, NoXchg{}, df, &lg);
+    if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
+    if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
@@ -914,6 +933,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   }
   store_env_step<T, KW, NJ>(tile, lane, e, K);
   if (any_reset) store_env_episode<T, KW>(K, tile, lane, e);
+  if constexpr (LAG) lag_store<T, NROT>(DA.L, i, lg);
 }
 
 // WaypointQuadEnv.reset for masked envs (mask null = all) + observation of every env.

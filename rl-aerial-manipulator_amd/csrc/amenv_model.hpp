@@ -172,10 +172,75 @@ template <typename T, int NROT> struct DynFac<T, NROT, true> {
   T inv_ki;         // 1 / kI
 };
 
+// ---- first-order rotor lag (include/amenv.h amenv_set_rotor_lag) -------------------------------------------------
+// One state number per env and rotor: w = sqrt(delivered thrust), rotor speed up to sqrt(k_f).  Once per control step the commanded
+// speed c = sqrt(clamped thrust) is approached by w' = w + a (c - w), a = a_up when the rotor speeds up, else a_down; the rotor delivers
+// w'^2 over the whole step.  The states live in a side buffer of the handle, tiled like the blob: [n_pad / 64][NROT][64] values of T (one
+// coalesced load and store per lane and rotor, and ONE address per lane: the rotors are constant offsets from it -- with [NROT][n_pad] rows
+// the closed-loop kernel kept NROT 64-bit addresses alive from its first load to its last store and spilled them), with the episode-start
+// values w0[NROT] behind them (read on the reset path only); the buffer and the two coefficients
+// travel in a kernel argument of their own, in the LAG instantiations only (HotParams is at its SGPR budget: the fp64 helper-wave kernel
+// has no scalar register left for w0[]).  LAG is built only together with DR (unit ranges when randomisation is off).
+template <typename T, int NROT, bool LAG> struct LagArg { int unused; };
+template <typename T, int NROT> struct LagArg<T, NROT, true> {
+  T* w;              // [n_pad / 64][NROT][64] rotor states | [NROT] w0: rotors at the nominal hover command
+  uint32_t n_pad;    // the handle's padded env count (whole tiles)
+  T a_up, a_down;    // -expm1(-dt / tau), formed on the host in fp64
+};
+// The one kernel argument that carries both switches: DrArg's bytes unless LAG (the kernels without lag keep their argument segment).
+template <typename T, int NROT, bool DR, bool LAG> struct DynArg { DrArg<DR> R; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; };
+// env i's rotor r sits at lag_slot(i) + 64 r
+template <int NROT> __device__ __forceinline__ size_t lag_slot(int i) { return size_t(i >> 6) * (NROT * 64) + size_t(i & 63); }
+// What dynamics() filters through: get(r) / set(r, w') and the two coefficients.  LagLane keeps the rotor states in the lane's registers
+// (empty when off); LagLds keeps them in an LDS column of the lane's own, [2 NROT + 2][NE] floats, for the closed-loop kernel whose NORM
+// forms have no VGPR to spare: one rotor's state is in a register at a time, and the randomisation's per-lane factors (s_r, 1 / (km m),
+// 1 / kI) sit in the same column instead of in DynFac's registers (holds_s), which is what makes the room.
+template <typename T, int NROT, bool LAG> struct LagLane { static constexpr bool on = false, holds_s = false; };
+template <typename T, int NROT> struct LagLane<T, NROT, true> {
+  static constexpr bool on = true, holds_s = false;
+  T w[NROT]; T a_up, a_down;
+  __device__ __forceinline__ T get(int r) const { return w[r]; }
+  __device__ __forceinline__ void set(int r, T v) { w[r] = v; }
+};
+template <int NROT, int NE, bool LAG> struct LagLds { static constexpr bool on = false, holds_s = false; };
+template <int NROT, int NE> struct LagLds<NROT, NE, true> {
+  static constexpr bool on = true, holds_s = true;
+  float* col; float a_up, a_down;   // col: &wl[env within the workgroup]; rows 0..NROT-1 w_r, rows NROT.. s_r, then 1 / (km m), 1 / kI
+  __device__ __forceinline__ float get(int r) const { return col[r * NE]; }
+  __device__ __forceinline__ void set(int r, float v) { col[r * NE] = v; }
+  __device__ __forceinline__ float s(int r) const { return col[(NROT + r) * NE]; }
+  __device__ __forceinline__ float inv_mass() const { return col[2 * NROT * NE]; }
+  __device__ __forceinline__ float inv_ki() const { return col[(2 * NROT + 1) * NE]; }
+  __device__ __forceinline__ void put(const DynFac<float, NROT, true>& d) {
+#pragma unroll
+    for (int r = 0; r < NROT; r++) col[(NROT + r) * NE] = d.s[r];
+    col[2 * NROT * NE] = d.inv_mass; col[(2 * NROT + 1) * NE] = d.inv_ki;
+  }
+};
+template <typename T, int NROT>
+__device__ __forceinline__ void lag_load(const LagArg<T, NROT, true>& L, int i, LagLane<T, NROT, true>& g) {
+  g.a_up = L.a_up; g.a_down = L.a_down;
+  const T* p = L.w + lag_slot<NROT>(i);
+#pragma unroll
+  for (int r = 0; r < NROT; r++) g.w[r] = p[r * 64];
+}
+template <typename T, int NROT>
+__device__ __forceinline__ void lag_store(const LagArg<T, NROT, true>& L, int i, const LagLane<T, NROT, true>& g) {
+  T* p = L.w + lag_slot<NROT>(i);
+#pragma unroll
+  for (int r = 0; r < NROT; r++) p[r * 64] = g.w[r];
+}
+template <typename T, int NROT>
+__device__ __forceinline__ void lag_restart(const LagArg<T, NROT, true>& L, LagLane<T, NROT, true>& g) {   // a new episode starts
+#pragma unroll
+  for (int r = 0; r < NROT; r++) g.w[r] = L.w[size_t(NROT) * L.n_pad + r];
+}
+
 // Quadcopter.update (quadcopter.py:105-114) with RK4 in place of odeint.
-template <typename T, int NROT, int KW, bool DR = false>
+template <typename T, int NROT, int KW, bool DR = false, typename LG = LagLane<T, NROT, false>>
 __device__ __forceinline__ void dynamics(const HotParams<T, NROT>& P, Env<T, KW>& e, float a0, float a1, float a2, float a3,
-                                         const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}) {
+                                         const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr) {
   // action scaling in fp32, left to right (rl_env_scaledObs.py:125-126)
   const float Ff = (a0 * P.mass_f) * P.g_f;
   const T u0 = T(Ff), u1 = T(a1 * P.mscale_f), u2 = T(a2 * P.mscale_f), u3 = T(a3 * P.mscale_f);
@@ -186,11 +251,21 @@ __device__ __forceinline__ void dynamics(const HotParams<T, NROT>& P, Env<T, KW>
     if (NROT == AMENV_MAX_ROTORS && r >= P.n_rotors) break;  // generic instantiation: runtime rotor count
     T t = fma_(P.alloc[r][0], u0, fma_(P.alloc[r][1], u1, fma_(P.alloc[r][2], u2, P.alloc[r][3] * u3)));
     t = clamp_(t, P.tmin[r], P.tmax[r]);   // np.maximum(np.minimum(t, max), min), quadcopter.py:110
-    if constexpr (DR) t = t * df.s[r];     // the rotor delivers s_r of its (nominally saturated) command
+    if constexpr (LG::on) {                // the rotor's speed follows the command's with a first-order lag; it delivers w'^2
+      const T c = sqrt_(t);
+      const T w = lg->get(r);
+      const T wn = fma_(c > w ? lg->a_up : lg->a_down, c - w, w);
+      lg->set(r, wn);
+      t = wn * wn;
+    }
+    if constexpr (DR) {                    // the rotor delivers s_r of its (nominally saturated) command
+      if constexpr (LG::holds_s) t = t * lg->s(r); else t = t * df.s[r];
+    }
     F = F + t; Mx = fma_(P.mixm[0][r], t, Mx); My = fma_(P.mixm[1][r], t, My); Mz = fma_(P.mixm[2][r], t, Mz);
   }
   T Fm;
-  if constexpr (DR) { Fm = F * df.inv_mass; Mx = Mx * df.inv_ki; My = My * df.inv_ki; Mz = Mz * df.inv_ki; }
+  if constexpr (DR && LG::holds_s) { const T ik = lg->inv_ki(); Fm = F * lg->inv_mass(); Mx = Mx * ik; My = My * ik; Mz = Mz * ik; }
+  else if constexpr (DR) { Fm = F * df.inv_mass; Mx = Mx * df.inv_ki; My = My * df.inv_ki; Mz = Mz * df.inv_ki; }
   else Fm = F * P.inv_mass;
   const T h = P.h, hh = T(0.5) * h, h6 = h * T(1.0 / 6.0);
   int it = 0;

@@ -32,11 +32,15 @@ struct NormArg {
 };
 
 // DR: per-episode dynamics randomisation: factors drawn at entry and again for a lane after its auto-reset.
-template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false>
+// LAG: first-order rotor lag.  The NORM forms have no VGPR to spare, so the rotor states of this kernel live in LDS, and with
+// them the randomisation's factors ((2 NROT + 2) x NE floats, every lane its own column: no barrier): dynamics() filters them there one
+// rotor at a time (LagLds), and the states go back to the handle's side buffer once at the end.
+template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
                                                                                          const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
-                                                                                         const DrArg<DR> R) {
+                                                                                         const DynArg<float, NROT, DR, LAG> DA) {
+  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -46,6 +50,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   __shared__ __attribute__((aligned(16))) float meanb[NE * 4];
   __shared__ float valb[NE];
   __shared__ double md[NORM ? 2 * OD : 1];                                // entry statistics: mean | 1 / sqrt(var + eps)
+  __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors, [2 NROT + 2][NE]: each lane reads and writes its own column
   __bf16* h3 = h1;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
@@ -179,7 +184,12 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   };
   if (mine) {
     load_env<float, KW, 0>(K, tile, tl, e);
-    if constexpr (DR) df = dr_factors<float, NROT>(P, C, R.r, C.gid0 + i, e.episode);
+    if constexpr (DR && !LAG) df = dr_factors<float, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    if constexpr (LAG) {
+#pragma unroll
+      for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[lag_slot<NROT>(i) + r * 64];
+      LagLds<NROT, NE, true>{wl + el, 0.0f, 0.0f}.put(dr_factors<float, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode));
+    }
     const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
 #pragma unroll
     for (int c = 0; c < AD; c++) { const uint4 v = ac[c]; std_a[c] = __uint_as_float(v.x); ls_a[c] = __uint_as_float(v.y); }
@@ -235,9 +245,18 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
     sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
-    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
-                                                                           ep_ret, NoXchg{}, df);
-    if constexpr (DR) { if (was_reset) df = dr_factors<float, NROT>(P, C, R.r, gid, e.episode); }   // the new episode's vehicle
+    LagLds<NROT, NE, LAG> lg;
+    if constexpr (LAG) { lg.col = wl + el; lg.a_up = DA.L.a_up; lg.a_down = DA.L.a_down; }
+    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset,
+                                                                                ep_len, ep_ret, NoXchg{}, df, &lg);
+    if constexpr (DR && !LAG) { if (was_reset) df = dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode); }   // the new episode's vehicle
+    if constexpr (LAG) {
+      if (was_reset) {   // the new episode's rotors: w0 (behind the states in the side buffer), and the new episode's vehicle
+#pragma unroll
+        for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[size_t(NROT) * DA.L.n_pad + r];
+        lg.put(dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode));
+      }
+    }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);
@@ -261,6 +280,10 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   if (mine) {
     store_env_step<float, KW, 0>(tile, tl, e, K);
     if (any_reset) store_env_episode<float, KW>(K, tile, tl, e);
+    if constexpr (LAG) {
+#pragma unroll
+      for (int r = 0; r < NROT; r++) DA.L.w[lag_slot<NROT>(i) + r * 64] = wl[r * NE + el];
+    }
   }
   if constexpr (NORM) {
     if (N.update != 0) {   // one reduction per env wavefront (lanes without an active env hold zeros), one atomic per column and wavefront

@@ -32,7 +32,10 @@ class GpuWaypointEnv:
 
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
-                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None):
+                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None):
+        from .rotor_lag import RotorLag
+        if rotor_lag is not None and not isinstance(rotor_lag, RotorLag):   # before any device is touched
+            raise L.AmenvError(f"rotor_lag: expected a RotorLag or None, got {type(rotor_lag).__name__}")
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -86,6 +89,9 @@ class GpuWaypointEnv:
         self.randomization = None
         if randomization is not None:
             self.set_randomization(randomization)
+        self.rotor_lag = None
+        if rotor_lag is not None:
+            self.set_rotor_lag(rotor_lag)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -125,6 +131,32 @@ class GpuWaypointEnv:
         out = torch.empty(self.num_envs, 2 + self.n_rotors, dtype=torch.float32, device=self.device)
         self._check(self.lib.amenv_dynamics_factors(self._h, C.c_void_p(out.data_ptr()), self._stream()), "amenv_dynamics_factors")
         return out
+
+    def set_rotor_lag(self, lag):
+        """First-order rotor lag (a `RotorLag`, or None = rotors deliver their command at once; rigid vehicles with 4 or 6 rotors, not
+        with kernel="team").  Turning it on sets every env's rotor state to the nominal hover command; new time constants on an env where
+        it is on keep the states and apply from the next launch.  A configuration call: it may allocate and synchronise."""
+        from .rotor_lag import RotorLag
+        if lag is not None and not isinstance(lag, RotorLag):
+            raise L.AmenvError(f"set_rotor_lag: expected a RotorLag or None, got {type(lag).__name__}")
+        c = None if lag is None else lag.to_c()
+        self._check(self.lib.amenv_set_rotor_lag(self._h, None if c is None else C.byref(c)), "amenv_set_rotor_lag")
+        self.rotor_lag = lag
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
+    def rotor_state(self):
+        """[N, n_rotors] of the state dtype: every rotor's state w = sqrt(delivered thrust).  Needs the rotor lag on."""
+        out = torch.empty(self.num_envs, self.n_rotors, dtype=self.state_dtype, device=self.device)
+        self._check(self.lib.amenv_get_rotor_state(self._h, C.c_void_p(out.data_ptr()), self._stream()), "amenv_get_rotor_state")
+        return out
+
+    def set_rotor_state(self, w):
+        """The inverse of rotor_state(): parity injection, checkpoint / restore."""
+        t = torch.as_tensor(w).to(device=self.device, dtype=self.state_dtype).contiguous()
+        if tuple(t.shape) != (self.num_envs, self.n_rotors):
+            raise L.AmenvError(f"set_rotor_state: expected shape {(self.num_envs, self.n_rotors)}, got {tuple(t.shape)}")
+        self._check(self.lib.amenv_set_rotor_state(self._h, C.c_void_p(t.data_ptr()), self._stream()), "amenv_set_rotor_state")
+        torch.cuda.current_stream(self.device).synchronize()   # the staging tensor stays alive until the copy has run
 
     def reset(self, mask=None):
         """WaypointQuadEnv.reset (v2/rl_env_scaledObs.py:40-79) for all envs, or those with mask != 0."""
