@@ -44,6 +44,9 @@ def main():
                         help=f"per-episode dynamics randomisation: scale {what} by a factor drawn from [1 - F, 1 + F] (rigid vehicles; DESIGN 4i)")
     ap.add_argument("--rotor-lag", type=float, default=None, metavar="TAU",
                     help="first-order rotor lag with time constant TAU seconds, up and down (rigid vehicles; the hexacopter model's motors: 0.015; DESIGN 4j)")
+    ap.add_argument("--sensor-noise", type=float, nargs=4, default=None, metavar=("P", "V", "W", "A"),
+                    help="sensor noise on the observations: standard deviations of position (m), velocity (m/s), body rate (rad/s) and attitude (rad) "
+                         "(fp32 rigid vehicles; DESIGN 4l)")
     ap.add_argument("--log-json", default=None, help="write the learning curve (one record per iteration) and the final evaluation to this file")
     ap.add_argument("--warm-start-pid", type=int, default=None, metavar="DAGGER_ROUNDS",
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
@@ -67,6 +70,8 @@ def main():
         env.set_randomization(amd.DynamicsRandomization.around_one(mass=a.randomize_mass, inertia=a.randomize_inertia, thrust=a.randomize_thrust))
     if a.rotor_lag is not None:
         env.set_rotor_lag(amd.RotorLag(a.rotor_lag))
+    if a.sensor_noise is not None:
+        env.set_sensor_noise(amd.SensorNoise(*a.sensor_noise))
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,

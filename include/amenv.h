@@ -441,6 +441,38 @@ int amenv_get_rotor_state(amenv* env, void* out, void* stream);
 /* the inverse: parity injection, checkpoint / restore.  Refused while the lag is off. */
 int amenv_set_rotor_state(amenv* env, const void* in, void* stream);
 
+/* ---- sensor noise on the observations ----------------------------------------------------------------------
+ * Opt-in, per handle, all standard deviations 0 by default.  Every observation row a kernel forms -- the step row, the terminal row, the
+ * post-reset row, the amenv_reset row, the amenv_observe row, every row of amenv_rollout and amenv_rollout_policy[_norm] -- is formed from a
+ * perturbed COPY of the 13 state numbers; the state itself, reward, termination, the reset draws, amenv_get_state, amenv_ee_position and
+ * the Monitor totals use the true state.  The noise is a pure function of (config seed, global env id, episode, s), s = the env's step
+ * field as stored after the row's step (0 for a post-reset row): no state is stored, sharding by global env id is unaffected, a run can be
+ * replayed, and amenv_observe returns the row the last step returned.
+ *   draw    three Philox4x32-10 blocks, key = seed, counter = (gid lo, gid hi, episode, 0x4E000000 | ((s & 0x3FFFFF) << 2) | b), b = 0, 1, 2;
+ *           word k of block b is sample j = 4 b + k:  n_j = (float(sum of the word's four bytes) - 510.0f) * 0.006765875f
+ *           (unit variance, |n| <= 3.4506, excess kurtosis -0.3: an Irwin-Hall sum of four byte-uniforms; no Box-Muller, so the samples
+ *           are integer arithmetic and one multiply, reproducible bit for bit on a CPU)
+ *   j 0..2  p += sigma_position n     j 3..5  v += sigma_velocity n     j 6..8  w += sigma_rate n          (one fma each)
+ *   j 9..11 d = (sigma_attitude / 2) n;  q~ = q (x) (1, d) (Hamilton product, scalar first), renormalised
+ * With the observation normaliser inside amenv_rollout_policy_norm the noise comes first: the frozen statistics normalise the noisy row
+ * and the `update` sums count the noisy raw rows.
+ * Served: fp32 handles of what amenv_set_randomization serves (rigid vehicles with 4 or 6 rotors, every task, lane and helper-wave step
+ * kernels, amenv_rollout, amenv_rollout_policy[_norm] in the one-lane-per-env form), composable with randomisation and rotor lag.
+ * Refused with AMENV_ERR_INVALID, the handle untouched: a bad struct_size, a sigma that is not finite with 0 <= sigma <= 1, arm vehicles,
+ * other rotor counts, fp64 handles, a handle whose step kernel is the lane-quad one, task.max_episode_steps > 2^22 - 2 (s has 22 bits).
+ * A configuration call without allocation or launch; it applies from the next launch. */
+typedef struct amenv_sensor_noise {
+  uint32_t struct_size;   /* = sizeof(amenv_sensor_noise): guard */
+  float sigma_position;   /* m */
+  float sigma_velocity;   /* m/s */
+  float sigma_rate;       /* rad/s */
+  float sigma_attitude;   /* rad */
+} amenv_sensor_noise;
+/* z NULL or all sigmas 0 = off: the handle launches exactly the kernels it launched before. */
+int amenv_set_sensor_noise(amenv* env, const amenv_sensor_noise* z);
+/* out [N, 12] f32 (device): the twelve unit samples n_0 .. n_11 of every env's current (episode, step), whether the noise is on or off. */
+int amenv_sensor_noise_samples(amenv* env, float* out, void* stream);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

@@ -12,10 +12,11 @@ from . import vec_env
 from .gpu_env import GpuWaypointEnv
 from .randomization import DynamicsRandomization
 from .rotor_lag import RotorLag
+from .sensor_noise import SensorNoise
 from .vec_env import GpuVecEnv
 from .obs_norm import GpuVecNormalize, ObsNormalizer
 from . import baselines, ppo
 from .baselines import MinSnapTrajectory, PidController, PidWaypointPolicy
 from .ppo import PPO, ActorCritic, evaluate_policy, clone_pid_policy
 
-__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]
+__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]

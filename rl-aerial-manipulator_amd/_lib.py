@@ -75,6 +75,11 @@ class RotorLagC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("tau_up", C.c_double), ("tau_down", C.c_double)]
 
 
+class SensorNoiseC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sigma_position", C.c_float), ("sigma_velocity", C.c_float), ("sigma_rate", C.c_float),
+                ("sigma_attitude", C.c_float)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -96,6 +101,8 @@ SYMBOLS = {
     "amenv_set_rotor_lag": (C.c_int, [_P, C.POINTER(RotorLagC)]),
     "amenv_get_rotor_state": (C.c_int, [_P, _P, _P]),
     "amenv_set_rotor_state": (C.c_int, [_P, _P, _P]),
+    "amenv_set_sensor_noise": (C.c_int, [_P, C.POINTER(SensorNoiseC)]),
+    "amenv_sensor_noise_samples": (C.c_int, [_P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

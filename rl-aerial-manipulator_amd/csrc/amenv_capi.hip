@@ -66,6 +66,8 @@ struct amenv {
   DrRanges dr_r = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};   // its ranges (lo, hi - lo); {1, 1} = the nominal vehicle
   bool lag = false;                // amenv_set_rotor_lag: first-order rotor lag on
   double lag_a[2] = {1.0, 1.0};    // its coefficients -expm1(-dt / tau_up), -expm1(-dt / tau_down), fp64
+  bool noise = false;              // amenv_set_sensor_noise: sensor noise on the observation rows
+  NoiseSig noise_s = {0.0f, 0.0f, 0.0f, 0.0f};   // its standard deviations: position, velocity, body rate, attitude
   void* lag_w = nullptr;           // [n_tiles][n_rotors][64] rotor states | [n_rotors] w0, of the handle's dtype; allocated when the lag is first enabled
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
@@ -331,10 +333,17 @@ template <typename T, int NROT> LagArg<T, NROT, true> make_lag(const amenv& e) {
   L.a_up = T(e.lag_a[0]); L.a_down = T(e.lag_a[1]);
   return L;
 }
-// the kernels' last argument: the randomisation ranges, and behind them the lag block in the LAG instantiations
-template <typename T, int NROT, bool DR, bool LAG> DynArg<T, NROT, DR, LAG> make_dyn(const amenv& e) {
-  if constexpr (LAG) return DynArg<T, NROT, true, true>{make_dr<true>(e), make_lag<T, NROT>(e)};
+// the kernels' last argument: the randomisation ranges, behind them the lag block in the LAG instantiations, behind that the sensor
+// noise's sigmas in the NOISE ones
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false> DynArg<T, NROT, DR, LAG, NOISE> make_dyn(const amenv& e) {
+  if constexpr (LAG && NOISE) return DynArg<T, NROT, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}};
+  else if constexpr (NOISE) return DynArg<T, NROT, true, false, true>{make_dr<true>(e), NoiseArg<true>{e.noise_s}};
+  else if constexpr (LAG) return DynArg<T, NROT, true, true>{make_dr<true>(e), make_lag<T, NROT>(e)};
   else return DynArg<T, NROT, DR, false>{make_dr<DR>(e)};
+}
+// the cold kernels' (reset, observe) runtime switch
+NoiseRt make_noise_rt(const amenv& e) {
+  return NoiseRt{e.noise_s, uint32_t(e.cfg.seed), uint32_t(e.cfg.seed >> 32), e.cfg.env_id_offset, e.noise ? 1 : 0};
 }
 
 bool is_v1(const amenv_config* c) { return c->task.variant == AMENV_TASK_V1_SCALED17 || c->task.variant == AMENV_TASK_V1_RAW17; }
@@ -467,6 +476,7 @@ std::string kernel_name(const amenv& e) {
   std::string name = buf;
   if (e.dr) name += " +dr";
   if (e.lag) name += " +lag";
+  if (e.noise) name += " +noise";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -481,7 +491,7 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 
 // amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
 // runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG>
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG, bool NOISE>
 hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const ColdParams C = make_cold(e);
@@ -504,15 +514,15 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG>(e));
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG, NOISE>(e));
 }
 
 // amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
 // if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false>
+template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false, bool NOISE = false>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG>(e, io, T_steps, s);
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
@@ -555,24 +565,24 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
         const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
-                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG>(e));
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG, NOISE>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
+                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG, NOISE>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG>(e));
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG, NOISE>(e));
     }
   }
   return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
-template <typename T, int NROT, bool DR = false, bool LAG = false>
+template <typename T, int NROT, bool DR = false, bool LAG = false, bool NOISE = false>
 hipError_t dispatch_k(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG>(e, io, T_steps, s, timed);
-  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG>(e, io, T_steps, s, timed);
+  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
+  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);
+  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);
 }
 
 template <typename T>
@@ -581,6 +591,13 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
   if (e.cfg.vehicle.n_joints == 3) {
     if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
+  }
+  if constexpr (sizeof(T) == 4) {
+    if (e.noise) {   // amenv_set_sensor_noise admits fp32 handles of what amenv_set_randomization admits; the NOISE kernels are DR ones, with or without LAG
+      if (nr == 4) return e.lag ? dispatch_k<T, 4, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 4, true, false, true>(e, io, T_steps, s, timed);
+      if (nr == 6) return e.lag ? dispatch_k<T, 6, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 6, true, false, true>(e, io, T_steps, s, timed);
+      return hipErrorInvalidValue;
+    }
   }
   if (e.lag) {  // amenv_set_rotor_lag admits what amenv_set_randomization admits; the LAG kernels are the DR ones (unit ranges when that is off)
     if (nr == 4) return dispatch_k<T, 4, true, true>(e, io, T_steps, s, timed);
@@ -601,7 +618,7 @@ template <typename T>
 hipError_t launch_reset(const amenv& e, const uint8_t* mask, float* obs, int pad_only, hipStream_t s) {
   const int bs = 256, n_pad = e.n_tiles * 64;
   hipLaunchKernelGGL((reset_kernel<T>), dim3((n_pad + bs - 1) / bs), dim3(bs), 0, s, e.cfg.num_envs, n_pad, e.cfg.task.num_waypoints, e.cfg.task.variant, e.cfg.vehicle.n_joints,
-                     e.cfg.task.ee_task, e.tile_bytes, make_cold(e), make_arm<T>(e), e.blob, mask, obs, pad_only);
+                     e.cfg.task.ee_task, e.tile_bytes, make_cold(e), make_arm<T>(e), e.blob, mask, obs, pad_only, make_noise_rt(e));
   return hipGetLastError();
 }
 
@@ -609,7 +626,7 @@ template <typename T>
 hipError_t launch_observe(const amenv& e, float* obs, float* ee, hipStream_t s) {
   const int n = e.cfg.num_envs, bs = 256, K = e.cfg.task.num_waypoints, nj = e.cfg.vehicle.n_joints;
   if (obs) hipLaunchKernelGGL((observe_kernel<T>), dim3((n + bs - 1) / bs), dim3(bs), 0, s, n, K, e.cfg.task.variant, nj, e.cfg.task.ee_task, e.tile_bytes, make_arm<T>(e),
-                              (const void*)e.blob, obs);
+                              (const void*)e.blob, obs, make_noise_rt(e));
   if (ee) hipLaunchKernelGGL((ee_position_kernel<T>), dim3((n + bs - 1) / bs), dim3(bs), 0, s, n, K, nj, e.tile_bytes, make_arm<T>(e), (const void*)e.blob, ee);
   return hipGetLastError();
 }
@@ -634,32 +651,33 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifndef AMENV_RIGID_WG64_MAX
 #define AMENV_RIGID_WG64_MAX 24576
 #endif
-template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG>
+template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG, bool NOISE>
 hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
   const ColdParams C = make_cold(e);
-  const DynArg<float, NROT, DR, LAG> R = make_dyn<float, NROT, DR, LAG>(e);
+  const DynArg<float, NROT, DR, LAG, NOISE> R = make_dyn<float, NROT, DR, LAG, NOISE>(e);
   const int n = e.cfg.num_envs;
   if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG, NOISE>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG, NOISE>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG, NOISE>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   return hipGetLastError();
 }
-template <bool NORM, bool DR, bool LAG = false>
+template <bool NORM, bool DR, bool LAG = false, bool NOISE = false>
 hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const bool four = e.cfg.vehicle.n_rotors == 4;
   if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
-    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG, NOISE>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG, NOISE>(e, T, io, N, s);
   if (e.cfg.task.num_waypoints == 1)
-    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG>(e, T, io, N, s);
-  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG>(e, T, io, N, s)
-              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s);
+  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s)
+              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s);
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true>(e, T, io, N, s);
   if (e.lag) return launch_rigid_policy_dr<NORM, true, true>(e, T, io, N, s);   // (unit ranges when randomisation is off)
   return e.dr ? launch_rigid_policy_dr<NORM, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, false>(e, T, io, N, s);
 }
@@ -674,6 +692,20 @@ __global__ void dr_factors_kernel(int n, uint32_t tile_bytes, const void* __rest
   dr_draw<NROT>(C, R, C.gid0 + i, episode, f);
 #pragma unroll
   for (int k = 0; k < 2 + NROT; k++) out[size_t(i) * (2 + NROT) + k] = f[k];
+}
+
+// amenv_sensor_noise_samples: [N][12] = the twelve unit samples of every env's current (episode, step) (noise_block: the kernels' own draw)
+__global__ void noise_samples_kernel(int n, uint32_t tile_bytes, const void* __restrict__ blob, const ColdParams C, float* __restrict__ out) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int4 iv = *iptr4(const_cast<char*>(tile_base(blob, tile_bytes, i)), i & 63);   // {step, counter, flags, episode}
+#pragma unroll
+  for (uint32_t b = 0; b < 3; b++) {
+    float f[4];
+    noise_block(C.seed_lo, C.seed_hi, C.gid0 + i, iv.w, iv.x, b, f);
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[size_t(i) * 12 + 4 * b + k] = f[k];
+  }
 }
 
 // amenv_set_rotor_lag / amenv_reset: w <- w0 for the masked envs (mask null = all; padding lanes always, as reset_kernel does)
@@ -1039,6 +1071,47 @@ int amenv_dynamics_factors(amenv* e, float* out, void* stream) {
   return AMENV_OK;
 }
 
+int amenv_set_sensor_noise(amenv* e, const amenv_sensor_noise* z) {
+  if (!e) return AMENV_ERR_INVALID;
+  const NoiseSig off = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (!z) {   // off: the handle launches the kernels it launched before
+    e->noise = false; e->noise_s = off;
+    e->kname = kernel_name(*e);
+    return AMENV_OK;
+  }
+  if (z->struct_size != sizeof(amenv_sensor_noise)) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: struct_size must be sizeof(amenv_sensor_noise)");
+  const float sg[4] = {z->sigma_position, z->sigma_velocity, z->sigma_rate, z->sigma_attitude};
+  const char* nm[4] = {"sigma_position", "sigma_velocity", "sigma_rate", "sigma_attitude"};
+  for (int q = 0; q < 4; q++)
+    if (!std::isfinite(sg[q]) || !(sg[q] >= 0.0f) || !(sg[q] <= 1.0f))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_sensor_noise: ") + nm[q] + " must be finite with 0 <= sigma <= 1");
+  const amenv_vehicle& v = e->cfg.vehicle;
+  if (v.n_joints > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: built for rigid vehicles (the arm kernels are not built with it)");
+  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: built for rigid vehicles with 4 or 6 rotors");
+  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: fp32 handles only (the fp64 builds are logic gates of the dynamics)");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  if (e->cfg.task.max_episode_steps > (1 << 22) - 2)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: max_episode_steps must be <= 2^22 - 2 (the step field of the draw's counter has 22 bits)");
+  const bool any = sg[0] != 0.0f || sg[1] != 0.0f || sg[2] != 0.0f || sg[3] != 0.0f;   // all zeros: the same as off
+  e->noise = any;
+  e->noise_s = any ? NoiseSig{sg[0], sg[1], sg[2], sg[3]} : off;
+  e->kname = kernel_name(*e);
+  return AMENV_OK;
+}
+
+int amenv_sensor_noise_samples(amenv* e, float* out, void* stream) {
+  if (!e || !out) return fail(e, AMENV_ERR_INVALID, "amenv_sensor_noise_samples: NULL argument");
+  const int nr = e->cfg.vehicle.n_rotors, n = e->cfg.num_envs;
+  if (e->cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6) || e->cfg.dtype != AMENV_F32)
+    return fail(e, AMENV_ERR_INVALID, "amenv_sensor_noise_samples: built for fp32 rigid vehicles with 4 or 6 rotors");
+  DeviceGuard g(e->device);
+  hipLaunchKernelGGL(noise_samples_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), out);
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
 int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   if (!e) return AMENV_ERR_INVALID;
   if (!lag) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused)
@@ -1190,7 +1263,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && !e->lag && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  const bool quad = !e->dr && !e->lag && !e->noise && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");

@@ -275,11 +275,13 @@ __device__ __forceinline__ void observe_reset(const Env<T, KW>& e, bool ee_task,
   }
 }
 
-template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false, typename LG = LagLane<T, NROT, false>>
+template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false, typename LG = LagLane<T, NROT, false>,
+          typename NZ = NoiseArg<false>>
 __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const ColdParams& C, const ArmArg<T, NJ>& AA, Env<T, KW>& e, const float* act, int i,
                                               bool active, T& reward, float* o, const StepIO& io, char* tile, int lane,
                                               bool have_episode, bool& was_reset, int& ep_len_out, float& ep_ret_out, const X& x = X{},
-                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr) {
+                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr, const NZ& nz = NZ{}) {
+  static_assert(!NZ::on || NJ == 0, "sensor noise is built for rigid vehicles");
   constexpr int OD = ObsDim<VAR, NJ>::value;
   const int K = KW == 1 ? 1 : P.K;
   if constexpr (NJ > 0) {
@@ -299,8 +301,14 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
   constexpr bool kColdElsewhere = ROLE == ARM_ROLE_FLAGS;   // helper waves write terminal / post-reset rows and the reset state
   constexpr bool kLazyObs = ROLE == ARM_ROLE_MAIN || kColdElsewhere;
   auto obs_now = [&]() {
-    if constexpr (VAR == VAR_V1) { observe_v1<T, KW>(P.raw_obs != 0, e, o); } else { observe<T, KW, EE>(K, e, o, ee_task); }
-    if constexpr (NJ > 0) observe_joints<T, KW>(e, o);
+    if constexpr (NZ::on) {   // sensor noise: the row is formed from a perturbed copy, keyed by the env's current (episode, step)
+      Env<T, KW> c = e;
+      sensor_perturb<T, KW, NZ::lds_ne>(C.seed_lo, C.seed_hi, nz.s, C.gid0 + i, e.episode, e.step, c, nz.column());
+      if constexpr (VAR == VAR_V1) { observe_v1<T, KW>(P.raw_obs != 0, c, o); } else { observe<T, KW, EE>(K, c, o, ee_task); }
+    } else {
+      if constexpr (VAR == VAR_V1) { observe_v1<T, KW>(P.raw_obs != 0, e, o); } else { observe<T, KW, EE>(K, e, o, ee_task); }
+      if constexpr (NJ > 0) observe_joints<T, KW>(e, o);
+    }
   };
   if constexpr (!kLazyObs) obs_now();
   was_reset = false;
@@ -338,6 +346,10 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
       }
       if (resets) {
         if constexpr (kColdElsewhere) { (void)r; }
+        else if constexpr (NZ::on) {   // the post-reset row of (episode + 1, step 0), by the general path (no observe_reset shortcut)
+          if constexpr (VAR == VAR_V1) reset_from_words_v1<T, KW>(K, e, r); else reset_from_words<T, KW>(C, K, e, r);
+          obs_now();
+        }
         else if constexpr (VAR == VAR_V1) { reset_from_words_v1<T, KW>(K, e, r); observe_v1<T, KW>(P.raw_obs != 0, e, o); }
         else {
           reset_from_words<T, KW>(C, K, e, r);
@@ -388,13 +400,15 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 #endif
 // DR: per-episode dynamics randomisation, rigid vehicles only; the factors are drawn once per launch from the loaded episode.
 // LAG: first-order rotor lag, built together with DR only; the rotor states are loaded from and stored to the handle's side buffer.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false>
+// NOISE: sensor noise on the observation rows, built together with DR only, fp32 only.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG> DA) {
+                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
+  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -428,8 +442,8 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
   DynFac<T, NROT, DR> df;
   if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
-  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset, ep_len, ep_ret,
-                                                                      NoXchg{}, df, &lg);
+  uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
+                                                                      ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
   const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
   AMENV_STAMP(3);          // dynamics + task + obs computed
   accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
@@ -486,12 +500,16 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 //             ended), passes the barrier, takes the reset position of reset lanes from LDS and stores the state of every lane.
 // DR: the waves that integrate (main, observation) draw the factors of the loaded episode.
 // LAG: both of them load the same rotor states and filter them; the main wave alone stores, after the barrier.
-template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false>
+// NOISE: every wave that forms a row perturbs a copy of the state first -- the observation wave with the step key it forms itself
+// (loaded step + 1: it does not run the task step, which increments exactly once on the single-waypoint v2 task), the reset wave its
+// (episode + 1, step 0) row, the main wave of the 128-thread form inside step_lane.  Nothing is added to the integrating wave of the 256-thread form.
+template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false, bool NOISE = false>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                      const DynArg<T, NROT, DR, LAG> DA) {
+                                                      const DynArg<T, NROT, DR, LAG, NOISE> DA) {
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
+  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, 0>::value;
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
@@ -555,7 +573,13 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       AMENV_STAMP(1);
       reset_from_words<T, KW>(C, 1, er, r);
       float ro[kObsDimMax];
-      observe_reset<T, KW, false, 0>(er, false, ro);
+      if constexpr (NOISE) {         // the new episode's first row: key (episode + 1, step 0), general observation path
+        Env<T, KW> c = er;
+        sensor_perturb<T, KW>(C.seed_lo, C.seed_hi, DA.Z.s, C.gid0 + i, er.episode, 0, c);
+        observe<T, KW>(1, c, ro);
+      } else {
+        observe_reset<T, KW, false, 0>(er, false, ro);
+      }
       rst[lane] = float(er.px); rst[64 + lane] = float(er.py); rst[128 + lane] = float(er.pz); rst[192 + lane] = float(er.final_yaw);
       AMENV_STAMP(2); AMENV_STAMP(3);
       __syncthreads();               // flags published (and this wave's reset positions)
@@ -591,7 +615,13 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       dynamics<T, NROT, KW, DR, LagLane<T, NROT, LAG>>(P, e, act[0], act[1], act[2], act[3], df, &lg);
       AMENV_STAMP(2);
       float ho[kObsDimMax];
-      observe<T, KW>(1, e, ho);
+      if constexpr (NOISE) {         // this wave does not run the task step: the row's key is the step the main wave is about to store
+        Env<T, KW> c = e;
+        sensor_perturb<T, KW>(C.seed_lo, C.seed_hi, DA.Z.s, C.gid0 + i, e.episode, e.step + 1, c);
+        observe<T, KW>(1, c, ho);
+      } else {
+        observe<T, KW>(1, e, ho);
+      }
       stage_obs<OD>(lds + lane * OD, ho);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -620,7 +650,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     AMENV_STAMP(1);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
     uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_FLAGS, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
-                                                                                    ep_len, ep_ret, NoXchg{}, df, &lg);
+                                                                                    ep_len, ep_ret, NoXchg{}, df, &lg);   // (forms no row: no noise argument)
     AMENV_STAMP(2);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     flag[lane] = (is_done ? 1u : 0u) | (was_reset ? 2u : 0u);
@@ -670,8 +700,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
-                                                                                    ep_len, ep_ret, x, df, &lg);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false,
+                                                                                    was_reset, ep_len, ep_ret, x, df, &lg, noise_of(DA));
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int(blockIdx.x), bits, is_done, ep_len, ep_ret);
     store_env_step<T, KW>(tile, lane, e);
@@ -873,13 +903,15 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
 // State stays in registers across steps: HBM traffic per env-step drops to action + outputs.
 // DR: factors drawn at entry and again for a lane after its auto-reset.
 // LAG: the rotor states stay in registers over the steps, restart at w0 after an auto-reset and are stored once at the end.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false>
+// NOISE: every row is formed from a perturbed copy of the state, as in step_kernel.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false>
 __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, int n_steps, const StepTail tl, const HotParams<T, NROT> P,
-                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG> DA) {
+                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
+  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, nullptr, nullptr, nullptr, tl.stats};
@@ -912,8 +944,8 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
       }
     }
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
-    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset, ep_len,
-                                                                        ep_ret, NoXchg{}, df, &lg);
+    uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset,
+                                                                        ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
     if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); }
     any_reset |= was_reset;
@@ -952,7 +984,7 @@ __device__ __forceinline__ void joints_and_tool(const ArmParams<T>& A, int K, in
 
 template <typename T>
 __global__ void reset_kernel(int n, int n_pad, int K, int variant, int nj, int ee_task, uint32_t tile_bytes, const ColdParams C, const ArmParams<T> A,
-                             void* __restrict__ blob, const uint8_t* __restrict__ mask, float* __restrict__ obs, int pad_only) {
+                             void* __restrict__ blob, const uint8_t* __restrict__ mask, float* __restrict__ obs, int pad_only, const NoiseRt nz) {
   const bool v1 = variant != AMENV_TASK_V2_SCALED20;
   const int od = v1 ? 17 : 20 + 2 * nj + (nj > 0 ? 3 : 0);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -973,6 +1005,7 @@ __global__ void reset_kernel(int n, int n_pad, int K, int variant, int nj, int e
     float o[kObsDimMax];
     joints_and_tool<T, AMENV_MAX_WAYPOINTS>(A, K, nj, tile, lane, e);   // (zero joints after a reset)
     if (do_reset && nj > 0) { e.eox = A.ee_home[0]; e.eoy = A.ee_home[1]; e.eoz = A.ee_home[2]; }   // as the step kernels' reset path
+    if (nz.on) sensor_perturb<T, AMENV_MAX_WAYPOINTS>(nz.seed_lo, nz.seed_hi, nz.s, nz.gid0 + i, e.episode, e.step, e);   // wave-uniform; e is a copy by now (state stored above)
     if (v1) observe_v1<T, AMENV_MAX_WAYPOINTS>(variant == AMENV_TASK_V1_RAW17, e, o);
     else observe<T, AMENV_MAX_WAYPOINTS, true>(K, e, o, nj > 0 && ee_task != 0);
     if (nj > 0) observe_joints<T, AMENV_MAX_WAYPOINTS>(e, o);
@@ -983,7 +1016,7 @@ __global__ void reset_kernel(int n, int n_pad, int K, int variant, int nj, int e
 // _get_observation of the current state for every env (no stepping).
 template <typename T>
 __global__ void observe_kernel(int n, int K, int variant, int nj, int ee_task, uint32_t tile_bytes, const ArmParams<T> A, const void* __restrict__ blob,
-                               float* __restrict__ obs) {
+                               float* __restrict__ obs, const NoiseRt nz) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const bool v1 = variant != AMENV_TASK_V2_SCALED20;
@@ -993,6 +1026,7 @@ __global__ void observe_kernel(int n, int K, int variant, int nj, int ee_task, u
   load_env<T, AMENV_MAX_WAYPOINTS>(K, tile, threadIdx.x & 63, e);
   joints_and_tool<T, AMENV_MAX_WAYPOINTS>(A, K, nj, tile, threadIdx.x & 63, e);
   float o[kObsDimMax];
+  if (nz.on) sensor_perturb<T, AMENV_MAX_WAYPOINTS>(nz.seed_lo, nz.seed_hi, nz.s, nz.gid0 + i, e.episode, e.step, e);   // wave-uniform; the stored (episode, step): the last row's key
   if (v1) observe_v1<T, AMENV_MAX_WAYPOINTS>(variant == AMENV_TASK_V1_RAW17, e, o);
   else observe<T, AMENV_MAX_WAYPOINTS, true>(K, e, o, nj > 0 && ee_task != 0);
   if (nj > 0) observe_joints<T, AMENV_MAX_WAYPOINTS>(e, o);

@@ -187,9 +187,33 @@ template <typename T, int NROT> struct LagArg<T, NROT, true> {
   uint32_t n_pad;    // the handle's padded env count (whole tiles)
   T a_up, a_down;    // -expm1(-dt / tau), formed on the host in fp64
 };
-// The one kernel argument that carries both switches: DrArg's bytes unless LAG (the kernels without lag keep their argument segment).
-template <typename T, int NROT, bool DR, bool LAG> struct DynArg { DrArg<DR> R; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; };
+// ---- sensor noise on the observations (include/amenv.h amenv_set_sensor_noise) -----------------------------------
+// Four standard deviations (position m, velocity m/s, body rate rad/s, attitude rad); they travel behind the lag's fields in the NOISE
+// instantiations only.  NOISE is built only together with DR (unit ranges when randomisation is off), fp32 only.
+struct NoiseSig { float p, v, w, a; };
+template <bool NOISE> struct NoiseArg { static constexpr bool on = false; static constexpr int lds_ne = 0; };
+template <> struct NoiseArg<true> {
+  static constexpr bool on = true; static constexpr int lds_ne = 0;
+  NoiseSig s;
+  __device__ __forceinline__ float* column() const { return nullptr; }
+};
+// The closed-loop kernel's NORM forms have no VGPR to spare: there the perturbed copy goes through an LDS column of the lane's own,
+// [13][NE] floats (no barrier): each Philox block's four results leave the registers before the next block is drawn, and observe() reads
+// the copy back one number at a time.
+template <int NE> struct NoiseLds {
+  static constexpr bool on = true; static constexpr int lds_ne = NE;
+  NoiseSig s; float* col;
+  __device__ __forceinline__ float* column() const { return col; }
+};
+// The one kernel argument that carries the switches: DrArg's bytes unless LAG or NOISE (the kernels without them keep their argument segment).
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false> struct DynArg { DrArg<DR> R; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, false> { DrArg<true> R; LagArg<T, NROT, true> L; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, false, true> { DrArg<true> R; NoiseArg<true> Z; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; };
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE>
+__host__ __device__ __forceinline__ NoiseArg<NOISE> noise_of(const DynArg<T, NROT, DR, LAG, NOISE>& a) {
+  if constexpr (NOISE) return a.Z; else return NoiseArg<false>{};
+}
 // env i's rotor r sits at lag_slot(i) + 64 r
 template <int NROT> __device__ __forceinline__ size_t lag_slot(int i) { return size_t(i >> 6) * (NROT * 64) + size_t(i & 63); }
 // What dynamics() filters through: get(r) / set(r, w') and the two coefficients.  LagLane keeps the rotor states in the lane's registers
@@ -568,6 +592,59 @@ __device__ __forceinline__ DynFac<T, NROT, true> dr_factors(const HotParams<T, N
   d.inv_ki = rcp_(T(f[1]));
   return d;
 }
+
+// ---- sensor noise -----------------------------------------------------------------------------------------------
+// Twelve unit samples per (seed, global env id, episode, step): three Philox blocks, counter (gid, episode, kNoiseTag | step << 2 | b); the
+// top byte differs from every other draw's last counter word (resets 0..4, randomisation 0x4452....).  Word k of block b is sample 4 b + k:
+// the sum of the word's four bytes (ONE v_sad_u8), centred and scaled -- an Irwin-Hall sum of four byte-uniforms, variance 21845, |n| <=
+// 3.4506.  Integer arithmetic, one exact subtraction and one multiply: numpy reproduces it bit for bit (tests/noise_ref.py).
+constexpr uint32_t kNoiseTag = 0x4E000000u;
+constexpr float kNoiseScale = 0.006765875f;   // fp32 nearest to 21845^-1/2
+__device__ __forceinline__ float noise_unit(uint32_t w) { return (float(int32_t(__builtin_amdgcn_sad_u8(w, 0u, 0u))) - 510.0f) * kNoiseScale; }
+__device__ __forceinline__ void noise_block(uint32_t seed_lo, uint32_t seed_hi, int64_t gid, int32_t episode, int32_t step, uint32_t b, float* n /*[4]*/) {
+  uint32_t w[4];
+  philox4x32_10(seed_lo, seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode),
+                kNoiseTag | ((uint32_t(step) & 0x3FFFFFu) << 2) | b, w);
+#pragma unroll
+  for (int k = 0; k < 4; k++) n[k] = noise_unit(w[k]);
+}
+// Perturb a COPY of the state (the 13 numbers the observation reads) in place; the key's step is the env's step field as stored after the
+// observation's step (0 for a post-reset row).  Samples 0..2 position, 3..5 velocity, 6..8 body rate: one fma each; 9..11 a small rotation
+// d = sigma_a / 2 * n applied on the body side, q~ = q (x) (1, d) (Hamilton, scalar first), renormalised.  Each block is used up before the
+// next is drawn (four samples live at a time).  NE > 0 (fp32): the results are staged through the LDS column `col` ([13][NE] floats, the
+// lane's own) as they are formed and read back at the end, so that the copy does not sit in registers beside the Philox rounds.
+template <typename T, int KW, int NE = 0>
+__device__ __forceinline__ void sensor_perturb(uint32_t seed_lo, uint32_t seed_hi, const NoiseSig& S, int64_t gid, int32_t episode, int32_t step, Env<T, KW>& c,
+                                               float* col = nullptr) {
+  static_assert(NE == 0 || sizeof(T) == 4, "the LDS column holds floats");
+  float n[4];
+  noise_block(seed_lo, seed_hi, gid, episode, step, 0u, n);
+  c.px = fma_(T(S.p), T(n[0]), c.px); c.py = fma_(T(S.p), T(n[1]), c.py); c.pz = fma_(T(S.p), T(n[2]), c.pz);
+  c.vx = fma_(T(S.v), T(n[3]), c.vx);
+  if constexpr (NE > 0) { col[0] = c.px; col[NE] = c.py; col[2 * NE] = c.pz; col[3 * NE] = c.vx; asm volatile("" ::: "memory"); }
+  noise_block(seed_lo, seed_hi, gid, episode, step, 1u, n);
+  c.vy = fma_(T(S.v), T(n[0]), c.vy); c.vz = fma_(T(S.v), T(n[1]), c.vz);
+  c.wx = fma_(T(S.w), T(n[2]), c.wx); c.wy = fma_(T(S.w), T(n[3]), c.wy);
+  if constexpr (NE > 0) { col[4 * NE] = c.vy; col[5 * NE] = c.vz; col[6 * NE] = c.wx; col[7 * NE] = c.wy; asm volatile("" ::: "memory"); }
+  noise_block(seed_lo, seed_hi, gid, episode, step, 2u, n);
+  c.wz = fma_(T(S.w), T(n[0]), c.wz);
+  const T ha = T(0.5f * S.a);
+  const T dx = ha * T(n[1]), dy = ha * T(n[2]), dz = ha * T(n[3]);
+  const T qw = fma_(-c.qz, dz, fma_(-c.qy, dy, fma_(-c.qx, dx, c.qw)));
+  const T qx = fma_(-c.qz, dy, fma_(c.qy, dz, fma_(c.qw, dx, c.qx)));
+  const T qy = fma_(-c.qx, dz, fma_(c.qz, dx, fma_(c.qw, dy, c.qy)));
+  const T qz = fma_(-c.qy, dx, fma_(c.qx, dy, fma_(c.qw, dz, c.qz)));
+  const T rn = rsqrt_(fma_(qw, qw, fma_(qx, qx, fma_(qy, qy, qz * qz))));
+  c.qw = qw * rn; c.qx = qx * rn; c.qy = qy * rn; c.qz = qz * rn;
+  if constexpr (NE > 0) {
+    col[8 * NE] = c.wz; col[9 * NE] = c.qw; col[10 * NE] = c.qx; col[11 * NE] = c.qy; col[12 * NE] = c.qz;
+    asm volatile("" ::: "memory");   // the copy is read back from the column: nothing is forwarded in registers
+    c.px = col[0]; c.py = col[NE]; c.pz = col[2 * NE]; c.vx = col[3 * NE]; c.vy = col[4 * NE]; c.vz = col[5 * NE]; c.wx = col[6 * NE];
+    c.wy = col[7 * NE]; c.wz = col[8 * NE]; c.qw = col[9 * NE]; c.qx = col[10 * NE]; c.qy = col[11 * NE]; c.qz = col[12 * NE];
+  }
+}
+// What the cold, host-launched kernels (reset, observe) take: a wave-uniform switch, the sigmas and the key's seed / first global id.
+struct NoiseRt { NoiseSig s; uint32_t seed_lo, seed_hi; int64_t gid0; int32_t on; };
 
 // WaypointQuadEnv.reset (rl_env_scaledObs.py:40-79) with the DESIGN.md draw table.  All draws
 // are formed in fp32 with explicit fmaf so the CPU oracle reproduces them bit for bit.

@@ -35,12 +35,16 @@ struct NormArg {
 // LAG: first-order rotor lag.  The NORM forms have no VGPR to spare, so the rotor states of this kernel live in LDS, and with
 // them the randomisation's factors ((2 NROT + 2) x NE floats, every lane its own column: no barrier): dynamics() filters them there one
 // rotor at a time (LagLds), and the states go back to the handle's side buffer once at the end.
-template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false>
+// NOISE: sensor noise: row 0 and every later row are formed from a perturbed copy of the state; the noise comes first and the
+// normaliser second (the frozen statistics normalise the noisy row, the `update` sums count the noisy raw rows).  In the NORM forms the
+// perturbed copy is staged through LDS (13 x NE floats, every lane its own column: NoiseLds).
+template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false, bool NOISE = false>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
                                                                                          const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
-                                                                                         const DynArg<float, NROT, DR, LAG> DA) {
+                                                                                         const DynArg<float, NROT, DR, LAG, NOISE> DA) {
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
+  static_assert(!NOISE || DR, "sensor noise is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -51,6 +55,8 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   __shared__ float valb[NE];
   __shared__ double md[NORM ? 2 * OD : 1];                                // entry statistics: mean | 1 / sqrt(var + eps)
   __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors, [2 NROT + 2][NE]: each lane reads and writes its own column
+  constexpr bool kNoiseLds = NOISE && NORM;
+  __shared__ float zl[kNoiseLds ? 13 * NE : 1];                           // sensor noise: the perturbed copy of the 13 state numbers, [13][NE]
   __bf16* h3 = h1;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
@@ -193,7 +199,13 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
 #pragma unroll
     for (int c = 0; c < AD; c++) { const uint4 v = ac[c]; std_a[c] = __uint_as_float(v.x); ls_a[c] = __uint_as_float(v.y); }
-    if constexpr (VAR == VAR_V1) observe_v1<float, KW>(P.raw_obs != 0, e, o); else observe<float, KW>(K, e, o);
+    if constexpr (NOISE) {   // row 0: the stored (episode, step) is the key of the row the previous launch (or the reset) published
+      Env<float, KW> c = e;
+      sensor_perturb<float, KW, kNoiseLds ? NE : 0>(C.seed_lo, C.seed_hi, DA.Z.s, C.gid0 + i, e.episode, e.step, c, zl + el);
+      if constexpr (VAR == VAR_V1) observe_v1<float, KW>(P.raw_obs != 0, c, o); else observe<float, KW>(K, c, o);
+    } else {
+      if constexpr (VAR == VAR_V1) observe_v1<float, KW>(P.raw_obs != 0, e, o); else observe<float, KW>(K, e, o);
+    }
     __bf16* xr = xin + el * kXS;
     __bf16* xl = xlo + el * kXS;
 #pragma unroll
@@ -247,8 +259,13 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     float reward; bool was_reset; int ep_len; float ep_ret;
     LagLds<NROT, NE, LAG> lg;
     if constexpr (LAG) { lg.col = wl + el; lg.a_up = DA.L.a_up; lg.a_down = DA.L.a_down; }
-    const uint32_t bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset,
-                                                                                ep_len, ep_ret, NoXchg{}, df, &lg);
+    uint32_t bits;
+    if constexpr (kNoiseLds)
+      bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>, NoiseLds<NE>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
+                                                                                                   ep_ret, NoXchg{}, df, &lg, NoiseLds<NE>{DA.Z.s, zl + el});
+    else
+      bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
+                                                                                                      ep_ret, NoXchg{}, df, &lg, noise_of(DA));
     if constexpr (DR && !LAG) { if (was_reset) df = dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) {
       if (was_reset) {   // the new episode's rotors: w0 (behind the states in the side buffer), and the new episode's vehicle

@@ -32,10 +32,14 @@ class GpuWaypointEnv:
 
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
-                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None):
+                 rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
+                 sensor_noise=None):
         from .rotor_lag import RotorLag
+        from .sensor_noise import SensorNoise
         if rotor_lag is not None and not isinstance(rotor_lag, RotorLag):   # before any device is touched
             raise L.AmenvError(f"rotor_lag: expected a RotorLag or None, got {type(rotor_lag).__name__}")
+        if sensor_noise is not None and not isinstance(sensor_noise, SensorNoise):
+            raise L.AmenvError(f"sensor_noise: expected a SensorNoise or None, got {type(sensor_noise).__name__}")
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -92,6 +96,9 @@ class GpuWaypointEnv:
         self.rotor_lag = None
         if rotor_lag is not None:
             self.set_rotor_lag(rotor_lag)
+        self.sensor_noise = None
+        if sensor_noise is not None:
+            self.set_sensor_noise(sensor_noise)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -157,6 +164,25 @@ class GpuWaypointEnv:
             raise L.AmenvError(f"set_rotor_state: expected shape {(self.num_envs, self.n_rotors)}, got {tuple(t.shape)}")
         self._check(self.lib.amenv_set_rotor_state(self._h, C.c_void_p(t.data_ptr()), self._stream()), "amenv_set_rotor_state")
         torch.cuda.current_stream(self.device).synchronize()   # the staging tensor stays alive until the copy has run
+
+    def set_sensor_noise(self, noise):
+        """Sensor noise on every observation row (a `SensorNoise`, or None = exact observations; fp32 rigid vehicles with 4 or 6 rotors,
+        not with kernel="team").  A pure function of (seed, env id, episode, step): nothing is stored, it applies from the next launch,
+        and observe() repeats the row the last step returned.  Reward, termination, get_state() and stats() stay exact."""
+        from .sensor_noise import SensorNoise
+        if noise is not None and not isinstance(noise, SensorNoise):
+            raise L.AmenvError(f"set_sensor_noise: expected a SensorNoise or None, got {type(noise).__name__}")
+        c = None if noise is None else noise.to_c()
+        self._check(self.lib.amenv_set_sensor_noise(self._h, None if c is None else C.byref(c)), "amenv_set_sensor_noise")
+        self.sensor_noise = noise
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
+    def sensor_noise_samples(self):
+        """[N, 12] f32 on this env's device: the unit samples of every env's current (episode, step) -- position 0..2, velocity 3..5,
+        body rate 6..8, attitude 9..11 -- drawn by the kernels' own device function."""
+        out = torch.empty(self.num_envs, 12, dtype=torch.float32, device=self.device)
+        self._check(self.lib.amenv_sensor_noise_samples(self._h, C.c_void_p(out.data_ptr()), self._stream()), "amenv_sensor_noise_samples")
+        return out
 
     def reset(self, mask=None):
         """WaypointQuadEnv.reset (v2/rl_env_scaledObs.py:40-79) for all envs, or those with mask != 0."""

@@ -8,6 +8,7 @@ and `evaluate_policy` do per step).  Compares the one-launch policy forward (`am
     python tools/rollout_rate.py --one-launch --vehicle hexa_arm --n-joints 2 [--waypoints 4]
     --randomize: per-episode dynamics randomisation on (rigid vehicles; the quadrotor's one-launch rollout then runs the lane form)
     --rotor-lag TAU: first-order rotor lag on (rigid vehicles; the same rule for the quadrotor's one-launch rollout)
+    --sensor-noise P V W A: sensor noise on the observations (fp32 rigid vehicles; the same rule)
 """
 import argparse
 import json
@@ -32,9 +33,12 @@ if __name__ == "__main__":
     ap.add_argument("--block-size", type=int, default=0, help="amenv_config.block_size (64: the quadrotor's one-launch rollout runs the lane form, not the lane-quad one)")
     ap.add_argument("--randomize", action="store_true", help="per-episode dynamics randomisation on (mass and inertia +-20 %%, thrust +-5 %%; DESIGN 4i)")
     ap.add_argument("--rotor-lag", type=float, default=None, metavar="TAU", help="first-order rotor lag with time constant TAU seconds (DESIGN 4j)")
+    ap.add_argument("--sensor-noise", type=float, nargs=4, default=None, metavar=("P", "V", "W", "A"),
+                    help="sensor noise on the observations: standard deviations of position, velocity, body rate, attitude (DESIGN 4l)")
     a = ap.parse_args()
     import torch
     import rl_aerial_manipulator_amd as amd
+    noise = None if a.sensor_noise is None else amd.SensorNoise(*a.sensor_noise)
     lag = None if a.rotor_lag is None else amd.RotorLag(a.rotor_lag)
     dr = amd.DynamicsRandomization.around_one(mass=0.2, inertia=0.2, thrust=0.05) if a.randomize else None
     out = {}
@@ -44,7 +48,7 @@ if __name__ == "__main__":
         for n in a.envs:
             for fused in (True, False):
                 env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints, block_size=a.block_size,
-                                         randomization=dr, rotor_lag=lag)
+                                         randomization=dr, rotor_lag=lag, sensor_noise=noise)
                 norm = ObsNormalizer(env.obs_dim) if a.normalize_obs else None
                 algo = PPO(env, obs_normalizer=norm, fused_rollout=fused, n_steps=a.rollout_steps, seed=0)
                 algo.fused_rollout_fp32_stats = False        # time the rollout itself: no fp32 re-evaluation of the buffer behind it
@@ -63,12 +67,12 @@ if __name__ == "__main__":
                 env.close()
                 if norm is not None:
                     norm.close()
-        print(json.dumps({"vehicle": a.vehicle, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "block_size": a.block_size, "n_joints": a.n_joints, "waypoints": a.waypoints, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
+        print(json.dumps({"vehicle": a.vehicle, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "block_size": a.block_size, "n_joints": a.n_joints, "waypoints": a.waypoints, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
                           "loop": "PPO.collect_rollouts (policy + sample + clip + step [+ normaliser] x T, GAE)", "results": out}))
         sys.exit(0)
     for n in a.envs:
         env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints, block_size=a.block_size,
-                                         randomization=dr, rotor_lag=lag)
+                                         randomization=dr, rotor_lag=lag, sensor_noise=noise)
         pol = amd.ActorCritic(env.obs_dim, env.act_dim).to(env.device).flatten_()
         for mode in ("fused", "torch"):
             obs = env.reset()
@@ -94,4 +98,4 @@ if __name__ == "__main__":
             out[f"{n}_{mode}"] = {"eager_us_per_step": dt / a.steps * 1e6, "graph_us_per_step": dg / (a.steps // 16 * 16) * 1e6,
                                   "graph_env_steps_per_s": n * (a.steps // 16 * 16) / dg}
         env.close()
-    print(json.dumps({"vehicle": a.vehicle, "task": a.task, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
+    print(json.dumps({"vehicle": a.vehicle, "task": a.task, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
