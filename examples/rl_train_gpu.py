@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--sensor-noise", type=float, nargs=4, default=None, metavar=("P", "V", "W", "A"),
                     help="sensor noise on the observations: standard deviations of position (m), velocity (m/s), body rate (rad/s) and attitude (rad) "
                          "(fp32 rigid vehicles; DESIGN 4l)")
+    ap.add_argument("--action-delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="per-episode actuation latency: each env applies the action it was given MIN..MAX control steps of 5 ms ago (0..8; "
+                         "fp32 rigid vehicles; DESIGN 4m)")
     ap.add_argument("--log-json", default=None, help="write the learning curve (one record per iteration) and the final evaluation to this file")
     ap.add_argument("--warm-start-pid", type=int, default=None, metavar="DAGGER_ROUNDS",
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
@@ -72,6 +75,8 @@ def main():
         env.set_rotor_lag(amd.RotorLag(a.rotor_lag))
     if a.sensor_noise is not None:
         env.set_sensor_noise(amd.SensorNoise(*a.sensor_noise))
+    if a.action_delay is not None:
+        env.set_action_delay(amd.ActionDelay(*a.action_delay))
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,

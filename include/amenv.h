@@ -35,6 +35,7 @@ extern "C" {
 #define AMENV_MAX_ROTORS 8
 #define AMENV_MAX_WAYPOINTS 4
 #define AMENV_MAX_JOINTS 3
+#define AMENV_MAX_ACTION_DELAY 8   /* control steps: 40 ms at 200 Hz (amenv_set_action_delay) */
 
 /* error codes */
 #define AMENV_OK 0
@@ -472,6 +473,41 @@ typedef struct amenv_sensor_noise {
 int amenv_set_sensor_noise(amenv* env, const amenv_sensor_noise* z);
 /* out [N, 12] f32 (device): the twelve unit samples n_0 .. n_11 of every env's current (episode, step), whether the noise is on or off. */
 int amenv_sensor_noise_samples(amenv* env, float* out, void* stream);
+
+/* ---- per-episode actuation latency ---------------------------------------------------------------------------
+ * Opt-in, per handle, off by default.  Each env has an integer delay d, drawn when its episode starts and fixed for that episode, and a
+ * history of the last 8 action rows it was GIVEN (4 floats each, the caller's row as passed; in amenv_rollout_policy[_norm] the clipped
+ * sample).  A step with given row a applies a if d = 0, else the row given d steps ago, to the dynamics (fp32 action scaling, mixer, clamp,
+ * lag filter, thrust factors: all unchanged and in the same order); then a enters the history.  Where the episode is younger than d steps
+ * the applied row is the hover row (1, 0, 0, 0).  Nothing else changes: reward, task, observation (neither d nor the pending rows are
+ * observed), reset draws, Monitor totals, amenv_dims, the state layout, amenv_get_state / amenv_set_state; `actions` and `logp` of the
+ * closed loop record the policy's own samples.
+ *   draw    one Philox4x32-10 block, key = seed, counter = (gid lo, gid hi, episode, 0x4C540000), episode = AMENV_I_EPISODE while that
+ *           episode runs;  d = min_steps + (((w0 >> 16) * (max_steps - min_steps + 1)) >> 16)   (integer arithmetic only)
+ *   start   an auto-reset inside a step or rollout, and amenv_reset for the masked envs: d is drawn for the new episode number and all 8
+ *           history rows become hover.  With auto-reset off a finished env keeps both.
+ *   on/off  off -> on: every env draws d for its current episode and gets hover rows.  A new range on a handle where it is on keeps every
+ *           env's d and history and applies to the episodes that start afterwards.  amenv_set_state does not touch d or the history
+ *           (their order does not depend on the step field); amenv_set_seed re-keys the draws of later episodes only.
+ * Served: fp32 handles of what amenv_set_randomization serves (rigid vehicles with 4 or 6 rotors, every task, lane and helper-wave step
+ * kernels, amenv_rollout, amenv_rollout_policy[_norm] in the one-lane-per-env form), composable with randomisation, rotor lag and sensor
+ * noise in every combination.
+ * Refused with AMENV_ERR_INVALID, the handle untouched: a bad struct_size, min_steps < 0, min_steps > max_steps, max_steps >
+ * AMENV_MAX_ACTION_DELAY, arm vehicles, other rotor counts, fp64 handles, a handle whose step kernel is the lane-quad one.
+ * A configuration call like amenv_set_rotor_lag: the first enable allocates the side buffer (132 B per env) and off -> on synchronises;
+ * not to be called inside a stream capture. */
+typedef struct amenv_action_delay {
+  uint32_t struct_size;            /* = sizeof(amenv_action_delay): guard */
+  int32_t min_steps, max_steps;    /* control steps, 0 <= min_steps <= max_steps <= AMENV_MAX_ACTION_DELAY */
+} amenv_action_delay;
+/* z NULL = off: the handle launches exactly the kernels it launched before. */
+int amenv_set_action_delay(amenv* env, const amenv_action_delay* z);
+/* d_out [N] int32, recent_out [N, 8, 4] f32 in AGE order (row k was given k + 1 steps ago; hover where the episode is younger), device
+ * pointers, recent_out 16-byte aligned; either may be NULL.  Only enqueues.  Refused while the delay is off. */
+int amenv_get_action_delay_state(amenv* env, int32_t* d_out, float* recent_out, void* stream);
+/* the inverse: checkpoint / restore, parity injection; either may be NULL (that part stays).  d is clamped to 0..8 by the kernel (the
+ * pointers are device memory: the host cannot check them).  Only enqueues.  Refused while the delay is off. */
+int amenv_set_action_delay_state(amenv* env, const int32_t* d_in, const float* recent_in, void* stream);
 
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under

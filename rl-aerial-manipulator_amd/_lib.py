@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMENV_LIB") or os.path.join(HERE, "libamenv.so")
 
 MAX_ROTORS, MAX_WAYPOINTS, MAX_JOINTS = 8, 4, 3
+MAX_ACTION_DELAY = 8
 ABI_VERSION = 2
 F32, F64 = 0, 1
 FLAG_AUTO_RESET, FLAG_NAN_GUARD = 1, 2
@@ -80,6 +81,10 @@ class SensorNoiseC(C.Structure):
                 ("sigma_attitude", C.c_float)]
 
 
+class ActionDelayC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_steps", C.c_int32), ("max_steps", C.c_int32)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -103,6 +108,9 @@ SYMBOLS = {
     "amenv_set_rotor_state": (C.c_int, [_P, _P, _P]),
     "amenv_set_sensor_noise": (C.c_int, [_P, C.POINTER(SensorNoiseC)]),
     "amenv_sensor_noise_samples": (C.c_int, [_P, _P, _P]),
+    "amenv_set_action_delay": (C.c_int, [_P, C.POINTER(ActionDelayC)]),
+    "amenv_get_action_delay_state": (C.c_int, [_P, _P, _P, _P]),
+    "amenv_set_action_delay_state": (C.c_int, [_P, _P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

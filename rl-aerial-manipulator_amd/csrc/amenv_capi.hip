@@ -69,6 +69,9 @@ struct amenv {
   bool noise = false;              // amenv_set_sensor_noise: sensor noise on the observation rows
   NoiseSig noise_s = {0.0f, 0.0f, 0.0f, 0.0f};   // its standard deviations: position, velocity, body rate, attitude
   void* lag_w = nullptr;           // [n_tiles][n_rotors][64] rotor states | [n_rotors] w0, of the handle's dtype; allocated when the lag is first enabled
+  bool delay = false;              // amenv_set_action_delay: per-episode actuation latency on
+  int32_t delay_lo = 0, delay_hi = 0;   // its range of control steps, for the episodes that start from now on
+  void* delay_h = nullptr;         // float4 [n_tiles][8][64] given rows | int32 [n_tiles * 64] d | head << 4; allocated when the delay is first enabled
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
   std::string kname;
@@ -333,10 +336,20 @@ template <typename T, int NROT> LagArg<T, NROT, true> make_lag(const amenv& e) {
   L.a_up = T(e.lag_a[0]); L.a_down = T(e.lag_a[1]);
   return L;
 }
+DelayArg<true> make_delay(const amenv& e) {
+  DelayArg<true> D;
+  D.h = static_cast<float4*>(e.delay_h); D.n_pad = uint32_t(e.n_tiles) * 64u;
+  D.lo = e.delay_lo; D.span = e.delay_hi - e.delay_lo + 1;
+  return D;
+}
 // the kernels' last argument: the randomisation ranges, behind them the lag block in the LAG instantiations, behind that the sensor
-// noise's sigmas in the NOISE ones
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false> DynArg<T, NROT, DR, LAG, NOISE> make_dyn(const amenv& e) {
-  if constexpr (LAG && NOISE) return DynArg<T, NROT, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}};
+// noise's sigmas in the NOISE ones, behind those the actuation latency's fields in the DELAY ones
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false, bool DELAY = false> DynArg<T, NROT, DR, LAG, NOISE, DELAY> make_dyn(const amenv& e) {
+  if constexpr (DELAY && LAG && NOISE) return DynArg<T, NROT, true, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}, make_delay(e)};
+  else if constexpr (DELAY && NOISE) return DynArg<T, NROT, true, false, true, true>{make_dr<true>(e), NoiseArg<true>{e.noise_s}, make_delay(e)};
+  else if constexpr (DELAY && LAG) return DynArg<T, NROT, true, true, false, true>{make_dr<true>(e), make_lag<T, NROT>(e), make_delay(e)};
+  else if constexpr (DELAY) return DynArg<T, NROT, true, false, false, true>{make_dr<true>(e), make_delay(e)};
+  else if constexpr (LAG && NOISE) return DynArg<T, NROT, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}};
   else if constexpr (NOISE) return DynArg<T, NROT, true, false, true>{make_dr<true>(e), NoiseArg<true>{e.noise_s}};
   else if constexpr (LAG) return DynArg<T, NROT, true, true>{make_dr<true>(e), make_lag<T, NROT>(e)};
   else return DynArg<T, NROT, DR, false>{make_dr<DR>(e)};
@@ -477,6 +490,7 @@ std::string kernel_name(const amenv& e) {
   if (e.dr) name += " +dr";
   if (e.lag) name += " +lag";
   if (e.noise) name += " +noise";
+  if (e.delay) name += " +delay";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -491,7 +505,7 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 
 // amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
 // runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG, bool NOISE>
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG, bool NOISE, bool DELAY>
 hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const ColdParams C = make_cold(e);
@@ -514,15 +528,15 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG, NOISE>(e));
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
 }
 
 // amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
 // if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false, bool NOISE = false>
+template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>(e, io, T_steps, s);
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
@@ -565,24 +579,30 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
         const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG, NOISE>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
-                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG, NOISE>(e));
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG, NOISE, DELAY>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
+                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG, NOISE>(e));
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
     }
   }
   return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
-template <typename T, int NROT, bool DR = false, bool LAG = false, bool NOISE = false>
+template <typename T, int NROT, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 hipError_t dispatch_k(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);
-  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG, NOISE>(e, io, T_steps, s, timed);
+  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
+  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);
+  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);
+}
+// amenv_set_action_delay admits fp32 handles of what amenv_set_randomization admits; the DELAY kernels are DR ones, for all four (LAG, NOISE) pairs
+template <typename T, int NROT>
+hipError_t dispatch_delay(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
+  if (e.lag) return e.noise ? dispatch_k<T, NROT, true, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, NROT, true, true, false, true>(e, io, T_steps, s, timed);
+  return e.noise ? dispatch_k<T, NROT, true, false, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, NROT, true, false, false, true>(e, io, T_steps, s, timed);
 }
 
 template <typename T>
@@ -593,6 +613,11 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
   }
   if constexpr (sizeof(T) == 4) {
+    if (e.delay) {
+      if (nr == 4) return dispatch_delay<T, 4>(e, io, T_steps, s, timed);
+      if (nr == 6) return dispatch_delay<T, 6>(e, io, T_steps, s, timed);
+      return hipErrorInvalidValue;
+    }
     if (e.noise) {   // amenv_set_sensor_noise admits fp32 handles of what amenv_set_randomization admits; the NOISE kernels are DR ones, with or without LAG
       if (nr == 4) return e.lag ? dispatch_k<T, 4, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 4, true, false, true>(e, io, T_steps, s, timed);
       if (nr == 6) return e.lag ? dispatch_k<T, 6, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 6, true, false, true>(e, io, T_steps, s, timed);
@@ -651,32 +676,36 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifndef AMENV_RIGID_WG64_MAX
 #define AMENV_RIGID_WG64_MAX 24576
 #endif
-template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG, bool NOISE>
+template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG, bool NOISE, bool DELAY>
 hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
   const ColdParams C = make_cold(e);
-  const DynArg<float, NROT, DR, LAG, NOISE> R = make_dyn<float, NROT, DR, LAG, NOISE>(e);
+  const DynArg<float, NROT, DR, LAG, NOISE, DELAY> R = make_dyn<float, NROT, DR, LAG, NOISE, DELAY>(e);
   const int n = e.cfg.num_envs;
   if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG, NOISE>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG, NOISE>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG, NOISE>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   return hipGetLastError();
 }
-template <bool NORM, bool DR, bool LAG = false, bool NOISE = false>
+template <bool NORM, bool DR, bool LAG = false, bool NOISE = false, bool DELAY = false>
 hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const bool four = e.cfg.vehicle.n_rotors == 4;
   if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
-    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG, NOISE>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG, NOISE>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
   if (e.cfg.task.num_waypoints == 1)
-    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s);
-  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s)
-              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE>(e, T, io, N, s);
+    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
+  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s)
+              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
+  if (e.delay) {   // (all four (LAG, NOISE) pairs)
+    if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true, true>(e, T, io, N, s);
+    return e.lag ? launch_rigid_policy_dr<NORM, true, true, false, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, false, true>(e, T, io, N, s);
+  }
   if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true>(e, T, io, N, s);
   if (e.lag) return launch_rigid_policy_dr<NORM, true, true>(e, T, io, N, s);   // (unit ranges when randomisation is off)
   return e.dr ? launch_rigid_policy_dr<NORM, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, false>(e, T, io, N, s);
@@ -741,6 +770,46 @@ hipError_t launch_lag_transpose(const amenv& e, void* api, int to_api, hipStream
   const int n = e.cfg.num_envs;
   hipLaunchKernelGGL(lag_transpose_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, int(e.cfg.vehicle.n_rotors), static_cast<T*>(e.lag_w),
                      static_cast<T*>(api), to_api);
+  return hipGetLastError();
+}
+
+// amenv_set_action_delay (off -> on) / amenv_reset: the masked envs (mask null = all; padding lanes always, as reset_kernel does) draw d for
+// the episode the blob holds by now and get 8 hover rows
+__global__ void delay_reset_kernel(int n, uint32_t tile_bytes, const void* __restrict__ blob, const ColdParams C, const DelayArg<true> D, const uint8_t* __restrict__ mask) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= int(D.n_pad)) return;
+  if (i < n && mask && !mask[i]) return;
+  const int32_t episode = iptr4(const_cast<char*>(tile_base(blob, tile_bytes, i)), i & 63)->w;
+  DelayLane dl{delay_draw(C.seed_lo, C.seed_hi, D, C.gid0 + i, episode), 0};
+  delay_push(D, i, dl, make_float4(1.0f, 0.0f, 0.0f, 0.0f), true);
+}
+// amenv_get_action_delay_state (to_api) / amenv_set_action_delay_state: d [N], rows [N][8][4] in AGE order (row k was given k + 1 steps ago)
+// <-> the side buffer's ring.  The setter restarts the ring at head 0 and clamps d to 0..8.
+__global__ void delay_state_kernel(int n, const DelayArg<true> D, int32_t* __restrict__ d_api, float4* __restrict__ rows_api, int to_api) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  float4* p = D.h + delay_slot(i);
+  int32_t* w = delay_word(D) + i;
+  if (to_api) {
+    const int32_t m = *w;
+    const int head = (m >> 4) & 7;
+    if (d_api) d_api[i] = m & 15;
+    if (rows_api)
+      for (int k = 0; k < AMENV_MAX_ACTION_DELAY; k++) rows_api[size_t(i) * AMENV_MAX_ACTION_DELAY + k] = p[64 * ((head - 1 - k) & 7)];
+  } else {
+    const int32_t m = *w;
+    int d = m & 15;
+    if (d_api) d = min(max(d_api[i], 0), AMENV_MAX_ACTION_DELAY);
+    if (rows_api) {
+      for (int k = 0; k < AMENV_MAX_ACTION_DELAY; k++) p[64 * ((-1 - k) & 7)] = rows_api[size_t(i) * AMENV_MAX_ACTION_DELAY + k];
+      *w = d;                   // head 0
+    } else {
+      *w = d | (m & 0x70);      // the ring stays as it is
+    }
+  }
+}
+hipError_t launch_delay_reset(const amenv& e, const uint8_t* mask, hipStream_t s) {
+  hipLaunchKernelGGL(delay_reset_kernel, dim3(e.n_tiles / 4), dim3(256), 0, s, e.cfg.num_envs, e.tile_bytes, (const void*)e.blob, make_cold(e), make_delay(e), mask);
   return hipGetLastError();
 }
 
@@ -994,6 +1063,7 @@ int amenv_destroy(amenv* e) {
     if (e->team_consts) (void)hipFree(e->team_consts);
     if (e->pol_pack) (void)hipFree(e->pol_pack);
     if (e->lag_w) (void)hipFree(e->lag_w);
+    if (e->delay_h) (void)hipFree(e->delay_h);
     if (e->io_act) (void)hipFree(e->io_act);
     if (e->io_obs) (void)hipFree(e->io_obs);
     if (e->io_term) (void)hipFree(e->io_term);
@@ -1156,6 +1226,67 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   return AMENV_OK;
 }
 
+int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!z) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused)
+    e->delay = false;
+    e->kname = kernel_name(*e);
+    return AMENV_OK;
+  }
+  const amenv_vehicle& v = e->cfg.vehicle;
+  if (z->struct_size != sizeof(amenv_action_delay)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: struct_size must be sizeof(amenv_action_delay)");
+  if (z->min_steps < 0 || z->min_steps > z->max_steps || z->max_steps > AMENV_MAX_ACTION_DELAY)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: need 0 <= min_steps <= max_steps <= AMENV_MAX_ACTION_DELAY (8)");
+  if (v.n_joints > 0 || e->pub_nj > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: built for rigid vehicles (the arm kernels are not built with it)");
+  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: built for rigid vehicles with 4 or 6 rotors");
+  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: fp32 handles only (the fp64 builds are logic gates of the dynamics)");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  DeviceGuard g(e->device);
+  if (!e->delay_h) {   // first enable: the one allocation
+    const size_t n_pad = size_t(e->n_tiles) * 64;
+    void* buf = nullptr;
+    hipError_t st = hipMalloc(&buf, n_pad * (AMENV_MAX_ACTION_DELAY * sizeof(float4) + sizeof(int32_t)));
+    if (st != hipSuccess) return fail(e, AMENV_ERR_ALLOC, std::string("amenv_set_action_delay: hipMalloc: ") + hipGetErrorString(st));
+    e->delay_h = buf;
+  }
+  const bool was_on = e->delay;
+  e->delay_lo = z->min_steps; e->delay_hi = z->max_steps;
+  e->delay = true;
+  e->kname = kernel_name(*e);
+  if (!was_on) {     // off -> on: every env draws d for its current episode and gets hover rows; on -> on keeps d and the rows (curricula)
+    AMENV_HIP(e, launch_delay_reset(*e, nullptr, nullptr));
+    AMENV_HIP(e, hipDeviceSynchronize());
+  }
+  return AMENV_OK;
+}
+
+int amenv_get_action_delay_state(amenv* e, int32_t* d_out, float* recent_out, void* stream) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!d_out && !recent_out) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: NULL arguments");
+  if (!e->delay) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: the action delay is off (amenv_set_action_delay)");
+  if (recent_out && !aligned16(recent_out)) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: recent_out must be 16-byte aligned");
+  DeviceGuard g(e->device);
+  const int n = e->cfg.num_envs;
+  hipLaunchKernelGGL(delay_state_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, make_delay(*e), d_out, reinterpret_cast<float4*>(recent_out), 1);
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
+int amenv_set_action_delay_state(amenv* e, const int32_t* d_in, const float* recent_in, void* stream) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!d_in && !recent_in) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: NULL arguments");
+  if (!e->delay) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: the action delay is off (amenv_set_action_delay)");
+  if (recent_in && !aligned16(recent_in)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: recent_in must be 16-byte aligned");
+  DeviceGuard g(e->device);
+  const int n = e->cfg.num_envs;
+  hipLaunchKernelGGL(delay_state_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, make_delay(*e), const_cast<int32_t*>(d_in),
+                     reinterpret_cast<float4*>(const_cast<float*>(recent_in)), 0);
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
 int amenv_get_rotor_state(amenv* e, void* out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   if (!out) return fail(e, AMENV_ERR_INVALID, "amenv_get_rotor_state: NULL argument");
@@ -1183,6 +1314,7 @@ int amenv_reset(amenv* e, const uint8_t* mask, float* obs_out, void* stream) {
   float* o = (e->io_obs && obs_out) ? e->io_obs : obs_out;
   AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_reset<double>(*e, mask, o, 0, s) : launch_reset<float>(*e, mask, o, 0, s));
   if (e->lag) AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, mask, s) : launch_lag_reset<float>(*e, mask, s));
+  if (e->delay) AMENV_HIP(e, launch_delay_reset(*e, mask, s));
   if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
   return AMENV_OK;
 }
@@ -1263,7 +1395,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && !e->lag && !e->noise && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");

@@ -401,14 +401,17 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 // DR: per-episode dynamics randomisation, rigid vehicles only; the factors are drawn once per launch from the loaded episode.
 // LAG: first-order rotor lag, built together with DR only; the rotor states are loaded from and stored to the handle's side buffer.
 // NOISE: sensor noise on the observation rows, built together with DR only, fp32 only.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false>
+// DELAY: per-episode actuation latency, built together with DR only, fp32 only; the row given d steps ago is loaded from the
+// handle's side buffer in place of the given one, which enters the buffer after the step.
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE> DA) {
+                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
+  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -428,9 +431,11 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   LagLane<T, NROT, LAG> lg;
   if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);   // (padding lanes own valid slots of the side buffer as of the blob)
   float act[AD];
+  DelayLane dl; float4 given;
   if constexpr (NJ == 0) {
     const float4 a = io.actions[min(i, hd.n - 1)];  // padding lanes re-read the last env's action: no exec branch in the prologue
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
+    if constexpr (DELAY) { given = a; delay_apply(DA.D, i, dl, act); }
   } else {
     const float* ap = reinterpret_cast<const float*>(io.actions) + size_t(min(i, hd.n - 1)) * AD;   // 28-B rows: dword loads
 #pragma unroll
@@ -450,6 +455,7 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   store_env_step<T, KW, NJ>(tile, lane, e, K);
   if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
   if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
+  if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
   if (active) {
     reinterpret_cast<T*>(io.reward)[i] = reward;
     io.done[i] = is_done ? 1 : 0;
@@ -503,13 +509,17 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 // NOISE: every wave that forms a row perturbs a copy of the state first -- the observation wave with the step key it forms itself
 // (loaded step + 1: it does not run the task step, which increments exactly once on the single-waypoint v2 task), the reset wave its
 // (episode + 1, step 0) row, the main wave of the 128-thread form inside step_lane.  Nothing is added to the integrating wave of the 256-thread form.
-template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false, bool NOISE = false>
+// DELAY: the waves that integrate load the same delayed row before the barrier; the main wave alone stores, after it.  In the
+// 256-thread form the reset wave draws the next episode's d for every lane and leaves it in LDS (no Philox on the main wave); in the
+// 128-thread form the main wave draws it on its episode-end path.
+template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                      const DynArg<T, NROT, DR, LAG, NOISE> DA) {
+                                                      const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
+  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, 0>::value;
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
@@ -539,6 +549,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     // [64] bit 0: episode ended on a real env, bit 1: the lane is reset | [64] info bits | [64] length | [64] return | [4][64] reset position, final yaw
     uint32_t* flag = words;
     float* rst = reinterpret_cast<float*>(words + 256);
+    uint32_t* next_d = words + 576;   // [64] DELAY: the next episode's d of every lane (behind the Monitor wave's sums at 512..529)
     if (role == 3) {                 // Monitor wave: owns totals replica [tile] during this launch -- loads it now, no atomics later
       unsigned long long* totals = io.stats + size_t(blockIdx.x & (kStatsReplicas - 1)) * kStatsStride;
       unsigned long long* acc = reinterpret_cast<unsigned long long*>(words + 512);   // [S_COUNT] this launch's additions (LDS)
@@ -581,6 +592,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
         observe_reset<T, KW, false, 0>(er, false, ro);
       }
       rst[lane] = float(er.px); rst[64 + lane] = float(er.py); rst[128 + lane] = float(er.pz); rst[192 + lane] = float(er.final_yaw);
+      if constexpr (DELAY) next_d[lane] = uint32_t(delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, er.episode));   // (er.episode: the new episode's number)
       AMENV_STAMP(2); AMENV_STAMP(3);
       __syncthreads();               // flags published (and this wave's reset positions)
       AMENV_STAMP(4);
@@ -607,6 +619,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
+    DelayLane dl;
+    if constexpr (DELAY) delay_apply(DA.D, i, dl, act);
     if (role == 2) {
 #ifdef AMENV_STAMPS
       AMENV_STAMP_DRAIN();
@@ -664,9 +678,11 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       e.last_distance = T(-1); e.ep_return = T(0);
       e.step = 0; e.counter = 0; e.flags = 0; e.episode += 1;
       if constexpr (LAG) lag_restart<T, NROT>(DA.L, lg);
+      if constexpr (DELAY) dl.d = int(next_d[lane]);
     }
     store_env_step<T, KW>(tile, lane, e);
     if constexpr (LAG) lag_store<T, NROT>(DA.L, i, lg);   // (the observation wave loaded its copy before the barrier)
+    if constexpr (DELAY) delay_push(DA.D, i, dl, a, was_reset);   // (likewise: it used its row before the barrier)
     if (active) {
       reinterpret_cast<T*>(io.reward)[i] = reward;
       io.done[i] = is_done ? 1 : 0;
@@ -699,6 +715,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
+    DelayLane dl;
+    if constexpr (DELAY) delay_apply(DA.D, i, dl, act);
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
     uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false,
                                                                                     was_reset, ep_len, ep_ret, x, df, &lg, noise_of(DA));
@@ -707,6 +725,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     store_env_step<T, KW>(tile, lane, e);
     if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
+    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, a, was_reset); }
     if (active) {
       reinterpret_cast<T*>(io.reward)[i] = reward;
       io.done[i] = is_done ? 1 : 0;
@@ -904,14 +923,16 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
 // DR: factors drawn at entry and again for a lane after its auto-reset.
 // LAG: the rotor states stay in registers over the steps, restart at w0 after an auto-reset and are stored once at the end.
 // NOISE: every row is formed from a perturbed copy of the state, as in step_kernel.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false>
+// DELAY: every step goes through the side buffer as in step_kernel (its own word and slots: a lane's accesses are in order).
+template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, int n_steps, const StepTail tl, const HotParams<T, NROT> P,
-                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE> DA) {
+                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
   static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
+  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, nullptr, nullptr, nullptr, tl.stats};
@@ -935,9 +956,13 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   StepIO io_t = io; io_t.terminal_obs = nullptr; io_t.ep_return = nullptr; io_t.ep_len = nullptr;
   for (int t = 0; t < n_steps; t++) {
     float act[AD];
+    DelayLane dl; float4 given;
     {
       const float* ap = reinterpret_cast<const float*>(io.actions) + (size_t(t) * n + min(i, hd.n - 1)) * AD;
-      if constexpr (NJ == 0) { const float4 a = *reinterpret_cast<const float4*>(ap); act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w; }
+      if constexpr (NJ == 0) {
+        const float4 a = *reinterpret_cast<const float4*>(ap); act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
+        if constexpr (DELAY) { given = a; delay_apply(DA.D, i, dl, act); }
+      }
       else {
 #pragma unroll
         for (int j = 0; j < AD; j++) act[j] = ap[j];
@@ -948,6 +973,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
                                                                         ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
     if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); }
+    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);

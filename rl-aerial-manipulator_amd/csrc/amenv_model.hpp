@@ -205,13 +205,31 @@ template <int NE> struct NoiseLds {
   NoiseSig s; float* col;
   __device__ __forceinline__ float* column() const { return col; }
 };
-// The one kernel argument that carries the switches: DrArg's bytes unless LAG or NOISE (the kernels without them keep their argument segment).
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false> struct DynArg { DrArg<DR> R; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, false> { DrArg<true> R; LagArg<T, NROT, true> L; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, false, true> { DrArg<true> R; NoiseArg<true> Z; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; };
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE>
-__host__ __device__ __forceinline__ NoiseArg<NOISE> noise_of(const DynArg<T, NROT, DR, LAG, NOISE>& a) {
+// ---- per-episode actuation latency (include/amenv.h amenv_set_action_delay) ---------------------------------------
+// Each env applies the action row it was given d control steps ago, d drawn per episode from [lo, lo + span - 1].  The last 8 given rows
+// live in a side buffer of the handle, tiled like the lag's: float4 [n_pad / 64][8 slots][64 envs] (a lane moves a whole row with one
+// dword x4 access, a wave 1 KiB), and behind them one word per env, int32 [n_pad]: d | head << 4.  The ring is ordered by a head index of its
+// own (the slot the next given row goes to), never by the env's step field: the row given k + 1 steps ago sits in slot (head - 1 - k) & 7.
+// The fields travel behind the noise's in the DELAY instantiations only.  DELAY is built only together with DR, fp32 only.
+template <bool DELAY> struct DelayArg { static constexpr bool on = false; };
+template <> struct DelayArg<true> {
+  static constexpr bool on = true;
+  float4* h;           // [n_pad / 64][8][64] given rows | int32 [n_pad] d | head << 4
+  uint32_t n_pad;      // the handle's padded env count (whole tiles)
+  int32_t lo, span;    // min_steps, max_steps - min_steps + 1
+};
+struct DelayLane { int d, head; };
+// The one kernel argument that carries the switches: DrArg's bytes unless LAG, NOISE or DELAY (the kernels without them keep their argument segment).
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false, bool DELAY = false> struct DynArg { DrArg<DR> R; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, false, false> { DrArg<true> R; LagArg<T, NROT, true> L; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, false, true, false> { DrArg<true> R; NoiseArg<true> Z; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, true, false> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, false, false, true> { DrArg<true> R; DelayArg<true> D; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, false, true> { DrArg<true> R; LagArg<T, NROT, true> L; DelayArg<true> D; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, false, true, true> { DrArg<true> R; NoiseArg<true> Z; DelayArg<true> D; };
+template <typename T, int NROT> struct DynArg<T, NROT, true, true, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; DelayArg<true> D; };
+template <typename T, int NROT, bool DR, bool LAG, bool NOISE, bool DELAY>
+__host__ __device__ __forceinline__ NoiseArg<NOISE> noise_of(const DynArg<T, NROT, DR, LAG, NOISE, DELAY>& a) {
   if constexpr (NOISE) return a.Z; else return NoiseArg<false>{};
 }
 // env i's rotor r sits at lag_slot(i) + 64 r
@@ -645,6 +663,40 @@ __device__ __forceinline__ void sensor_perturb(uint32_t seed_lo, uint32_t seed_h
 }
 // What the cold, host-launched kernels (reset, observe) take: a wave-uniform switch, the sigmas and the key's seed / first global id.
 struct NoiseRt { NoiseSig s; uint32_t seed_lo, seed_hi; int64_t gid0; int32_t on; };
+
+// ---- actuation latency: the draw, and the two accesses of a step -------------------------------------------------------------
+constexpr uint32_t kDelayBlock = 0x4C540000u;   // counter word 3 of the d draw ("LT"; resets use 0..4, randomisation 0x4452...., noise 0x4E......)
+// env i's slot k sits at delay_slot(i) + 64 k (float4 units); its word at delay_word(D)[i]
+__device__ __forceinline__ size_t delay_slot(int i) { return size_t(i >> 6) * (AMENV_MAX_ACTION_DELAY * 64) + size_t(i & 63); }
+__device__ __forceinline__ int32_t* delay_word(const DelayArg<true>& D) { return reinterpret_cast<int32_t*>(D.h + size_t(D.n_pad) * AMENV_MAX_ACTION_DELAY); }
+// d of (env, episode): one Philox block, integer arithmetic only (w0's top 16 bits times the range's width, <= 9: no overflow)
+__device__ __forceinline__ int delay_draw(uint32_t seed_lo, uint32_t seed_hi, const DelayArg<true>& D, int64_t gid, int32_t episode) {
+  uint32_t w[4];
+  philox4x32_10(seed_lo, seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), kDelayBlock, w);
+  return D.lo + int(((w[0] >> 16) * uint32_t(D.span)) >> 16);
+}
+// Before dynamics(): the env's word, then ONE slot -- the row given d steps ago, which replaces the given row unless d = 0 (the load is
+// unconditional: with d = 0 it reads the slot the given row is about to enter; padding lanes own valid slots as of the blob).
+__device__ __forceinline__ void delay_apply(const DelayArg<true>& D, int i, DelayLane& dl, float* act) {
+  const int32_t m = delay_word(D)[i];
+  dl.d = m & 15; dl.head = (m >> 4) & 7;
+  const float4 r = D.h[delay_slot(i) + 64 * ((dl.head - dl.d) & 7)];
+  if (dl.d != 0) { act[0] = r.x; act[1] = r.y; act[2] = r.z; act[3] = r.w; }
+}
+// After the step: the given row enters the history (ONE slot), or, where a new episode starts (the caller has put its d into dl), all 8
+// slots become the hover row; then the word.
+__device__ __forceinline__ void delay_push(const DelayArg<true>& D, int i, DelayLane& dl, const float4 given, bool was_reset) {
+  float4* p = D.h + delay_slot(i);
+  if (was_reset) {
+#pragma unroll
+    for (int k = 0; k < AMENV_MAX_ACTION_DELAY; k++) p[64 * k] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    dl.head = 0;
+  } else {
+    p[64 * dl.head] = given;
+    dl.head = (dl.head + 1) & 7;
+  }
+  delay_word(D)[i] = dl.d | (dl.head << 4);
+}
 
 // WaypointQuadEnv.reset (rl_env_scaledObs.py:40-79) with the DESIGN.md draw table.  All draws
 // are formed in fp32 with explicit fmaf so the CPU oracle reproduces them bit for bit.

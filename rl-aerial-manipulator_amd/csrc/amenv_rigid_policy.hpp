@@ -38,13 +38,17 @@ struct NormArg {
 // NOISE: sensor noise: row 0 and every later row are formed from a perturbed copy of the state; the noise comes first and the
 // normaliser second (the frozen statistics normalise the noisy row, the `update` sums count the noisy raw rows).  In the NORM forms the
 // perturbed copy is staged through LDS (13 x NE floats, every lane its own column: NoiseLds).
-template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false, bool NOISE = false>
+// DELAY: per-episode actuation latency: the clipped sample is the GIVEN row; the row given d steps ago is applied.  Nothing of the
+// history is held in registers over a step: the env's word and one slot are loaded from the handle's (L2-resident) side buffer in front of
+// the dynamics, one slot and the word are stored behind them.  `actions` and `logp` record the policy's own samples.
+template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
                                                                                          const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
-                                                                                         const DynArg<float, NROT, DR, LAG, NOISE> DA) {
+                                                                                         const DynArg<float, NROT, DR, LAG, NOISE, DELAY> DA) {
   static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
   static_assert(!NOISE || DR, "sensor noise is built together with the randomisation switch");
+  static_assert(!DELAY || DR, "the actuation latency is built together with the randomisation switch");
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -254,6 +258,8 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
       *reinterpret_cast<float4*>(io.actions + (tn + i) * AD) = make_float4(raw[0], raw[1], raw[2], raw[3]);
       io.logp[tn + i] = logp; io.values[tn + i] = value;
     }
+    DelayLane dl; float4 given;
+    if constexpr (DELAY) { given = make_float4(act[0], act[1], act[2], act[3]); delay_apply(DA.D, i, dl, act); }
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
     sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
@@ -274,6 +280,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
         lg.put(dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode));
       }
     }
+    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, gid, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);

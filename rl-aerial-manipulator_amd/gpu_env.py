@@ -33,13 +33,16 @@ class GpuWaypointEnv:
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
                  rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
-                 sensor_noise=None):
+                 sensor_noise=None, action_delay=None):
+        from .action_delay import ActionDelay
         from .rotor_lag import RotorLag
         from .sensor_noise import SensorNoise
         if rotor_lag is not None and not isinstance(rotor_lag, RotorLag):   # before any device is touched
             raise L.AmenvError(f"rotor_lag: expected a RotorLag or None, got {type(rotor_lag).__name__}")
         if sensor_noise is not None and not isinstance(sensor_noise, SensorNoise):
             raise L.AmenvError(f"sensor_noise: expected a SensorNoise or None, got {type(sensor_noise).__name__}")
+        if action_delay is not None and not isinstance(action_delay, ActionDelay):
+            raise L.AmenvError(f"action_delay: expected an ActionDelay or None, got {type(action_delay).__name__}")
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -99,6 +102,9 @@ class GpuWaypointEnv:
         self.sensor_noise = None
         if sensor_noise is not None:
             self.set_sensor_noise(sensor_noise)
+        self.action_delay = None
+        if action_delay is not None:
+            self.set_action_delay(action_delay)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -183,6 +189,41 @@ class GpuWaypointEnv:
         out = torch.empty(self.num_envs, 12, dtype=torch.float32, device=self.device)
         self._check(self.lib.amenv_sensor_noise_samples(self._h, C.c_void_p(out.data_ptr()), self._stream()), "amenv_sensor_noise_samples")
         return out
+
+    def set_action_delay(self, delay):
+        """Per-episode actuation latency (an `ActionDelay`, or None = every action is applied in the step that receives it; fp32 rigid
+        vehicles with 4 or 6 rotors, not with kernel="team").  Turning it on draws every env's delay for its current episode and fills its
+        history with hover rows; a new range on an env where it is on keeps both and applies to the episodes that start afterwards.  A
+        configuration call: it may allocate and synchronise."""
+        from .action_delay import ActionDelay
+        if delay is not None and not isinstance(delay, ActionDelay):
+            raise L.AmenvError(f"set_action_delay: expected an ActionDelay or None, got {type(delay).__name__}")
+        c = None if delay is None else delay._as_c()
+        self._check(self.lib.amenv_set_action_delay(self._h, None if c is None else C.byref(c)), "amenv_set_action_delay")
+        self.action_delay = delay
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
+    def action_delay_state(self):
+        """(d [N] int32, recent [N, 8, 4] f32): every env's delay and the last 8 action rows it was given, in age order (recent[:, k] was
+        given k + 1 steps ago; the hover row where the episode is younger).  Needs the action delay on."""
+        d = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        recent = torch.empty(self.num_envs, L.MAX_ACTION_DELAY, 4, dtype=torch.float32, device=self.device)
+        self._check(self.lib.amenv_get_action_delay_state(self._h, C.c_void_p(d.data_ptr()), C.c_void_p(recent.data_ptr()), self._stream()),
+                    "amenv_get_action_delay_state")
+        return d, recent
+
+    def set_action_delay_state(self, d, recent):
+        """The inverse of action_delay_state(): checkpoint / restore, parity injection.  d outside 0..8 is clamped."""
+        n = self.num_envs
+        dt = torch.as_tensor(d).to(device=self.device, dtype=torch.int32).contiguous()
+        rt = torch.as_tensor(recent).to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(dt.shape) != (n,) or tuple(rt.shape) != (n, L.MAX_ACTION_DELAY, 4):
+            raise L.AmenvError(f"set_action_delay_state: expected shapes {(n,)} and {(n, L.MAX_ACTION_DELAY, 4)}, got {tuple(dt.shape)} and {tuple(rt.shape)}")
+        if rt.data_ptr() % 16:
+            rt = rt.clone()
+        self._check(self.lib.amenv_set_action_delay_state(self._h, C.c_void_p(dt.data_ptr()), C.c_void_p(rt.data_ptr()), self._stream()),
+                    "amenv_set_action_delay_state")
+        torch.cuda.current_stream(self.device).synchronize()   # the staging tensors stay alive until the copy has run
 
     def reset(self, mask=None):
         """WaypointQuadEnv.reset (v2/rl_env_scaledObs.py:40-79) for all envs, or those with mask != 0."""
