@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--action-delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
                     help="per-episode actuation latency: each env applies the action it was given MIN..MAX control steps of 5 ms ago (0..8; "
                          "fp32 rigid vehicles; DESIGN 4m)")
+    ap.add_argument("--action-history", type=int, default=None, metavar="H",
+                    help="append the last H (1 or 2) action rows each env was given to its observation rows: the commands still in flight under "
+                         "--action-delay / --rotor-lag (fp32 rigid vehicles; not with --normalize-obs --fused-rollout; DESIGN 4n)")
     ap.add_argument("--log-json", default=None, help="write the learning curve (one record per iteration) and the final evaluation to this file")
     ap.add_argument("--warm-start-pid", type=int, default=None, metavar="DAGGER_ROUNDS",
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
@@ -77,6 +80,8 @@ def main():
         env.set_sensor_noise(amd.SensorNoise(*a.sensor_noise))
     if a.action_delay is not None:
         env.set_action_delay(amd.ActionDelay(*a.action_delay))
+    if a.action_history is not None:
+        env.set_action_history(amd.ActionHistory(a.action_history))
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,

@@ -509,6 +509,40 @@ int amenv_get_action_delay_state(amenv* env, int32_t* d_out, float* recent_out, 
  * pointers are device memory: the host cannot check them).  Only enqueues.  Refused while the delay is off. */
 int amenv_set_action_delay_state(amenv* env, const int32_t* d_in, const float* recent_in, void* stream);
 
+/* ---- action history in the observation rows -------------------------------------------------------------------
+ * Opt-in, per handle, off by default; composes with randomisation, rotor lag, sensor noise and the action delay in every combination.
+ * While it is on with H = rows (1 or 2), every observation row the library publishes is the task's row followed by the last H action rows
+ * the env was GIVEN, most recent first: obs_dim = base + 4 H, base = 20 (v2 task) or 17 (v1 tasks).  Columns base + 4 k .. base + 4 k + 3
+ * hold the row given k + 1 steps ago in this episode, bit for bit as the caller passed it (in amenv_rollout_policy the clipped sample, as
+ * for the delay): raw values, thrust / (m g) in [0, 2] and moments in [-1, 1], not scaled, not perturbed by the sensor noise, not replaced
+ * by the applied row.  Where the episode is younger than k + 1 steps the columns hold the hover row (1, 0, 0, 0).  They are the first H rows
+ * of what amenv_get_action_delay_state publishes as recent_out, after the step's push.
+ *   step row of an env that goes on                   [a_t, a_{t-1}]
+ *   terminal row (written where done)                 [a_t, a_{t-1}]: the history before the reset wipes it
+ *   post-reset row of an auto-reset env,
+ *   amenv_reset row of a masked env                   hover rows
+ *   amenv_reset row of an unmasked env, amenv_observe the env's current history
+ *   rows of amenv_rollout / amenv_rollout_policy      as the same steps through amenv_step publish them (row 0 of the closed loop: the
+ *                                                     current history)
+ * The history IS the delay's side buffer.  With the delay off the delay machinery runs with range (0, 0): every d is 0, the applied row is
+ * the given row and the dynamics are bit-identical to a handle without either.  Turning the history on where neither was on allocates the
+ * buffer (a configuration call like amenv_set_action_delay: it may allocate and synchronise, not inside a stream capture) and fills it with
+ * hover rows; where the delay is on, the history shows the rows the delay has kept.  amenv_set_action_delay keeps its rules (off -> on draws
+ * d and fills hover rows, a new range keeps d and the rows); while the history is on, amenv_set_action_delay(NULL) means range (0, 0) for
+ * the episodes that start afterwards and the buffer stays.  amenv_get/set_action_delay_state work while either is on.
+ * Nothing else changes: reward, task, state layout, amenv_get_state / amenv_set_state, reset draws (nothing is drawn: sharding by global env
+ * id holds), Monitor totals, amenv_dims(cfg), amenv_bytes_per_env_step(cfg).
+ * Served: fp32 handles of what amenv_set_action_delay serves, through amenv_step, amenv_step_timed, amenv_rollout, amenv_reset,
+ * amenv_observe and amenv_rollout_policy in the one-lane-per-env form (a config the lane-quad closed loop would serve runs the one-lane form
+ * while the history is on).  Every obs / terminal_obs buffer passed while it is on has rows of amenv_obs_dim(env) floats.
+ * Refused with AMENV_ERR_INVALID, the handle untouched: rows outside 0..2, arm vehicles, other rotor counts, fp64 handles, a handle whose
+ * step kernel is the lane-quad one; and amenv_rollout_policy_norm while the history is on (normalise step by step).
+ * amenv_policy_forward, amenv_policy_forward_mfma and amenv_ppo_mlp_step accept the (obs_dim, act_dim) pairs (24, 4), (28, 4), (21, 4), (25, 4). */
+/* rows = 0: off (the handle publishes base-width rows and, if the delay is off too, launches exactly the kernels it launched before) */
+int amenv_set_action_history(amenv* env, int32_t rows);
+/* the row width every obs / terminal_obs buffer of this handle must have now: base + 4 rows */
+int32_t amenv_obs_dim(const amenv* env);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

@@ -111,6 +111,8 @@ SYMBOLS = {
     "amenv_set_action_delay": (C.c_int, [_P, C.POINTER(ActionDelayC)]),
     "amenv_get_action_delay_state": (C.c_int, [_P, _P, _P, _P]),
     "amenv_set_action_delay_state": (C.c_int, [_P, _P, _P, _P]),
+    "amenv_set_action_history": (C.c_int, [_P, C.c_int32]),
+    "amenv_obs_dim": (C.c_int32, [_P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

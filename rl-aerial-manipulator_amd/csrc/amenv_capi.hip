@@ -71,7 +71,10 @@ struct amenv {
   void* lag_w = nullptr;           // [n_tiles][n_rotors][64] rotor states | [n_rotors] w0, of the handle's dtype; allocated when the lag is first enabled
   bool delay = false;              // amenv_set_action_delay: per-episode actuation latency on
   int32_t delay_lo = 0, delay_hi = 0;   // its range of control steps, for the episodes that start from now on
-  void* delay_h = nullptr;         // float4 [n_tiles][8][64] given rows | int32 [n_tiles * 64] d | head << 4; allocated when the delay is first enabled
+  void* delay_h = nullptr;         // float4 [n_tiles][8][64] given rows | int32 [n_tiles * 64] d | head << 4; allocated when the delay or the history is first enabled
+  int hist = 0;                    // amenv_set_action_history: given action rows appended to every observation row, 0..2; > 0 runs the DELAY kernels
+  float* hist_obs = nullptr;       // [N][obs_dim] the task's rows of amenv_reset / amenv_observe while the history is on, widened into the caller's buffer
+  bool delay_path() const { return delay || hist > 0; }   // the DELAY instantiations run: the latency, the history (range (0, 0) without the latency) or both
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
   std::string kname;
@@ -339,7 +342,8 @@ template <typename T, int NROT> LagArg<T, NROT, true> make_lag(const amenv& e) {
 DelayArg<true> make_delay(const amenv& e) {
   DelayArg<true> D;
   D.h = static_cast<float4*>(e.delay_h); D.n_pad = uint32_t(e.n_tiles) * 64u;
-  D.lo = e.delay_lo; D.span = e.delay_hi - e.delay_lo + 1;
+  D.lo = e.delay ? e.delay_lo : 0; D.span = e.delay ? e.delay_hi - e.delay_lo + 1 : 1;   // the history alone: range (0, 0), every d is 0
+  D.hist = e.hist;
   return D;
 }
 // the kernels' last argument: the randomisation ranges, behind them the lag block in the LAG instantiations, behind that the sensor
@@ -491,6 +495,7 @@ std::string kernel_name(const amenv& e) {
   if (e.lag) name += " +lag";
   if (e.noise) name += " +noise";
   if (e.delay) name += " +delay";
+  if (e.hist) name += " +history " + std::to_string(e.hist);
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -528,7 +533,7 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + (DELAY ? 4 * e.hist : 0)) * sizeof(float), s,
                 e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
 }
 
@@ -578,14 +583,14 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
       break;
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
-        const size_t lds = size_t(64 * ObsDim<VAR, 0>::value + 12 * 64) * sizeof(float);
+        const size_t lds = size_t(64 * (ObsDim<VAR, 0>::value + (DELAY ? 8 : 0)) + 12 * 64) * sizeof(float);   // (the DELAY forms stage rows of up to two more action rows)
         return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG, NOISE, DELAY>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
                       io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + (DELAY ? 4 * e.hist : 0)) * sizeof(float), s,
                     e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
     }
   }
@@ -613,7 +618,7 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
   }
   if constexpr (sizeof(T) == 4) {
-    if (e.delay) {
+    if (e.delay_path()) {
       if (nr == 4) return dispatch_delay<T, 4>(e, io, T_steps, s, timed);
       if (nr == 6) return dispatch_delay<T, 6>(e, io, T_steps, s, timed);
       return hipErrorInvalidValue;
@@ -702,7 +707,7 @@ hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, con
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  if (e.delay) {   // (all four (LAG, NOISE) pairs)
+  if (e.delay_path()) {   // (all four (LAG, NOISE) pairs)
     if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true, true>(e, T, io, N, s);
     return e.lag ? launch_rigid_policy_dr<NORM, true, true, false, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, false, true>(e, T, io, N, s);
   }
@@ -813,12 +818,29 @@ hipError_t launch_delay_reset(const amenv& e, const uint8_t* mask, hipStream_t s
   return hipGetLastError();
 }
 
+// amenv_reset / amenv_observe while the action history is on: the task's rows (pitch od) -> the caller's (pitch od + 4 H), each ending
+// in the first H rows of its env's history, most recent first (after delay_reset_kernel on the same stream: hover rows for the masked envs)
+__global__ void hist_widen_kernel(int n, int od, const DelayArg<true> D, const float* __restrict__ rows, float* __restrict__ out) {
+  const int w = od + 4 * D.hist;
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= int64_t(n) * w) return;
+  const int i = int(t / w), c = int(t % w);
+  if (c < od) { out[t] = rows[size_t(i) * od + c]; return; }
+  const int k = (c - od) >> 2, head = (delay_word(D)[i] >> 4) & 7;
+  out[t] = reinterpret_cast<const float*>(D.h + delay_slot(i) + 64 * ((head - 1 - k) & 7))[(c - od) & 3];
+}
+hipError_t launch_hist_widen(const amenv& e, float* out, hipStream_t s) {
+  const int64_t total = int64_t(e.cfg.num_envs) * (e.obs_dim + 4 * e.hist);
+  hipLaunchKernelGGL(hist_widen_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, e.cfg.num_envs, e.obs_dim, make_delay(e), (const float*)e.hist_obs, out);
+  return hipGetLastError();
+}
+
 // amenv_rollout_policy[_norm] after the entry checks: pack the parameters, fill the kernel's I/O block
 PolicyIO policy_io(amenv& e, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards,
                    uint8_t* dones, uint32_t* info_bits, float* terminal_obs, hipStream_t s) {
   // parameters -> bf16 MFMA fragments + per-lane action constants (they change every PPO iteration): a tiny kernel in front, no host sync
   const int pack_threads = 4 * (kPolFrags + kPolBias) * 64 + 64 + 4 * 4 * 64;
-  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, e.obs_dim, e.act_dim, e.io_act ? e.pub_nj : 0, e.pol_pack);
+  hipLaunchKernelGGL(policy_pack_kernel, dim3((pack_threads + 255) / 256), dim3(256), 0, s, flat_params, e.obs_dim + 4 * e.hist, e.act_dim, e.io_act ? e.pub_nj : 0, e.pol_pack);
   PolicyIO io;
   io.pack = reinterpret_cast<const uint4*>(e.pol_pack);
   io.seed_lo = uint32_t(seed); io.seed_hi = uint32_t(seed >> 32); io.draw0 = draw0;
@@ -1064,6 +1086,7 @@ int amenv_destroy(amenv* e) {
     if (e->pol_pack) (void)hipFree(e->pol_pack);
     if (e->lag_w) (void)hipFree(e->lag_w);
     if (e->delay_h) (void)hipFree(e->delay_h);
+    if (e->hist_obs) (void)hipFree(e->hist_obs);
     if (e->io_act) (void)hipFree(e->io_act);
     if (e->io_obs) (void)hipFree(e->io_obs);
     if (e->io_term) (void)hipFree(e->io_term);
@@ -1226,31 +1249,44 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   return AMENV_OK;
 }
 
+namespace {
+// What amenv_set_action_delay and amenv_set_action_history serve (one set: the history IS the delay's side buffer), and that buffer's one
+// allocation.  who: the entry point, for the messages.  AMENV_OK, or the failure already recorded in the handle.
+int delay_served(amenv* e, const std::string& who) {
+  const amenv_vehicle& v = e->cfg.vehicle;
+  if (v.n_joints > 0 || e->pub_nj > 0) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles (the arm kernels are not built with it)");
+  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles with 4 or 6 rotors");
+  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, who + ": fp32 handles only (the fp64 builds are logic gates of the dynamics)");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, who + ": the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  return AMENV_OK;
+}
+int delay_buffer(amenv* e, const std::string& who) {   // (under a DeviceGuard)
+  if (e->delay_h) return AMENV_OK;
+  const size_t n_pad = size_t(e->n_tiles) * 64;
+  void* buf = nullptr;
+  hipError_t st = hipMalloc(&buf, n_pad * (AMENV_MAX_ACTION_DELAY * sizeof(float4) + sizeof(int32_t)));
+  if (st != hipSuccess) return fail(e, AMENV_ERR_ALLOC, who + ": hipMalloc: " + hipGetErrorString(st));
+  e->delay_h = buf;
+  return AMENV_OK;
+}
+}  // namespace
+
 int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
   if (!e) return AMENV_ERR_INVALID;
-  if (!z) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused)
+  if (!z) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused) -- or, while the action history is
+    // on, the DELAY kernels with range (0, 0): every env keeps its d and its rows, the episodes that start from now on draw 0
     e->delay = false;
     e->kname = kernel_name(*e);
     return AMENV_OK;
   }
-  const amenv_vehicle& v = e->cfg.vehicle;
   if (z->struct_size != sizeof(amenv_action_delay)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: struct_size must be sizeof(amenv_action_delay)");
   if (z->min_steps < 0 || z->min_steps > z->max_steps || z->max_steps > AMENV_MAX_ACTION_DELAY)
     return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: need 0 <= min_steps <= max_steps <= AMENV_MAX_ACTION_DELAY (8)");
-  if (v.n_joints > 0 || e->pub_nj > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: built for rigid vehicles (the arm kernels are not built with it)");
-  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: built for rigid vehicles with 4 or 6 rotors");
-  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: fp32 handles only (the fp64 builds are logic gates of the dynamics)");
-  if (e->family == StepFamily::Quad)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
-                "use the lane or helper kernel");
+  if (int rc = delay_served(e, "amenv_set_action_delay")) return rc;
   DeviceGuard g(e->device);
-  if (!e->delay_h) {   // first enable: the one allocation
-    const size_t n_pad = size_t(e->n_tiles) * 64;
-    void* buf = nullptr;
-    hipError_t st = hipMalloc(&buf, n_pad * (AMENV_MAX_ACTION_DELAY * sizeof(float4) + sizeof(int32_t)));
-    if (st != hipSuccess) return fail(e, AMENV_ERR_ALLOC, std::string("amenv_set_action_delay: hipMalloc: ") + hipGetErrorString(st));
-    e->delay_h = buf;
-  }
+  if (int rc = delay_buffer(e, "amenv_set_action_delay")) return rc;   // first enable: the one allocation
   const bool was_on = e->delay;
   e->delay_lo = z->min_steps; e->delay_hi = z->max_steps;
   e->delay = true;
@@ -1262,10 +1298,39 @@ int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
   return AMENV_OK;
 }
 
+int amenv_set_action_history(amenv* e, int32_t rows) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (rows < 0 || rows > 2) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_history: rows must be 0 (off), 1 or 2");
+  if (rows == 0) {   // off: base-width rows again; without the delay the handle launches the kernels it launched before (the buffers stay allocated, unused)
+    e->hist = 0;
+    e->kname = kernel_name(*e);
+    return AMENV_OK;
+  }
+  if (int rc = delay_served(e, "amenv_set_action_history")) return rc;
+  DeviceGuard g(e->device);
+  if (int rc = delay_buffer(e, "amenv_set_action_history")) return rc;   // the delay's side buffer IS the history
+  if (!e->hist_obs) {
+    void* buf = nullptr;
+    hipError_t st = hipMalloc(&buf, size_t(e->cfg.num_envs) * e->obs_dim * sizeof(float));
+    if (st != hipSuccess) return fail(e, AMENV_ERR_ALLOC, std::string("amenv_set_action_history: hipMalloc: ") + hipGetErrorString(st));
+    e->hist_obs = static_cast<float*>(buf);
+  }
+  const bool buffer_live = e->delay_path();   // the delay or the history has kept the buffer current
+  e->hist = rows;
+  e->kname = kernel_name(*e);
+  if (!buffer_live) {   // neither was on: hover rows, and d = 0 from the range (0, 0)
+    AMENV_HIP(e, launch_delay_reset(*e, nullptr, nullptr));
+    AMENV_HIP(e, hipDeviceSynchronize());
+  }
+  return AMENV_OK;
+}
+
+int32_t amenv_obs_dim(const amenv* e) { return e ? e->obs_dim + 4 * e->hist : 0; }
+
 int amenv_get_action_delay_state(amenv* e, int32_t* d_out, float* recent_out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   if (!d_out && !recent_out) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: NULL arguments");
-  if (!e->delay) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: the action delay is off (amenv_set_action_delay)");
+  if (!e->delay_path()) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: the action delay and the action history are off (amenv_set_action_delay, amenv_set_action_history)");
   if (recent_out && !aligned16(recent_out)) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: recent_out must be 16-byte aligned");
   DeviceGuard g(e->device);
   const int n = e->cfg.num_envs;
@@ -1277,7 +1342,7 @@ int amenv_get_action_delay_state(amenv* e, int32_t* d_out, float* recent_out, vo
 int amenv_set_action_delay_state(amenv* e, const int32_t* d_in, const float* recent_in, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   if (!d_in && !recent_in) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: NULL arguments");
-  if (!e->delay) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: the action delay is off (amenv_set_action_delay)");
+  if (!e->delay_path()) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: the action delay and the action history are off (amenv_set_action_delay, amenv_set_action_history)");
   if (recent_in && !aligned16(recent_in)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay_state: recent_in must be 16-byte aligned");
   DeviceGuard g(e->device);
   const int n = e->cfg.num_envs;
@@ -1311,11 +1376,12 @@ int amenv_reset(amenv* e, const uint8_t* mask, float* obs_out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  float* o = (e->io_obs && obs_out) ? e->io_obs : obs_out;
+  float* o = (e->io_obs && obs_out) ? e->io_obs : (e->hist && obs_out) ? e->hist_obs : obs_out;   // (the history is refused on the arms: at most one of the two)
   AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_reset<double>(*e, mask, o, 0, s) : launch_reset<float>(*e, mask, o, 0, s));
   if (e->lag) AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, mask, s) : launch_lag_reset<float>(*e, mask, s));
-  if (e->delay) AMENV_HIP(e, launch_delay_reset(*e, mask, s));
-  if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
+  if (e->delay_path()) AMENV_HIP(e, launch_delay_reset(*e, mask, s));
+  if (o == e->hist_obs && o) AMENV_HIP(e, launch_hist_widen(*e, obs_out, s));   // hover rows for the masked envs, the current history for the others
+  else if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
   return AMENV_OK;
 }
 
@@ -1323,9 +1389,10 @@ int amenv_observe(amenv* e, float* obs_out, void* stream) {
   if (!e || !obs_out) return fail(e, AMENV_ERR_INVALID, "amenv_observe: NULL argument");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  float* o = e->io_obs ? e->io_obs : obs_out;
+  float* o = e->io_obs ? e->io_obs : e->hist ? e->hist_obs : obs_out;
   AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_observe<double>(*e, o, nullptr, s) : launch_observe<float>(*e, o, nullptr, s));
-  if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
+  if (e->hist) AMENV_HIP(e, launch_hist_widen(*e, obs_out, s));
+  else if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
   return AMENV_OK;
 }
 
@@ -1395,7 +1462,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay_path() && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");
@@ -1559,6 +1626,8 @@ int amenv_rollout_policy_norm(amenv* e, amenv_obsnorm* h, int32_t update, float 
   if (!e || !h) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: env and normaliser must be non-NULL");
   if (!rigid_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: built for fp32 rigid vehicles with 4 or 6 rotors (arm vehicles: amenv_rollout_policy, normalise outside)");
+  if (e->hist)
+    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: not built with the action history (amenv_set_action_history): normalise step by step, or turn the history off");
   if (h->dim != e->obs_dim) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser's dim differs from the env's obs_dim");
   if (h->device != e->device) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser lives on another device");
   if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
@@ -1616,6 +1685,11 @@ int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_
   else if (obs_dim == 17 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<17, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 25 && act_dim == 5) hipLaunchKernelGGL((policy_forward_kernel<25, 5>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 27 && act_dim == 6) hipLaunchKernelGGL((policy_forward_kernel<27, 6>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  // the rigid vehicles' rows with one or two action rows of history
+  else if (obs_dim == 24 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<24, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 28 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<28, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 21 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<21, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 25 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<25, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
   else return AMENV_ERR_INVALID;   // (20,4) v2 | (29,7) hexacopter + arm | (17,4) v1 | (25,5) / (27,6) hexacopter + 1- / 2-link arm
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
@@ -1624,7 +1698,7 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
                               void* workspace, void* stream) {
   if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return AMENV_ERR_INVALID;
   if (!((obs_dim == 20 && act_dim == 4) || (obs_dim == 29 && act_dim == 7) || (obs_dim == 17 && act_dim == 4) || (obs_dim == 25 && act_dim == 5) ||
-        (obs_dim == 27 && act_dim == 6)))
+        (obs_dim == 27 && act_dim == 6) || (act_dim == 4 && (obs_dim == 24 || obs_dim == 28 || obs_dim == 21 || obs_dim == 25))))
     return AMENV_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   uint16_t* WS = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + kMlpWsAdv);   // the split-weight area of amenv_ppo_mlp_step's workspace
@@ -1636,7 +1710,11 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
   if (obs_dim == 20) hipLaunchKernelGGL((mlp_forward_kernel<20, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 29) hipLaunchKernelGGL((mlp_forward_kernel<29, 7>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   else if (obs_dim == 17) hipLaunchKernelGGL((mlp_forward_kernel<17, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 25) hipLaunchKernelGGL((mlp_forward_kernel<25, 5>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 25 && act_dim == 5) hipLaunchKernelGGL((mlp_forward_kernel<25, 5>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 24) hipLaunchKernelGGL((mlp_forward_kernel<24, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 28) hipLaunchKernelGGL((mlp_forward_kernel<28, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 21) hipLaunchKernelGGL((mlp_forward_kernel<21, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+  else if (obs_dim == 25) hipLaunchKernelGGL((mlp_forward_kernel<25, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   else hipLaunchKernelGGL((mlp_forward_kernel<27, 6>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
@@ -1705,6 +1783,10 @@ int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_di
   else if (obs_dim == 17 && act_dim == 4) st = launch_mlp_step<17, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else if (obs_dim == 25 && act_dim == 5) st = launch_mlp_step<25, 5>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else if (obs_dim == 27 && act_dim == 6) st = launch_mlp_step<27, 6>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 24 && act_dim == 4) st = launch_mlp_step<24, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 28 && act_dim == 4) st = launch_mlp_step<28, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 21 && act_dim == 4) st = launch_mlp_step<21, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  else if (obs_dim == 25 && act_dim == 4) st = launch_mlp_step<25, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
   else return AMENV_ERR_INVALID;
   if (st != hipSuccess) return AMENV_ERR_HIP;
   const int trunk = kH1 * obs_dim + kH1 + kH2 * kH1 + kH2 + kH3 * kH2 + kH3;

@@ -157,6 +157,54 @@ __device__ __forceinline__ void flush_obs(const float* lds, float* __restrict__ 
   }
 }
 
+// The DELAY forms' rows: the task's OD columns, then hr.n given action rows; W = OD + 4 hr.n is the row pitch in LDS and in
+// global memory (wave-uniform; W = OD while the history is off).  OD = 20: W * 4 bytes is a multiple of 16 and the float4 accesses stay.
+template <int OD>
+__device__ __forceinline__ void stage_obs_hist(float* lds_row, const float* o, const HistRows& hr) {
+  stage_obs<OD>(lds_row, o);
+  hist_put<OD % 4 == 0>(lds_row + OD, hr);
+}
+// flush_obs with the pitch at run time: up to two more float4 passes than OD needs, every one predicated.  The history off takes flush_obs itself.
+template <int OD>
+__device__ __forceinline__ void flush_obs_hist(const float* lds, float* __restrict__ obs, int row0, int rows_valid, int bs, int tid, int n_hist) {
+  if (n_hist == 0) { flush_obs<OD>(lds, obs + size_t(row0) * OD, rows_valid, bs, tid); return; }
+  if (rows_valid <= 0) return;
+  const int W = OD + 4 * n_hist;
+  float* obs_block = obs + size_t(row0) * W;
+  const float4* s = reinterpret_cast<const float4*>(lds);
+  float4* d = reinterpret_cast<float4*>(obs_block);
+  const int nflt = rows_valid * W, nvec = nflt >> 2;
+  constexpr int PASSES = (OD + 8 + 3) / 4;
+  float4 v[PASSES];
+#pragma unroll
+  for (int j = 0; j < PASSES; j++) {
+    const int f = j * bs + tid;
+    v[j] = (f < nvec) ? s[f] : make_float4(0.f, 0.f, 0.f, 0.f);   // (nvec * 4 <= bs * W: inside the staging area)
+  }
+#pragma unroll
+  for (int j = 0; j < PASSES; j++) {
+    const int f = j * bs + tid;
+    if (f < nvec) d[f] = v[j];
+  }
+  if constexpr (OD % 4 != 0) {
+    const int t = 4 * nvec + tid;
+    if (t < nflt) obs_block[t] = lds[t];
+  }
+}
+// one row written by its own lane (terminal rows, post-reset rows of the helper-wave kernel)
+template <int OD>
+__device__ __forceinline__ void store_row_hist(float* __restrict__ rows, int i, const float* o, const HistRows& hr) {
+  float* t = rows + size_t(i) * (OD + 4 * hr.n);
+  if constexpr (OD % 4 == 0) {
+#pragma unroll
+    for (int j = 0; j < OD / 4; j++) reinterpret_cast<float4*>(t)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < OD; j++) t[j] = o[j];
+  }
+  hist_put<OD % 4 == 0>(t + OD, hr);
+}
+
 // Monitor-style running totals.  Episode ends are rare (usually zero or one lane of a wave per step), so:
 // ballot + popcount for the counters, a SCALAR loop over the finished lanes (v_readlane) for the length /
 // return sums -- no cross-lane shuffles -- and one no-return atomic per wave and non-zero counter.
@@ -276,11 +324,11 @@ __device__ __forceinline__ void observe_reset(const Env<T, KW>& e, bool ee_task,
 }
 
 template <typename T, int NROT, int KW, int VAR, int NJ, int ROLE = 0, typename X = NoXchg, bool DR = false, typename LG = LagLane<T, NROT, false>,
-          typename NZ = NoiseArg<false>>
+          typename NZ = NoiseArg<false>, typename HX = NoHist>
 __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const ColdParams& C, const ArmArg<T, NJ>& AA, Env<T, KW>& e, const float* act, int i,
                                               bool active, T& reward, float* o, const StepIO& io, char* tile, int lane,
                                               bool have_episode, bool& was_reset, int& ep_len_out, float& ep_ret_out, const X& x = X{},
-                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr, const NZ& nz = NZ{}) {
+                                              const DynFac<T, NROT, DR>& df = DynFac<T, NROT, DR>{}, LG* lg = nullptr, const NZ& nz = NZ{}, const HX* hx = nullptr) {
   static_assert(!NZ::on || NJ == 0, "sensor noise is built for rigid vehicles");
   constexpr int OD = ObsDim<VAR, NJ>::value;
   const int K = KW == 1 ? 1 : P.K;
@@ -329,7 +377,9 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
     if (ended) {  // SB3 DummyVecEnv + Monitor contract
       ep_len_out = e.step; ep_ret_out = float(e.ep_return);
       if (active) {
-        if (!kLazyObs && io.terminal_obs) {   // two-wave kernel: the terminal observation is the row the helper wave staged; copied after the barrier
+        if constexpr (HX::on) {   // DELAY forms: the row's pitch follows the history, whose rows end it -- as they are before the reset wipes them
+          if (!kLazyObs && io.terminal_obs) store_row_hist<OD>(io.terminal_obs, i, o, *hx);
+        } else if (!kLazyObs && io.terminal_obs) {   // two-wave kernel: the terminal observation is the row the helper wave staged; copied after the barrier
           float* t = io.terminal_obs + size_t(i) * OD;
           if constexpr (OD % 4 == 0) {
 #pragma unroll
@@ -432,10 +482,11 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);   // (padding lanes own valid slots of the side buffer as of the blob)
   float act[AD];
   DelayLane dl; float4 given;
+  std::conditional_t<DELAY, HistRows, NoHist> hr;   // DELAY: the action rows that end this env's observation rows
   if constexpr (NJ == 0) {
     const float4 a = io.actions[min(i, hd.n - 1)];  // padding lanes re-read the last env's action: no exec branch in the prologue
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
-    if constexpr (DELAY) { given = a; delay_apply(DA.D, i, dl, act); }
+    if constexpr (DELAY) { given = a; hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
   } else {
     const float* ap = reinterpret_cast<const float*>(io.actions) + size_t(min(i, hd.n - 1)) * AD;   // 28-B rows: dword loads
 #pragma unroll
@@ -448,14 +499,17 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   DynFac<T, NROT, DR> df;
   if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
   uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
-                                                                      ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
+                                                                      ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA), &hr);
   const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
   AMENV_STAMP(3);          // dynamics + task + obs computed
   accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
   store_env_step<T, KW, NJ>(tile, lane, e, K);
   if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
   if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
-  if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
+  if constexpr (DELAY) {
+    if (was_reset) { dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); hr.hover(); }   // (the post-reset row ends in hover rows)
+    delay_push(DA.D, i, dl, given, was_reset);
+  }
   if (active) {
     reinterpret_cast<T*>(io.reward)[i] = reward;
     io.done[i] = is_done ? 1 : 0;
@@ -470,11 +524,17 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   }
   (void)lds;
 #else
-  stage_obs<OD>(lds + threadIdx.x * OD, o);
-  __syncthreads();
   const int row0 = blockIdx.x * BS;
   const int rows = min(BS, hd.n - row0);
-  flush_obs<OD>(lds, io.obs + size_t(row0) * OD, rows, BS, int(threadIdx.x));
+  if constexpr (DELAY) {
+    stage_obs_hist<OD>(lds + threadIdx.x * (OD + 4 * hr.n), o, hr);
+    __syncthreads();
+    flush_obs_hist<OD>(lds, io.obs, row0, rows, BS, int(threadIdx.x), hr.n);
+  } else {
+    stage_obs<OD>(lds + threadIdx.x * OD, o);
+    __syncthreads();
+    flush_obs<OD>(lds, io.obs + size_t(row0) * OD, rows, BS, int(threadIdx.x));
+  }
 #endif
   AMENV_STAMP(5);          // obs flushed
   AMENV_STAMP(6);
@@ -524,13 +584,14 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, tl.terminal_obs, tl.ep_return, tl.ep_len, tl.stats};
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // [64 rows x OD] obs staging | [12][64] reset words (or flag words + reset positions)
+  extern __shared__ __attribute__((aligned(16))) float lds[];   // [64 rows x ODS] obs staging | [12][64] reset words (or flag words + reset positions)
+  constexpr int ODS = OD + (DELAY ? 8 : 0);                     // the DELAY forms stage rows of up to two more action rows, pitch OD + 4 n
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);   // 0 main, 1 reset, 2 observation, 3 Monitor
   const int i = blockIdx.x * 64 + lane;
   const bool active = i < hd.n;
   char* tile = const_cast<char*>(tile_base(hd.blob, hd.tile_bytes, i));
-  uint32_t* words = reinterpret_cast<uint32_t*>(lds + 64 * OD);
+  uint32_t* words = reinterpret_cast<uint32_t*>(lds + 64 * ODS);
   const int row0 = blockIdx.x * 64;
   const ArmArg<T, 0> AA{0};
   if constexpr (kObsWave) {
@@ -599,9 +660,14 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       if (flag[lane] & 2u) {         // (padding lanes run real arithmetic on their own slots: their state is reset too, rows are not written)
         store_env_episode<T, KW>(1, tile, lane, er);
         if (active) {
-          float4* d = reinterpret_cast<float4*>(io.obs + size_t(i) * OD);
+          if constexpr (DELAY) {     // a new episode's row ends in hover rows
+            HistRows hv; hv.n = DA.D.hist; hv.hover();
+            store_row_hist<OD>(io.obs, i, ro, hv);
+          } else {
+            float4* d = reinterpret_cast<float4*>(io.obs + size_t(i) * OD);
 #pragma unroll
-          for (int j = 0; j < OD / 4; j++) d[j] = make_float4(ro[4 * j], ro[4 * j + 1], ro[4 * j + 2], ro[4 * j + 3]);
+            for (int j = 0; j < OD / 4; j++) d[j] = make_float4(ro[4 * j], ro[4 * j + 1], ro[4 * j + 2], ro[4 * j + 3]);
+          }
         }
       }
       AMENV_STAMP(5);
@@ -620,7 +686,8 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     DelayLane dl;
-    if constexpr (DELAY) delay_apply(DA.D, i, dl, act);
+    std::conditional_t<DELAY, HistRows, NoHist> hr;   // DELAY: the rows' action history: the observation wave's alone, used before the barrier
+    if constexpr (DELAY) { hr.g0 = a; if (role == 2) delay_apply(DA.D, i, dl, act, hr); else delay_apply(DA.D, i, dl, act); }   // (wave-uniform)
     if (role == 2) {
 #ifdef AMENV_STAMPS
       AMENV_STAMP_DRAIN();
@@ -636,15 +703,18 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
       } else {
         observe<T, KW>(1, e, ho);
       }
-      stage_obs<OD>(lds + lane * OD, ho);
+      if constexpr (DELAY) stage_obs_hist<OD>(lds + lane * (OD + 4 * hr.n), ho, hr); else stage_obs<OD>(lds + lane * OD, ho);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      flush_obs<OD>(lds, io.obs + size_t(row0) * OD, min(64, hd.n - row0), 64, lane);
+      if constexpr (DELAY) flush_obs_hist<OD>(lds, io.obs, row0, min(64, hd.n - row0), 64, lane, hr.n);
+      else flush_obs<OD>(lds, io.obs + size_t(row0) * OD, min(64, hd.n - row0), 64, lane);
       AMENV_STAMP(3);
       __syncthreads();               // rows stored and acknowledged (wave 1 may now overwrite those of reset lanes); flags published
       AMENV_STAMP(4);
       if (flag[lane] & 1u) {
-        if (io.terminal_obs) {
+        if constexpr (DELAY) {
+          if (io.terminal_obs) store_row_hist<OD>(io.terminal_obs, i, ho, hr);   // (the history as it was before the reset: this wave's registers)
+        } else if (io.terminal_obs) {
           float4* t = reinterpret_cast<float4*>(io.terminal_obs + size_t(i) * OD);
 #pragma unroll
           for (int j = 0; j < OD / 4; j++) t[j] = make_float4(ho[4 * j], ho[4 * j + 1], ho[4 * j + 2], ho[4 * j + 3]);
@@ -716,24 +786,34 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     DelayLane dl;
-    if constexpr (DELAY) delay_apply(DA.D, i, dl, act);
+    std::conditional_t<DELAY, HistRows, NoHist> hr;
+    if constexpr (DELAY) { hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
     uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false,
-                                                                                    was_reset, ep_len, ep_ret, x, df, &lg, noise_of(DA));
+                                                                                    was_reset, ep_len, ep_ret, x, df, &lg, noise_of(DA), &hr);
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int(blockIdx.x), bits, is_done, ep_len, ep_ret);
     store_env_step<T, KW>(tile, lane, e);
     if (was_reset) store_env_episode<T, KW>(K, tile, lane, e);
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); lag_store<T, NROT>(DA.L, i, lg); }
-    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, a, was_reset); }
+    if constexpr (DELAY) {
+      if (was_reset) { dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); hr.hover(); }
+      delay_push(DA.D, i, dl, a, was_reset);
+    }
     if (active) {
       reinterpret_cast<T*>(io.reward)[i] = reward;
       io.done[i] = is_done ? 1 : 0;
       io.info[i] = bits;
     }
-    stage_obs<OD>(lds + lane * OD, o);
-    __syncthreads();
-    flush_obs<OD>(lds, io.obs + size_t(row0) * OD, min(64, hd.n - row0), 64, lane);
+    if constexpr (DELAY) {
+      stage_obs_hist<OD>(lds + lane * (OD + 4 * hr.n), o, hr);
+      __syncthreads();
+      flush_obs_hist<OD>(lds, io.obs, row0, min(64, hd.n - row0), 64, lane, hr.n);
+    } else {
+      stage_obs<OD>(lds + lane * OD, o);
+      __syncthreads();
+      flush_obs<OD>(lds, io.obs + size_t(row0) * OD, min(64, hd.n - row0), 64, lane);
+    }
   }
 }
 
@@ -957,11 +1037,12 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   for (int t = 0; t < n_steps; t++) {
     float act[AD];
     DelayLane dl; float4 given;
+    std::conditional_t<DELAY, HistRows, NoHist> hr;   // DELAY: the rows' action history
     {
       const float* ap = reinterpret_cast<const float*>(io.actions) + (size_t(t) * n + min(i, hd.n - 1)) * AD;
       if constexpr (NJ == 0) {
         const float4 a = *reinterpret_cast<const float4*>(ap); act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
-        if constexpr (DELAY) { given = a; delay_apply(DA.D, i, dl, act); }
+        if constexpr (DELAY) { given = a; hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
       }
       else {
 #pragma unroll
@@ -973,7 +1054,10 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
                                                                         ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
     if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); }
-    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
+    if constexpr (DELAY) {
+      if (was_reset) { dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); hr.hover(); }
+      delay_push(DA.D, i, dl, given, was_reset);
+    }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(io.stats, int((blockIdx.x * blockDim.x + threadIdx.x) >> 6), bits, is_done, ep_len, ep_ret);
@@ -983,9 +1067,15 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
       if (io.info) io.info[size_t(t) * n + i] = bits;
     }
     if (io.obs) {
-      stage_obs<OD>(lds + threadIdx.x * OD, o);
-      __syncthreads();
-      flush_obs<OD>(lds, io.obs + (size_t(t) * n + row0) * OD, rows, int(blockDim.x), int(threadIdx.x));
+      if constexpr (DELAY) {
+        stage_obs_hist<OD>(lds + threadIdx.x * (OD + 4 * hr.n), o, hr);
+        __syncthreads();
+        flush_obs_hist<OD>(lds, io.obs + size_t(t) * n * (OD + 4 * hr.n), row0, rows, int(blockDim.x), int(threadIdx.x), hr.n);
+      } else {
+        stage_obs<OD>(lds + threadIdx.x * OD, o);
+        __syncthreads();
+        flush_obs<OD>(lds, io.obs + (size_t(t) * n + row0) * OD, rows, int(blockDim.x), int(threadIdx.x));
+      }
       __syncthreads();
     }
   }

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/amenv.h"
 
@@ -217,8 +218,16 @@ template <> struct DelayArg<true> {
   float4* h;           // [n_pad / 64][8][64] given rows | int32 [n_pad] d | head << 4
   uint32_t n_pad;      // the handle's padded env count (whole tiles)
   int32_t lo, span;    // min_steps, max_steps - min_steps + 1
+  int32_t hist;        // action history: 0..2 given rows appended to every observation row; wave-uniform, in the struct's tail padding
 };
 struct DelayLane { int d, head; };
+// The rows an observation row of the DELAY forms ends with: n of them (wave-uniform), g0 given in this step, g1 the step before.
+struct HistRows {
+  static constexpr bool on = true;
+  int n; float4 g0, g1;
+  __device__ __forceinline__ void hover() { g0 = g1 = make_float4(1.0f, 0.0f, 0.0f, 0.0f); }
+};
+struct NoHist { static constexpr bool on = false; };
 // The one kernel argument that carries the switches: DrArg's bytes unless LAG, NOISE or DELAY (the kernels without them keep their argument segment).
 template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false, bool DELAY = false> struct DynArg { DrArg<DR> R; };
 template <typename T, int NROT> struct DynArg<T, NROT, true, true, false, false> { DrArg<true> R; LagArg<T, NROT, true> L; };
@@ -682,6 +691,29 @@ __device__ __forceinline__ void delay_apply(const DelayArg<true>& D, int i, Dela
   dl.d = m & 15; dl.head = (m >> 4) & 7;
   const float4 r = D.h[delay_slot(i) + 64 * ((dl.head - dl.d) & 7)];
   if (dl.d != 0) { act[0] = r.x; act[1] = r.y; act[2] = r.z; act[3] = r.w; }
+}
+// The same with the action history: where two rows are appended, the row given in the step before -- slot (head - 1) & 7 as it is
+// BEFORE this step's push -- is loaded next to the delayed row (independent addresses: no further dependent trip).  hr.g0 is the caller's.
+__device__ __forceinline__ void delay_apply(const DelayArg<true>& D, int i, DelayLane& dl, float* act, HistRows& hr) {
+  const int32_t m = delay_word(D)[i];
+  dl.d = m & 15; dl.head = (m >> 4) & 7;
+  const float4* p = D.h + delay_slot(i);
+  const float4 r = p[64 * ((dl.head - dl.d) & 7)];
+  hr.n = D.hist;
+  hr.g1 = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+  if (D.hist > 1) hr.g1 = p[64 * ((dl.head - 1) & 7)];
+  if (dl.d != 0) { act[0] = r.x; act[1] = r.y; act[2] = r.z; act[3] = r.w; }
+}
+// columns OD .. OD + 4 n of a row (dst points at column OD; float4 stores where the row is 16-byte aligned)
+template <bool VEC>
+__device__ __forceinline__ void hist_put(float* dst, const HistRows& hr) {
+  if constexpr (VEC) {
+    if (hr.n > 0) reinterpret_cast<float4*>(dst)[0] = hr.g0;
+    if (hr.n > 1) reinterpret_cast<float4*>(dst)[1] = hr.g1;
+  } else {
+    if (hr.n > 0) { dst[0] = hr.g0.x; dst[1] = hr.g0.y; dst[2] = hr.g0.z; dst[3] = hr.g0.w; }
+    if (hr.n > 1) { dst[4] = hr.g1.x; dst[5] = hr.g1.y; dst[6] = hr.g1.z; dst[7] = hr.g1.w; }
+  }
 }
 // After the step: the given row enters the history (ONE slot), or, where a new episode starts (the caller has put its d into dl), all 8
 // slots become the hover row; then the word.

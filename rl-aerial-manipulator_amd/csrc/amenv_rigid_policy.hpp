@@ -166,6 +166,10 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
 #pragma unroll
   for (int j = 0; j < (NORM ? OD : 1); j++) { s1[j] = 0.0; s2[j] = 0.0; }
   const bool count = NORM && active && N.update != 0;
+  constexpr bool kHist = DELAY && !NORM;                          // the action history is not built into the normaliser forms
+  std::conditional_t<kHist, HistRows, NoHist> hr;                 // the given rows that end every published row, row pitch OD + 4 n
+  int W = OD;
+  if constexpr (kHist) { hr.n = DA.D.hist; hr.hover(); W = OD + 4 * hr.n; }
   auto publish_obs = [&](float* grow, bool add) {                 // observation row -> rollout buffer and (two bf16 parts) the MLP input tile
     float v[OD];
 #pragma unroll
@@ -191,6 +195,13 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     __bf16* xl = xlo + el * kXS;
 #pragma unroll
     for (int j = 0; j < OD; j++) { const __bf16 hi = (__bf16)v[j]; xr[j] = hi; xl[j] = (__bf16)(v[j] - float(hi)); }
+    if constexpr (kHist) {   // columns OD .. W: raw, neither perturbed nor scaled; two bf16 parts like the others
+      if (active) hist_put<OD % 4 == 0>(grow + OD, hr);
+      const float g[8] = {hr.g0.x, hr.g0.y, hr.g0.z, hr.g0.w, hr.g1.x, hr.g1.y, hr.g1.z, hr.g1.w};
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (j < 4 * hr.n) { const __bf16 hi = (__bf16)g[j]; xr[OD + j] = hi; xl[OD + j] = (__bf16)(g[j] - float(hi)); }
+    }
   };
   if (mine) {
     load_env<float, KW, 0>(K, tile, tl, e);
@@ -213,8 +224,14 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     __bf16* xr = xin + el * kXS;
     __bf16* xl = xlo + el * kXS;
 #pragma unroll
-    for (int j = OD; j < 32; j++) { xr[j] = (__bf16)(j == OD ? 1.0f : 0.0f); xl[j] = (__bf16)0.0f; }   // bias column, K padding
-    publish_obs(io.obs + size_t(i) * OD, false);
+    for (int j = OD; j < 32; j++) { xr[j] = (__bf16)(j == W ? 1.0f : 0.0f); xl[j] = (__bf16)0.0f; }   // bias column (behind the history's), K padding
+    if constexpr (kHist) {   // row 0 ends in the env's current history
+      const int head = (delay_word(DA.D)[i] >> 4) & 7;
+      const float4* p = DA.D.h + delay_slot(i);
+      if (hr.n > 0) hr.g0 = p[64 * ((head - 1) & 7)];
+      if (hr.n > 1) hr.g1 = p[64 * ((head - 2) & 7)];
+    }
+    publish_obs(io.obs + size_t(i) * W, false);
   }
   const int64_t gid = C.gid0 + i;
   const uint32_t g_lo = uint32_t(uint64_t(gid)), g_hi = uint32_t(uint64_t(gid) >> 32);
@@ -259,9 +276,12 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
       io.logp[tn + i] = logp; io.values[tn + i] = value;
     }
     DelayLane dl; float4 given;
-    if constexpr (DELAY) { given = make_float4(act[0], act[1], act[2], act[3]); delay_apply(DA.D, i, dl, act); }
+    if constexpr (DELAY) {
+      given = make_float4(act[0], act[1], act[2], act[3]);
+      if constexpr (kHist) { hr.g0 = given; delay_apply(DA.D, i, dl, act, hr); } else delay_apply(DA.D, i, dl, act);
+    }
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
-    sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * OD : nullptr;
+    sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * W : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
     LagLds<NROT, NE, LAG> lg;
     if constexpr (LAG) { lg.col = wl + el; lg.a_up = DA.L.a_up; lg.a_down = DA.L.a_down; }
@@ -271,7 +291,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
                                                                                                    ep_ret, NoXchg{}, df, &lg, NoiseLds<NE>{DA.Z.s, zl + el});
     else
       bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
-                                                                                                      ep_ret, NoXchg{}, df, &lg, noise_of(DA));
+                                                                                                      ep_ret, NoXchg{}, df, &lg, noise_of(DA), &hr);
     if constexpr (DR && !LAG) { if (was_reset) df = dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) {
       if (was_reset) {   // the new episode's rotors: w0 (behind the states in the side buffer), and the new episode's vehicle
@@ -280,7 +300,10 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
         lg.put(dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode));
       }
     }
-    if constexpr (DELAY) { if (was_reset) dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, gid, e.episode); delay_push(DA.D, i, dl, given, was_reset); }
+    if constexpr (DELAY) {
+      if (was_reset) { dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, gid, e.episode); if constexpr (kHist) hr.hover(); }
+      delay_push(DA.D, i, dl, given, was_reset);
+    }
     any_reset |= was_reset;
     const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
     accumulate_stats(stats, int(blockIdx.x) * EW + (wave - 4), bits, is_done, ep_len, ep_ret);
@@ -299,7 +322,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
       io.dones[tn + i] = is_done ? 1 : 0;
       if (io.info) io.info[tn + i] = bits;
     }
-    publish_obs(io.obs + (tn + n + i) * OD, count);              // row t + 1, and the next step's MLP input
+    publish_obs(io.obs + (tn + n + i) * W, count);              // row t + 1, and the next step's MLP input
   }
   if (mine) {
     store_env_step<float, KW, 0>(tile, tl, e, K);

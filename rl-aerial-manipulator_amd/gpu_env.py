@@ -33,8 +33,9 @@ class GpuWaypointEnv:
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
                  rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
-                 sensor_noise=None, action_delay=None):
+                 sensor_noise=None, action_delay=None, action_history=None):
         from .action_delay import ActionDelay
+        from .action_history import ActionHistory
         from .rotor_lag import RotorLag
         from .sensor_noise import SensorNoise
         if rotor_lag is not None and not isinstance(rotor_lag, RotorLag):   # before any device is touched
@@ -43,6 +44,8 @@ class GpuWaypointEnv:
             raise L.AmenvError(f"sensor_noise: expected a SensorNoise or None, got {type(sensor_noise).__name__}")
         if action_delay is not None and not isinstance(action_delay, ActionDelay):
             raise L.AmenvError(f"action_delay: expected an ActionDelay or None, got {type(action_delay).__name__}")
+        if action_history is not None and not isinstance(action_history, ActionHistory):
+            raise L.AmenvError(f"action_history: expected an ActionHistory or None, got {type(action_history).__name__}")
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -105,6 +108,9 @@ class GpuWaypointEnv:
         self.action_delay = None
         if action_delay is not None:
             self.set_action_delay(action_delay)
+        self.action_history = None
+        if action_history is not None:
+            self.set_action_history(action_history)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -203,9 +209,25 @@ class GpuWaypointEnv:
         self.action_delay = delay
         self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
 
+    def set_action_history(self, history):
+        """Action history in the observation rows (an `ActionHistory`, or None = the task's rows; fp32 rigid vehicles with 4 or 6 rotors, not
+        with kernel="team").  While it is on every row this env publishes is the task's row followed by the last `rows` action rows the env
+        was given, most recent first (hover rows where the episode is younger): `obs_dim` = 20 (17 on the v1 tasks) + 4 rows.  `obs` and
+        `terminal_obs` are re-allocated at the new width (zeros: `observe()` returns the current rows).  A configuration call: it may
+        allocate and synchronise."""
+        from .action_history import ActionHistory
+        if history is not None and not isinstance(history, ActionHistory):
+            raise L.AmenvError(f"set_action_history: expected an ActionHistory or None, got {type(history).__name__}")
+        self._check(self.lib.amenv_set_action_history(self._h, 0 if history is None else history.rows), "amenv_set_action_history")
+        self.action_history = history
+        self.obs_dim = int(self.lib.amenv_obs_dim(self._h))
+        self.obs = torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.terminal_obs = torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
     def action_delay_state(self):
         """(d [N] int32, recent [N, 8, 4] f32): every env's delay and the last 8 action rows it was given, in age order (recent[:, k] was
-        given k + 1 steps ago; the hover row where the episode is younger).  Needs the action delay on."""
+        given k + 1 steps ago; the hover row where the episode is younger).  Needs the action delay or the action history on."""
         d = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
         recent = torch.empty(self.num_envs, L.MAX_ACTION_DELAY, 4, dtype=torch.float32, device=self.device)
         self._check(self.lib.amenv_get_action_delay_state(self._h, C.c_void_p(d.data_ptr()), C.c_void_p(recent.data_ptr()), self._stream()),

@@ -109,7 +109,8 @@ class ActorCritic(nn.Module):
         self.flat_param = self.flat_grad = None
 
     # ---- forward pieces -----------------------------------------------------------------------
-    _FUSED_DIMS = {(20, 4), (29, 7), (17, 4), (25, 5), (27, 6)}   # v2 | hexacopter + 3-link arm | v1 | + 1- / 2-link arm
+    _FUSED_DIMS = {(20, 4), (29, 7), (17, 4), (25, 5), (27, 6),   # v2 | hexacopter + 3-link arm | v1 | + 1- / 2-link arm
+                   (24, 4), (28, 4), (21, 4), (25, 4)}            # v2 / v1 rows with one or two action rows of history (ActionHistory)
     MFMA_FORWARD_ROWS = 8192   # batches from here on take amenv_policy_forward_mfma (below: the VALU kernel's shorter latency wins)
 
     def fused_ok(self, obs):
@@ -560,6 +561,9 @@ class PPO:
         # opt-in: the whole rollout (policy MLPs on the bf16 matrix cores, sampling, clip, env step) in ONE launch -- amenv_rollout_policy
         self.fused_rollout = bool(fused_rollout)
         self.fused_rollout_fp32_stats = bool(fused_rollout_fp32_stats)   # fused rollout: store the fp32 policy's log-probs / values (SB3's buffer semantics)
+        if self.fused_rollout and obs_normalizer is not None and getattr(env, "action_history", None) is not None:
+            raise L.AmenvError("fused_rollout with an observation normaliser is not built with the action history (amenv_rollout_policy_norm refuses it): "
+                               "use the step-by-step rollout (fused_rollout=False) with the normaliser, or fused_rollout without one")
         if self.fused_rollout and obs_normalizer is not None and int(env.cfg.vehicle.n_joints) != 0:
             raise L.AmenvError("fused_rollout with an observation normaliser is built for the rigid vehicles (amenv_rollout_policy_norm); "
                                "arm vehicles: fused_rollout without a normaliser, or the step-by-step rollout")

@@ -38,6 +38,8 @@ if __name__ == "__main__":
                     help="sensor noise on the observations: standard deviations of position, velocity, body rate, attitude (DESIGN 4l)")
     ap.add_argument("--action-delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
                     help="per-episode actuation latency: each env applies the action given MIN..MAX control steps ago (DESIGN 4m)")
+    ap.add_argument("--action-history", type=int, default=None, metavar="H",
+                    help="append the last H (1 or 2) given action rows to every observation row (DESIGN 4n; not with --normalize-obs --one-launch)")
     a = ap.parse_args()
     import torch
     import rl_aerial_manipulator_amd as amd
@@ -45,6 +47,7 @@ if __name__ == "__main__":
     lag = None if a.rotor_lag is None else amd.RotorLag(a.rotor_lag)
     delay = None if a.action_delay is None else amd.ActionDelay(*a.action_delay)
     dr = amd.DynamicsRandomization.around_one(mass=0.2, inertia=0.2, thrust=0.05) if a.randomize else None
+    hist = None if a.action_history is None else amd.ActionHistory(a.action_history)
     out = {}
     if a.one_launch:
         from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
@@ -52,7 +55,7 @@ if __name__ == "__main__":
         for n in a.envs:
             for fused in (True, False):
                 env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints, block_size=a.block_size,
-                                         randomization=dr, rotor_lag=lag, sensor_noise=noise, action_delay=delay)
+                                         randomization=dr, rotor_lag=lag, sensor_noise=noise, action_delay=delay, action_history=hist)
                 norm = ObsNormalizer(env.obs_dim) if a.normalize_obs else None
                 algo = PPO(env, obs_normalizer=norm, fused_rollout=fused, n_steps=a.rollout_steps, seed=0)
                 algo.fused_rollout_fp32_stats = False        # time the rollout itself: no fp32 re-evaluation of the buffer behind it
@@ -71,12 +74,12 @@ if __name__ == "__main__":
                 env.close()
                 if norm is not None:
                     norm.close()
-        print(json.dumps({"vehicle": a.vehicle, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "action_delay": a.action_delay, "block_size": a.block_size, "n_joints": a.n_joints, "waypoints": a.waypoints, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
+        print(json.dumps({"vehicle": a.vehicle, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "action_delay": a.action_delay, "action_history": a.action_history, "block_size": a.block_size, "n_joints": a.n_joints, "waypoints": a.waypoints, "task": a.task, "normalize_obs": a.normalize_obs, "rollout_steps": a.rollout_steps,
                           "loop": "PPO.collect_rollouts (policy + sample + clip + step [+ normaliser] x T, GAE)", "results": out}))
         sys.exit(0)
     for n in a.envs:
         env = amd.GpuWaypointEnv(n, vehicle=a.vehicle, task=a.task, seed=0, n_joints=a.n_joints, num_waypoints=a.waypoints, block_size=a.block_size,
-                                         randomization=dr, rotor_lag=lag, sensor_noise=noise, action_delay=delay)
+                                         randomization=dr, rotor_lag=lag, sensor_noise=noise, action_delay=delay, action_history=hist)
         pol = amd.ActorCritic(env.obs_dim, env.act_dim).to(env.device).flatten_()
         for mode in ("fused", "torch"):
             obs = env.reset()
@@ -102,4 +105,4 @@ if __name__ == "__main__":
             out[f"{n}_{mode}"] = {"eager_us_per_step": dt / a.steps * 1e6, "graph_us_per_step": dg / (a.steps // 16 * 16) * 1e6,
                                   "graph_env_steps_per_s": n * (a.steps // 16 * 16) / dg}
         env.close()
-    print(json.dumps({"vehicle": a.vehicle, "task": a.task, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "action_delay": a.action_delay, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
+    print(json.dumps({"vehicle": a.vehicle, "task": a.task, "randomize": a.randomize, "rotor_lag": a.rotor_lag, "sensor_noise": a.sensor_noise, "action_delay": a.action_delay, "action_history": a.action_history, "loop": "obs -> policy mean -> clip -> env.step", "results": out}))
