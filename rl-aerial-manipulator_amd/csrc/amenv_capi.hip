@@ -324,10 +324,6 @@ ColdParams make_cold(const amenv& e) {
   return C;
 }
 
-template <bool DR> DrArg<DR> make_dr(const amenv& e);
-template <> DrArg<false> make_dr<false>(const amenv&) { return DrArg<false>{0}; }
-template <> DrArg<true> make_dr<true>(const amenv& e) { return DrArg<true>{e.dr_r}; }
-
 // episode-start rotor state: the rotors spin at the NOMINAL hover command, sqrt(clamp(alloc[r] . (m g, 0, 0, 0))), fp64
 double lag_w0(const amenv_vehicle& v, int r) {
   const double t = v.alloc[r * 4] * (v.mass * v.g);
@@ -348,15 +344,13 @@ DelayArg<true> make_delay(const amenv& e) {
 }
 // the kernels' last argument: the randomisation ranges, behind them the lag block in the LAG instantiations, behind that the sensor
 // noise's sigmas in the NOISE ones, behind those the actuation latency's fields in the DELAY ones
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false, bool DELAY = false> DynArg<T, NROT, DR, LAG, NOISE, DELAY> make_dyn(const amenv& e) {
-  if constexpr (DELAY && LAG && NOISE) return DynArg<T, NROT, true, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}, make_delay(e)};
-  else if constexpr (DELAY && NOISE) return DynArg<T, NROT, true, false, true, true>{make_dr<true>(e), NoiseArg<true>{e.noise_s}, make_delay(e)};
-  else if constexpr (DELAY && LAG) return DynArg<T, NROT, true, true, false, true>{make_dr<true>(e), make_lag<T, NROT>(e), make_delay(e)};
-  else if constexpr (DELAY) return DynArg<T, NROT, true, false, false, true>{make_dr<true>(e), make_delay(e)};
-  else if constexpr (LAG && NOISE) return DynArg<T, NROT, true, true, true>{make_dr<true>(e), make_lag<T, NROT>(e), NoiseArg<true>{e.noise_s}};
-  else if constexpr (NOISE) return DynArg<T, NROT, true, false, true>{make_dr<true>(e), NoiseArg<true>{e.noise_s}};
-  else if constexpr (LAG) return DynArg<T, NROT, true, true>{make_dr<true>(e), make_lag<T, NROT>(e)};
-  else return DynArg<T, NROT, DR, false>{make_dr<DR>(e)};
+template <typename T, int NROT, unsigned DYN> DynArg<T, NROT, DYN> make_dyn(const amenv& e) {
+  DynArg<T, NROT, DYN> a;
+  if constexpr ((DYN & kDynDr) != 0) a.R.r = e.dr_r; else a.R.unused = 0;
+  if constexpr ((DYN & kDynLag) != 0) a.L = make_lag<T, NROT>(e);
+  if constexpr ((DYN & kDynNoise) != 0) a.Z.s = e.noise_s;
+  if constexpr ((DYN & kDynDelay) != 0) a.D = make_delay(e);
+  return a;
 }
 // the cold kernels' (reset, observe) runtime switch
 NoiseRt make_noise_rt(const amenv& e) {
@@ -510,7 +504,7 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 
 // amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
 // runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR, bool LAG, bool NOISE, bool DELAY>
+template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYN>
 hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
   const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
   const ColdParams C = make_cold(e);
@@ -518,12 +512,12 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   const int32_t n = e.cfg.num_envs;
   switch (e.family) {
     case StepFamily::Team:   // one wave per 4 envs; the fp64 build is a logic gate of amenv_step only (amenv_rollout refuses it)
-      if constexpr (NJ == 3 && sizeof(T) == 4 && !DR)
+      if constexpr (NJ == 3 && sizeof(T) == 4 && DYN == 0)
         return launch(e, false, rollout_kernel_team<NROT>, dim3(e.n_tiles * 16), dim3(64), 0, s, e.blob, tb, n, reinterpret_cast<const float*>(io.actions), io.obs,
                       static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, make_team<T>(e));
       return hipErrorInvalidValue;
     case StepFamily::Quad:   // one wave per 16 envs
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && !DR)
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && DYN == 0)
         return launch(e, false, rollout_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(64), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
                       io.info, T_steps, tl, C, make_quad(e));
       return hipErrorInvalidValue;
@@ -533,15 +527,15 @@ hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStre
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + (DELAY ? 4 * e.hist : 0)) * sizeof(float), s,
-                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
+  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DYN>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + ((DYN & kDynDelay) ? 4 * e.hist : 0)) * sizeof(float), s,
+                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DYN>(e));
 }
 
 // amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
 // if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
+template <typename T, int NROT, int KW, int VAR, int NJ = 0, unsigned DYN = 0>
 hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>(e, io, T_steps, s);
+  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DYN>(e, io, T_steps, s);
   ArmArg<T, NJ> AA;
   if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
   const HotParams<T, NROT> P = make_hot<T, NROT>(e);
@@ -551,7 +545,7 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
   const int32_t n = e.cfg.num_envs;
   switch (e.family) {
     case StepFamily::Team:   // 16 lanes per env; 16 envs per workgroup (four main waves + one episode-end helper wave) while each workgroup has a CU to itself, else 4 (one + one)
-      if constexpr (NJ == 3 && !DR) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
+      if constexpr (NJ == 3 && DYN == 0) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
         const TeamParamsT<T> TP = make_team<T>(e);
         if (team_wide(e))
           return launch(e, timed, step_kernel_team<T, NROT, 4>, dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, n, int32_t(e.n_tiles * 4),
@@ -561,7 +555,7 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
       }
       break;
     case StepFamily::Staged:   // one tile per 320-thread workgroup: four stage waves + main wave
-      if constexpr (NJ == 3 && !DR) {
+      if constexpr (NJ == 3 && DYN == 0) {
         if constexpr (sizeof(T) == 8) {   // the fp64 logic-gate build exchanges its aggregates in fp64: > 64 KB of dynamic LDS needs the attribute
           hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel_armk<T, NROT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
           if (ea != hipSuccess) return ea;
@@ -571,77 +565,76 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
       }
       break;
     case StepFamily::TwoWave:   // one tile per 128-thread workgroup: main + helper wave
-      if constexpr (NJ == 3 && sizeof(T) == 4 && !DR) {
+      if constexpr (NJ == 3 && sizeof(T) == 4 && DYN == 0) {
         const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + (kArmXchgSlots + 12) * 64) * sizeof(float);   // obs rows | RK4 exchange | reset words
         return launch(e, timed, step_kernel_arm2w<T, NROT>, dim3(e.n_tiles), dim3(128), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
       }
       break;
     case StepFamily::Quad:   // 4 lanes per env, 16 envs per workgroup: main wave + episode-end helper wave
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && !DR)
+      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && DYN == 0)
         return launch(e, timed, step_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(128), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
                       io.info, tl, C, make_quad(e));
       break;
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
-        const size_t lds = size_t(64 * (ObsDim<VAR, 0>::value + (DELAY ? 8 : 0)) + 12 * 64) * sizeof(float);   // (the DELAY forms stage rows of up to two more action rows)
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DR, LAG, NOISE, DELAY>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
-                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
+        const size_t lds = size_t(64 * (ObsDim<VAR, 0>::value + ((DYN & kDynDelay) ? 8 : 0)) + 12 * 64) * sizeof(float);   // (the DELAY forms stage rows of up to two more action rows)
+        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DYN>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
+                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DYN>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DR, LAG, NOISE, DELAY>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + (DELAY ? 4 * e.hist : 0)) * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DR, LAG, NOISE, DELAY>(e));
+      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DYN>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + ((DYN & kDynDelay) ? 4 * e.hist : 0)) * sizeof(float), s,
+                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DYN>(e));
     }
   }
   return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
 }
 
-template <typename T, int NROT, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
-hipError_t dispatch_k(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (is_v1(&e.cfg)) return launch_step<T, NROT, 2, VAR_V1, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return launch_step<T, NROT, 1, VAR_V2, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);
-  return launch_step<T, NROT, AMENV_MAX_WAYPOINTS, VAR_V2, 0, DR, LAG, NOISE, DELAY>(e, io, T_steps, s, timed);
+// The switch set a handle runs, for amenv_step, amenv_rollout and the closed-loop rollouts alike: the lag, the noise and the DELAY path, and DR with any
+// of them (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
+unsigned dyn_set(const amenv& e) {
+  const int nr = e.cfg.vehicle.n_rotors;
+  if (e.cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6)) return 0;
+  const unsigned on = (e.lag ? kDynLag : 0) | (e.noise ? kDynNoise : 0) | (e.delay_path() ? kDynDelay : 0);
+  return on | (on || e.dr ? kDynDr : 0);
 }
-// amenv_set_action_delay admits fp32 handles of what amenv_set_randomization admits; the DELAY kernels are DR ones, for all four (LAG, NOISE) pairs
-template <typename T, int NROT>
-hipError_t dispatch_delay(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (e.lag) return e.noise ? dispatch_k<T, NROT, true, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, NROT, true, true, false, true>(e, io, T_steps, s, timed);
-  return e.noise ? dispatch_k<T, NROT, true, false, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, NROT, true, false, false, true>(e, io, T_steps, s, timed);
+template <auto V> using const_c = std::integral_constant<decltype(V), V>;
+// f(const_c<NROT>, const_c<DYN>) with DYN == dyn, over the sets that are built for T (dyn_admitted) and NROT (the general rotor count: no switch)
+template <typename T, int NROT, unsigned DYN = 0, typename F>
+hipError_t with_dyn(unsigned dyn, F& f) {
+  if constexpr (DYN <= kDynAll) {
+    if constexpr (dyn_admitted<T, 0>(DYN) && (DYN == 0 || NROT == 4 || NROT == 6)) { if (dyn == DYN) return f(const_c<NROT>{}, const_c<DYN>{}); }
+    return with_dyn<T, NROT, DYN + 1>(dyn, f);
+  }
+  return hipErrorInvalidValue;
+}
+// a rigid handle's compile-time form: its rotor count (4, 6, or the general loop bound) and its switch set
+template <typename T, typename F>
+hipError_t with_rigid_form(const amenv& e, F f) {
+  const unsigned dyn = dyn_set(e);
+  const int nr = e.cfg.vehicle.n_rotors;
+  return nr == 4 ? with_dyn<T, 4>(dyn, f) : nr == 6 ? with_dyn<T, 6>(dyn, f) : with_dyn<T, AMENV_MAX_ROTORS>(dyn, f);
+}
+// a rigid handle's task: f(const_c<KW>, const_c<VAR>)
+template <typename F>
+hipError_t with_task(const amenv& e, F f) {
+  if (is_v1(&e.cfg)) return f(const_c<2>{}, const_c<VAR_V1>{});   // v1: up to 2 waypoints per episode
+  if (e.cfg.task.num_waypoints == 1) return f(const_c<1>{}, const_c<VAR_V2>{});
+  return f(const_c<AMENV_MAX_WAYPOINTS>{}, const_c<VAR_V2>{});
 }
 
 template <typename T>
 hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed = false) {
-  const int nr = e.cfg.vehicle.n_rotors;
   if (e.cfg.vehicle.n_joints == 3) {
     if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
   }
-  if constexpr (sizeof(T) == 4) {
-    if (e.delay_path()) {
-      if (nr == 4) return dispatch_delay<T, 4>(e, io, T_steps, s, timed);
-      if (nr == 6) return dispatch_delay<T, 6>(e, io, T_steps, s, timed);
-      return hipErrorInvalidValue;
-    }
-    if (e.noise) {   // amenv_set_sensor_noise admits fp32 handles of what amenv_set_randomization admits; the NOISE kernels are DR ones, with or without LAG
-      if (nr == 4) return e.lag ? dispatch_k<T, 4, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 4, true, false, true>(e, io, T_steps, s, timed);
-      if (nr == 6) return e.lag ? dispatch_k<T, 6, true, true, true>(e, io, T_steps, s, timed) : dispatch_k<T, 6, true, false, true>(e, io, T_steps, s, timed);
-      return hipErrorInvalidValue;
-    }
-  }
-  if (e.lag) {  // amenv_set_rotor_lag admits what amenv_set_randomization admits; the LAG kernels are the DR ones (unit ranges when that is off)
-    if (nr == 4) return dispatch_k<T, 4, true, true>(e, io, T_steps, s, timed);
-    if (nr == 6) return dispatch_k<T, 6, true, true>(e, io, T_steps, s, timed);
-    return hipErrorInvalidValue;
-  }
-  if (e.dr) {   // amenv_set_randomization admits rigid vehicles with 4 or 6 rotors on the lane and helper-wave families only
-    if (nr == 4) return dispatch_k<T, 4, true>(e, io, T_steps, s, timed);
-    if (nr == 6) return dispatch_k<T, 6, true>(e, io, T_steps, s, timed);
-    return hipErrorInvalidValue;
-  }
-  if (nr == 4) return dispatch_k<T, 4>(e, io, T_steps, s, timed);
-  if (nr == 6) return dispatch_k<T, 6>(e, io, T_steps, s, timed);
-  return dispatch_k<T, AMENV_MAX_ROTORS>(e, io, T_steps, s, timed);
+  return with_rigid_form<T>(e, [&](auto nrot, auto dyn) {
+    return with_task(e, [&](auto kw, auto var) {
+      return launch_step<T, decltype(nrot)::value, decltype(kw)::value, decltype(var)::value, 0, decltype(dyn)::value>(e, io, T_steps, s, timed);
+    });
+  });
 }
 
 template <typename T>
@@ -681,39 +674,29 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifndef AMENV_RIGID_WG64_MAX
 #define AMENV_RIGID_WG64_MAX 24576
 #endif
-template <int NROT, int KW, int VAR, bool NORM, bool DR, bool LAG, bool NOISE, bool DELAY>
+template <int NROT, int KW, int VAR, bool NORM, unsigned DYN>
 hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
   const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
   const ColdParams C = make_cold(e);
-  const DynArg<float, NROT, DR, LAG, NOISE, DELAY> R = make_dyn<float, NROT, DR, LAG, NOISE, DELAY>(e);
+  const DynArg<float, NROT, DYN> R = make_dyn<float, NROT, DYN>(e);
   const int n = e.cfg.num_envs;
   if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DYN>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DYN>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DR, LAG, NOISE, DELAY>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DYN>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   return hipGetLastError();
-}
-template <bool NORM, bool DR, bool LAG = false, bool NOISE = false, bool DELAY = false>
-hipError_t launch_rigid_policy_dr(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  const bool four = e.cfg.vehicle.n_rotors == 4;
-  if (is_v1(&e.cfg))   // v1: up to 2 waypoints per episode
-    return four ? launch_rigid_policy_k<4, 2, VAR_V1, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s) : launch_rigid_policy_k<6, 2, VAR_V1, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
-  if (e.cfg.task.num_waypoints == 1)
-    return four ? launch_rigid_policy_k<4, 1, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s) : launch_rigid_policy_k<6, 1, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
-  return four ? launch_rigid_policy_k<4, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s)
-              : launch_rigid_policy_k<6, AMENV_MAX_WAYPOINTS, VAR_V2, NORM, DR, LAG, NOISE, DELAY>(e, T, io, N, s);
 }
 template <bool NORM>
 hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  if (e.delay_path()) {   // (all four (LAG, NOISE) pairs)
-    if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true, true>(e, T, io, N, s);
-    return e.lag ? launch_rigid_policy_dr<NORM, true, true, false, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, false, true>(e, T, io, N, s);
-  }
-  if (e.noise) return e.lag ? launch_rigid_policy_dr<NORM, true, true, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, true, false, true>(e, T, io, N, s);
-  if (e.lag) return launch_rigid_policy_dr<NORM, true, true>(e, T, io, N, s);   // (unit ranges when randomisation is off)
-  return e.dr ? launch_rigid_policy_dr<NORM, true>(e, T, io, N, s) : launch_rigid_policy_dr<NORM, false>(e, T, io, N, s);
+  return with_rigid_form<float>(e, [&](auto nrot, auto dyn) {
+    if constexpr (decltype(nrot)::value == 4 || decltype(nrot)::value == 6)   // (rigid_pol_ok)
+      return with_task(e, [&](auto kw, auto var) {
+        return launch_rigid_policy_k<decltype(nrot)::value, decltype(kw)::value, decltype(var)::value, NORM, decltype(dyn)::value>(e, T, io, N, s);
+      });
+    else return hipErrorInvalidValue;
+  });
 }
 
 // amenv_dynamics_factors: [N][2 + NROT] = km, kI, s_0.. of every env's current episode (dr_draw: the kernels' own arithmetic)
@@ -1119,6 +1102,22 @@ int amenv_set_seed(amenv* e, uint64_t seed) {
   return AMENV_OK;
 }
 
+namespace {
+// What the rigid kernels' opt-in switches serve, checked by every setter (who, for the messages): rigid vehicles with 4 or 6 rotors off the lane-quad
+// family, fp32 handles where the switch's kernels are fp32 only.  AMENV_OK, or the failure already recorded in the handle.  (pub_nj > 0 implies
+// cfg.vehicle.n_joints == 3, so the clause the delay's check had changes nothing for the setters that tested n_joints alone.)
+int rigid_switch_served(amenv* e, const std::string& who, bool needs_f32, const char* arm_reason = "the arm kernels are not built with it") {
+  const int nr = e->cfg.vehicle.n_rotors;
+  if (e->cfg.vehicle.n_joints > 0 || e->pub_nj > 0) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles (" + arm_reason + ")");
+  if (nr != 4 && nr != 6) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles with 4 or 6 rotors");
+  if (needs_f32 && e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, who + ": fp32 handles only (the fp64 builds are logic gates of the dynamics)");
+  if (e->family == StepFamily::Quad)
+    return fail(e, AMENV_ERR_INVALID, who + ": the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
+                "use the lane or helper kernel");
+  return AMENV_OK;
+}
+}  // namespace
+
 int amenv_set_randomization(amenv* e, const amenv_randomization* r) {
   if (!e) return AMENV_ERR_INVALID;
   if (!r) {
@@ -1128,13 +1127,7 @@ int amenv_set_randomization(amenv* e, const amenv_randomization* r) {
     return AMENV_OK;
   }
   if (r->struct_size != sizeof(amenv_randomization)) return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: struct_size must be sizeof(amenv_randomization)");
-  if (e->cfg.vehicle.n_joints > 0)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: built for rigid vehicles (an arm vehicle's mass and inertia are not one scalar scale)");
-  if (e->cfg.vehicle.n_rotors != 4 && e->cfg.vehicle.n_rotors != 6)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: built for rigid vehicles with 4 or 6 rotors");
-  if (e->family == StepFamily::Quad)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
-                "use the lane or helper kernel");
+  if (int rc = rigid_switch_served(e, "amenv_set_randomization", false, "an arm vehicle's mass and inertia are not one scalar scale")) return rc;
   const float* rg[3] = {r->mass_scale, r->inertia_scale, r->thrust_scale};
   const char* nm[3] = {"mass_scale", "inertia_scale", "thrust_scale"};
   for (int q = 0; q < 3; q++) {
@@ -1178,13 +1171,7 @@ int amenv_set_sensor_noise(amenv* e, const amenv_sensor_noise* z) {
   for (int q = 0; q < 4; q++)
     if (!std::isfinite(sg[q]) || !(sg[q] >= 0.0f) || !(sg[q] <= 1.0f))
       return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_sensor_noise: ") + nm[q] + " must be finite with 0 <= sigma <= 1");
-  const amenv_vehicle& v = e->cfg.vehicle;
-  if (v.n_joints > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: built for rigid vehicles (the arm kernels are not built with it)");
-  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: built for rigid vehicles with 4 or 6 rotors");
-  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: fp32 handles only (the fp64 builds are logic gates of the dynamics)");
-  if (e->family == StepFamily::Quad)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
-                "use the lane or helper kernel");
+  if (int rc = rigid_switch_served(e, "amenv_set_sensor_noise", true)) return rc;
   if (e->cfg.task.max_episode_steps > (1 << 22) - 2)
     return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: max_episode_steps must be <= 2^22 - 2 (the step field of the draw's counter has 22 bits)");
   const bool any = sg[0] != 0.0f || sg[1] != 0.0f || sg[2] != 0.0f || sg[3] != 0.0f;   // all zeros: the same as off
@@ -1214,11 +1201,7 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   }
   const amenv_vehicle& v = e->cfg.vehicle;
   if (lag->struct_size != sizeof(amenv_rotor_lag)) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: struct_size must be sizeof(amenv_rotor_lag)");
-  if (v.n_joints > 0) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: built for rigid vehicles (the arm kernels are not built with it)");
-  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: built for rigid vehicles with 4 or 6 rotors");
-  if (e->family == StepFamily::Quad)
-    return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
-                "use the lane or helper kernel");
+  if (int rc = rigid_switch_served(e, "amenv_set_rotor_lag", false)) return rc;
   for (int r = 0; r < v.n_rotors; r++)
     if (!(v.t_min[r] >= 0.0)) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_lag: every t_min must be >= 0 (the rotor state is the square root of a thrust)");
   const double tau[2] = {lag->tau_up, lag->tau_down};
@@ -1250,18 +1233,7 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
 }
 
 namespace {
-// What amenv_set_action_delay and amenv_set_action_history serve (one set: the history IS the delay's side buffer), and that buffer's one
-// allocation.  who: the entry point, for the messages.  AMENV_OK, or the failure already recorded in the handle.
-int delay_served(amenv* e, const std::string& who) {
-  const amenv_vehicle& v = e->cfg.vehicle;
-  if (v.n_joints > 0 || e->pub_nj > 0) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles (the arm kernels are not built with it)");
-  if (v.n_rotors != 4 && v.n_rotors != 6) return fail(e, AMENV_ERR_INVALID, who + ": built for rigid vehicles with 4 or 6 rotors");
-  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, who + ": fp32 handles only (the fp64 builds are logic gates of the dynamics)");
-  if (e->family == StepFamily::Quad)
-    return fail(e, AMENV_ERR_INVALID, who + ": the lane-quad step kernel (step_kernel = AMENV_KERNEL_TEAM on a rigid vehicle) is not built with it; "
-                "use the lane or helper kernel");
-  return AMENV_OK;
-}
+// The side buffer of amenv_set_action_delay and amenv_set_action_history (one: the history IS the delay's buffer): its one allocation.
 int delay_buffer(amenv* e, const std::string& who) {   // (under a DeviceGuard)
   if (e->delay_h) return AMENV_OK;
   const size_t n_pad = size_t(e->n_tiles) * 64;
@@ -1284,7 +1256,7 @@ int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
   if (z->struct_size != sizeof(amenv_action_delay)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: struct_size must be sizeof(amenv_action_delay)");
   if (z->min_steps < 0 || z->min_steps > z->max_steps || z->max_steps > AMENV_MAX_ACTION_DELAY)
     return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: need 0 <= min_steps <= max_steps <= AMENV_MAX_ACTION_DELAY (8)");
-  if (int rc = delay_served(e, "amenv_set_action_delay")) return rc;
+  if (int rc = rigid_switch_served(e, "amenv_set_action_delay", true)) return rc;
   DeviceGuard g(e->device);
   if (int rc = delay_buffer(e, "amenv_set_action_delay")) return rc;   // first enable: the one allocation
   const bool was_on = e->delay;
@@ -1306,7 +1278,7 @@ int amenv_set_action_history(amenv* e, int32_t rows) {
     e->kname = kernel_name(*e);
     return AMENV_OK;
   }
-  if (int rc = delay_served(e, "amenv_set_action_history")) return rc;
+  if (int rc = rigid_switch_served(e, "amenv_set_action_history", true)) return rc;
   DeviceGuard g(e->device);
   if (int rc = delay_buffer(e, "amenv_set_action_history")) return rc;   // the delay's side buffer IS the history
   if (!e->hist_obs) {

@@ -453,15 +453,13 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 // NOISE: sensor noise on the observation rows, built together with DR only, fp32 only.
 // DELAY: per-episode actuation latency, built together with DR only, fp32 only; the row given d steps ago is loaded from the
 // handle's side buffer in place of the given one, which enters the buffer after the step.
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
+template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYN = 0>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
-  static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
-  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
-  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
-  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
+                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DYN> DA) {
+  static_assert(dyn_admitted<T, NJ>(DYN), "a switch set that is not built (amenv_model.hpp)");
+  constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
 #ifdef AMENV_STAMPS
   unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -572,14 +570,13 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 // DELAY: the waves that integrate load the same delayed row before the barrier; the main wave alone stores, after it.  In the
 // 256-thread form the reset wave draws the next episode's d for every lane and leaves it in LDS (no Philox on the main wave); in the
 // 128-thread form the main wave draws it on its episode-end path.
-template <typename T, int NROT, int KW, int VAR, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
+template <typename T, int NROT, int KW, int VAR, unsigned DYN = 0>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                      const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
-  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
-  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
-  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
+                                                      const DynArg<T, NROT, DYN> DA) {
+  static_assert(dyn_admitted<T, 0>(DYN), "a switch set that is not built (amenv_model.hpp)");
+  constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, 0>::value;
   constexpr bool kObsWave = KW == 1 && VAR == VAR_V2;              // launched with 256 threads then, else with 128
   const Head hd{blob, tile_bytes, n_envs};
@@ -1004,15 +1001,13 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
 // LAG: the rotor states stay in registers over the steps, restart at w0 after an auto-reset and are stored once at the end.
 // NOISE: every row is formed from a perturbed copy of the state, as in step_kernel.
 // DELAY: every step goes through the side buffer as in step_kernel (its own word and slots: a lane's accesses are in order).
-template <typename T, int NROT, int KW, int VAR, int NJ, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
+template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYN = 0>
 __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, int n_steps, const StepTail tl, const HotParams<T, NROT> P,
-                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DR, LAG, NOISE, DELAY> DA) {
-  static_assert(!DR || NJ == 0, "dynamics randomisation is built for rigid vehicles");
-  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
-  static_assert(!NOISE || (DR && sizeof(T) == 4), "sensor noise is built together with the randomisation switch, fp32 only");
-  static_assert(!DELAY || (DR && sizeof(T) == 4), "the actuation latency is built together with the randomisation switch, fp32 only");
+                                                      const ColdParams C, const ArmArg<T, NJ> AA, const DynArg<T, NROT, DYN> DA) {
+  static_assert(dyn_admitted<T, NJ>(DYN), "a switch set that is not built (amenv_model.hpp)");
+  constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
   const Head hd{blob, tile_bytes, n_envs};
   const StepIO io{actions, obs, reward_out, done, info, nullptr, nullptr, nullptr, tl.stats};

@@ -162,11 +162,11 @@ __device__ __forceinline__ Deriv<T> rhs(const PT& P, T vx, T vy, T vz, T qw, T q
 // Ranges travel as a kernel argument of their own, in the DR instantiations only (HotParams is at its SGPR budget).  A factor is
 // lo + span * u, span = hi - lo, all in fp32 (the library is built with -ffp-contract=off: a multiply, then an add).
 struct DrRanges { float lo[3], span[3]; };   // [0] mass, [1] inertia, [2] thrust (one draw per rotor)
-template <bool DR> struct DrArg { DrRanges r; };
+template <bool ON> struct DrArg { DrRanges r; };
 template <> struct DrArg<false> { int unused; };
 // Per-lane factors of the lane's current episode, drawn once per launch (and again after an auto-reset inside a rollout); empty when off.
 // F = sum s_r t_r and M = mixm (s . t); translational acceleration F / (km m); rotational J (M / kI - w x I w).
-template <typename T, int NROT, bool DR> struct DynFac {};
+template <typename T, int NROT, bool ON> struct DynFac {};
 template <typename T, int NROT> struct DynFac<T, NROT, true> {
   T s[NROT];        // thrust factor per rotor
   T inv_mass;       // 1 / (km m)
@@ -182,7 +182,7 @@ template <typename T, int NROT> struct DynFac<T, NROT, true> {
 // values w0[NROT] behind them (read on the reset path only); the buffer and the two coefficients
 // travel in a kernel argument of their own, in the LAG instantiations only (HotParams is at its SGPR budget: the fp64 helper-wave kernel
 // has no scalar register left for w0[]).  LAG is built only together with DR (unit ranges when randomisation is off).
-template <typename T, int NROT, bool LAG> struct LagArg { int unused; };
+template <typename T, int NROT, bool ON> struct LagArg { int unused; };
 template <typename T, int NROT> struct LagArg<T, NROT, true> {
   T* w;              // [n_pad / 64][NROT][64] rotor states | [NROT] w0: rotors at the nominal hover command
   uint32_t n_pad;    // the handle's padded env count (whole tiles)
@@ -192,7 +192,7 @@ template <typename T, int NROT> struct LagArg<T, NROT, true> {
 // Four standard deviations (position m, velocity m/s, body rate rad/s, attitude rad); they travel behind the lag's fields in the NOISE
 // instantiations only.  NOISE is built only together with DR (unit ranges when randomisation is off), fp32 only.
 struct NoiseSig { float p, v, w, a; };
-template <bool NOISE> struct NoiseArg { static constexpr bool on = false; static constexpr int lds_ne = 0; };
+template <bool ON> struct NoiseArg { static constexpr bool on = false; static constexpr int lds_ne = 0; };
 template <> struct NoiseArg<true> {
   static constexpr bool on = true; static constexpr int lds_ne = 0;
   NoiseSig s;
@@ -212,7 +212,7 @@ template <int NE> struct NoiseLds {
 // dword x4 access, a wave 1 KiB), and behind them one word per env, int32 [n_pad]: d | head << 4.  The ring is ordered by a head index of its
 // own (the slot the next given row goes to), never by the env's step field: the row given k + 1 steps ago sits in slot (head - 1 - k) & 7.
 // The fields travel behind the noise's in the DELAY instantiations only.  DELAY is built only together with DR, fp32 only.
-template <bool DELAY> struct DelayArg { static constexpr bool on = false; };
+template <bool ON> struct DelayArg { static constexpr bool on = false; };
 template <> struct DelayArg<true> {
   static constexpr bool on = true;
   float4* h;           // [n_pad / 64][8][64] given rows | int32 [n_pad] d | head << 4
@@ -228,33 +228,66 @@ struct HistRows {
   __device__ __forceinline__ void hover() { g0 = g1 = make_float4(1.0f, 0.0f, 0.0f, 0.0f); }
 };
 struct NoHist { static constexpr bool on = false; };
-// The one kernel argument that carries the switches: DrArg's bytes unless LAG, NOISE or DELAY (the kernels without them keep their argument segment).
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE = false, bool DELAY = false> struct DynArg { DrArg<DR> R; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, false, false> { DrArg<true> R; LagArg<T, NROT, true> L; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, false, true, false> { DrArg<true> R; NoiseArg<true> Z; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, true, false> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, false, false, true> { DrArg<true> R; DelayArg<true> D; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, false, true> { DrArg<true> R; LagArg<T, NROT, true> L; DelayArg<true> D; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, false, true, true> { DrArg<true> R; NoiseArg<true> Z; DelayArg<true> D; };
-template <typename T, int NROT> struct DynArg<T, NROT, true, true, true, true> { DrArg<true> R; LagArg<T, NROT, true> L; NoiseArg<true> Z; DelayArg<true> D; };
-template <typename T, int NROT, bool DR, bool LAG, bool NOISE, bool DELAY>
-__host__ __device__ __forceinline__ NoiseArg<NOISE> noise_of(const DynArg<T, NROT, DR, LAG, NOISE, DELAY>& a) {
-  if constexpr (NOISE) return a.Z; else return NoiseArg<false>{};
+// ---- the switch set ---------------------------------------------------------------------------------------------
+// One template parameter names the opt-in features a kernel is built with: a mask of these bits.
+constexpr unsigned kDynDr = 1, kDynLag = 2, kDynNoise = 4, kDynDelay = 8, kDynAll = 15;
+// The build rule, stated once: LAG, NOISE and DELAY are built only together with DR (unit ranges when randomisation is off); NOISE and
+// DELAY are fp32 only; every switch is built for rigid vehicles only.
+template <typename T, int NJ> constexpr bool dyn_admitted(unsigned dyn) {
+  return dyn <= kDynAll && (dyn == 0 || NJ == 0) && (!(dyn & (kDynLag | kDynNoise | kDynDelay)) || (dyn & kDynDr)) &&
+         (!(dyn & (kDynNoise | kDynDelay)) || sizeof(T) == 4);
 }
+// The one kernel argument that carries the switches: the ranges (an unused word when DR is off: the kernels without switches keep their
+// argument segment), behind them the lag's block, the noise's sigmas and the latency's fields, each only in the sets that have its bit.
+// A part that is off is an empty base; a part that is on is a plain aggregate, so the next one starts behind its padded end.
+template <bool ON> struct DynPartR { DrArg<ON> R; };
+template <typename T, int NROT, bool ON> struct DynPartL {};
+template <typename T, int NROT> struct DynPartL<T, NROT, true> { LagArg<T, NROT, true> L; };
+template <bool ON> struct DynPartZ {};
+template <> struct DynPartZ<true> { NoiseArg<true> Z; };
+template <bool ON> struct DynPartD {};
+template <> struct DynPartD<true> { DelayArg<true> D; };
+template <typename T, int NROT, unsigned DYN>
+struct DynArg : DynPartR<(DYN & kDynDr) != 0>, DynPartL<T, NROT, (DYN & kDynLag) != 0>, DynPartZ<(DYN & kDynNoise) != 0>, DynPartD<(DYN & kDynDelay) != 0> {};
+template <typename T, int NROT, unsigned DYN>
+__host__ __device__ __forceinline__ NoiseArg<(DYN & kDynNoise) != 0> noise_of(const DynArg<T, NROT, DYN>& a) {
+  if constexpr ((DYN & kDynNoise) != 0) return a.Z; else return NoiseArg<false>{};
+}
+// The argument bytes are those of a struct with the parts that are on as plain members: each part at the next multiple of its alignment
+// behind the part before it.  Size and alignment are pinned here; the offsets follow from the holders being plain aggregates, whose tail
+// padding (LagArg<float>'s) the ABI gives to no later base -- the size alone would not tell where the alignment rounds it up anyway.
+template <typename P> constexpr void dyn_member(bool on, size_t& end, size_t& align) {
+  if (on) { end = (end + alignof(P) - 1) / alignof(P) * alignof(P) + sizeof(P); align = alignof(P) > align ? alignof(P) : align; }
+}
+template <typename T, int NROT, unsigned DYN = 0> constexpr bool dyn_layouts_ok() {   // DYN and every admitted set above it
+  if constexpr (DYN > kDynAll) return true;
+  else if constexpr (!dyn_admitted<T, 0>(DYN)) return dyn_layouts_ok<T, NROT, DYN + 1>();
+  else {
+    using A = DynArg<T, NROT, DYN>;
+    size_t end = 0, align = 1;
+    dyn_member<DrArg<(DYN & kDynDr) != 0>>(true, end, align);
+    dyn_member<LagArg<T, NROT, true>>(DYN & kDynLag, end, align);
+    dyn_member<NoiseArg<true>>(DYN & kDynNoise, end, align);
+    dyn_member<DelayArg<true>>(DYN & kDynDelay, end, align);
+    return sizeof(A) == (end + align - 1) / align * align && alignof(A) == align && std::is_trivially_copyable<A>::value && dyn_layouts_ok<T, NROT, DYN + 1>();
+  }
+}
+static_assert(dyn_layouts_ok<float, 4>() && dyn_layouts_ok<float, 6>() && dyn_layouts_ok<double, 4>() && dyn_layouts_ok<double, 6>() && dyn_layouts_ok<float, AMENV_MAX_ROTORS>() &&
+              dyn_layouts_ok<double, AMENV_MAX_ROTORS>(), "a DynArg has the size and alignment of its parts as plain members of one struct");
 // env i's rotor r sits at lag_slot(i) + 64 r
 template <int NROT> __device__ __forceinline__ size_t lag_slot(int i) { return size_t(i >> 6) * (NROT * 64) + size_t(i & 63); }
 // What dynamics() filters through: get(r) / set(r, w') and the two coefficients.  LagLane keeps the rotor states in the lane's registers
 // (empty when off); LagLds keeps them in an LDS column of the lane's own, [2 NROT + 2][NE] floats, for the closed-loop kernel whose NORM
 // forms have no VGPR to spare: one rotor's state is in a register at a time, and the randomisation's per-lane factors (s_r, 1 / (km m),
 // 1 / kI) sit in the same column instead of in DynFac's registers (holds_s), which is what makes the room.
-template <typename T, int NROT, bool LAG> struct LagLane { static constexpr bool on = false, holds_s = false; };
+template <typename T, int NROT, bool ON> struct LagLane { static constexpr bool on = false, holds_s = false; };
 template <typename T, int NROT> struct LagLane<T, NROT, true> {
   static constexpr bool on = true, holds_s = false;
   T w[NROT]; T a_up, a_down;
   __device__ __forceinline__ T get(int r) const { return w[r]; }
   __device__ __forceinline__ void set(int r, T v) { w[r] = v; }
 };
-template <int NROT, int NE, bool LAG> struct LagLds { static constexpr bool on = false, holds_s = false; };
+template <int NROT, int NE, bool ON> struct LagLds { static constexpr bool on = false, holds_s = false; };
 template <int NROT, int NE> struct LagLds<NROT, NE, true> {
   static constexpr bool on = true, holds_s = true;
   float* col; float a_up, a_down;   // col: &wl[env within the workgroup]; rows 0..NROT-1 w_r, rows NROT.. s_r, then 1 / (km m), 1 / kI

@@ -41,14 +41,13 @@ struct NormArg {
 // DELAY: per-episode actuation latency: the clipped sample is the GIVEN row; the row given d steps ago is applied.  Nothing of the
 // history is held in registers over a step: the env's word and one slot are loaded from the handle's (L2-resident) side buffer in front of
 // the dynamics, one slot and the word are stored behind them.  `actions` and `logp` record the policy's own samples.
-template <int NROT, int KW, int VAR, bool NORM, int NE, bool DR = false, bool LAG = false, bool NOISE = false, bool DELAY = false>
+template <int NROT, int KW, int VAR, bool NORM, int NE, unsigned DYN = 0>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
                                                                                          const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
-                                                                                         const DynArg<float, NROT, DR, LAG, NOISE, DELAY> DA) {
-  static_assert(!LAG || DR, "the rotor lag is built together with the randomisation switch");
-  static_assert(!NOISE || DR, "sensor noise is built together with the randomisation switch");
-  static_assert(!DELAY || DR, "the actuation latency is built together with the randomisation switch");
+                                                                                         const DynArg<float, NROT, DYN> DA) {
+  static_assert(dyn_admitted<float, 0>(DYN), "a switch set that is not built (amenv_model.hpp)");
+  constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
