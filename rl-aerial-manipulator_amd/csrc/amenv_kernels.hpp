@@ -191,10 +191,9 @@ __device__ __forceinline__ void flush_obs_hist(const float* lds, float* __restri
     if (t < nflt) obs_block[t] = lds[t];
   }
 }
-// one row written by its own lane (terminal rows, post-reset rows of the helper-wave kernel)
+// one row written by its own lane (terminal rows, post-reset rows of the helper-wave kernel): float4 stores where every row is 16-byte aligned
 template <int OD>
-__device__ __forceinline__ void store_row_hist(float* __restrict__ rows, int i, const float* o, const HistRows& hr) {
-  float* t = rows + size_t(i) * (OD + 4 * hr.n);
+__device__ __forceinline__ void store_row(float* t, const float* o) {
   if constexpr (OD % 4 == 0) {
 #pragma unroll
     for (int j = 0; j < OD / 4; j++) reinterpret_cast<float4*>(t)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
@@ -202,6 +201,12 @@ __device__ __forceinline__ void store_row_hist(float* __restrict__ rows, int i, 
 #pragma unroll
     for (int j = 0; j < OD; j++) t[j] = o[j];
   }
+}
+// the same with the DELAY forms' history rows behind it (row pitch OD + 4 n)
+template <int OD>
+__device__ __forceinline__ void store_row_hist(float* __restrict__ rows, int i, const float* o, const HistRows& hr) {
+  float* t = rows + size_t(i) * (OD + 4 * hr.n);
+  store_row<OD>(t, o);
   hist_put<OD % 4 == 0>(t + OD, hr);
 }
 
@@ -380,14 +385,7 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
         if constexpr (HX::on) {   // DELAY forms: the row's pitch follows the history, whose rows end it -- as they are before the reset wipes them
           if (!kLazyObs && io.terminal_obs) store_row_hist<OD>(io.terminal_obs, i, o, *hx);
         } else if (!kLazyObs && io.terminal_obs) {   // two-wave kernel: the terminal observation is the row the helper wave staged; copied after the barrier
-          float* t = io.terminal_obs + size_t(i) * OD;
-          if constexpr (OD % 4 == 0) {
-#pragma unroll
-            for (int j = 0; j < OD / 4; j++) reinterpret_cast<float4*>(t)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
-          } else {
-#pragma unroll
-            for (int j = 0; j < OD; j++) t[j] = o[j];
-          }
+          store_row<OD>(io.terminal_obs + size_t(i) * OD, o);
         }
         if constexpr (!kColdElsewhere) {
           if (io.ep_return) io.ep_return[i] = ep_ret_out;

@@ -181,15 +181,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
         v[j] = o[j];
       }
     }
-    if (active) {
-      if constexpr (OD % 4 == 0) {
-#pragma unroll
-        for (int j = 0; j < OD / 4; j++) reinterpret_cast<float4*>(grow)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < OD; j++) grow[j] = v[j];
-      }
-    }
+    if (active) store_row<OD>(grow, v);
     __bf16* xr = xin + el * kXS;
     __bf16* xl = xlo + el * kXS;
 #pragma unroll

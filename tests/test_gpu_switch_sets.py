@@ -144,3 +144,33 @@ def test_closed_loop_runs_its_switch_set(form, c):
     if c & L:
         assert bool((a["w"] != start["w"]).any(dim=1).all())
     env.close(); ref.close()
+
+
+def test_rollout_with_history_and_lag_equals_steps():
+    """amenv_rollout with the action history beside the rotor lag, on a handle of the helper form: the one combination of this file's
+    kernels that nothing else launches (the history's own rollout tests run without the lag).  The rows of a T-step rollout, history
+    columns included, and every side state are those of T steps on a twin handle, across an episode end that a further step follows
+    (one-step time limit).  The history columns are the given rows; hover rows where the episode is younger."""
+    def make():
+        return amd.GpuWaypointEnv(N, seed=3, env_id_offset=500, max_episode_steps=1, **FORMS["hexa"], randomization=amd.DynamicsRandomization(mass=(1.5, 1.5)),
+                                  rotor_lag=amd.RotorLag(0.03, 0.05), action_delay=amd.ActionDelay(0, 2), action_history=amd.ActionHistory(2))
+    a, b = make(), make()
+    a.reset(); b.reset()
+    assert " +lag" in a.kernel_name and " +delay" in a.kernel_name and " +history 2" in a.kernel_name, a.kernel_name
+    g = _given()[:T].cuda()
+    hover = HOVER.cuda().expand(N, 4)
+    ro = a.rollout(g)
+    assert ro["obs"].shape == (T, N, 28)
+    fresh = torch.ones(N, dtype=torch.bool, device="cuda")         # no row was given in the env's episode before this step
+    for t in range(T):
+        o, r, d, i = b.step(g[t])
+        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
+        new = d.bool()[:, None]                                      # (auto-reset: the row is the new episode's first)
+        assert torch.equal(o[:, 20:24], torch.where(new, hover, g[t])), t
+        before = g[t - 1] if t > 0 else hover                       # (t = 0: every env is fresh)
+        assert torch.equal(o[:, 24:28], torch.where(new | fresh[:, None], hover, before)), t
+        fresh = d.bool()
+    assert bool(ro["done"][:-1].any()) and not bool(ro["done"].all())   # an episode end with a step behind it, and steps that end none
+    sa, sb = _snap(a, L | D), _snap(b, L | D)
+    assert _same(sa, sb, tuple(sa))
+    a.close(); b.close()
