@@ -30,6 +30,16 @@ def both_step(env, orc, a):
     return g, orc.step(a)
 
 
+def reward_flips(g, o, ok, dtype):
+    """Rewards of the envs in ok against the oracle's: 5e-5 of max(1, |r|) on fp32, 1e-9 on fp64.  An env sitting on the `progress > 0` threshold
+    of the +2 bonus (v2/rl_env_scaledObs.py:214-218) may differ by exactly that bonus: the number of such envs is returned, every other
+    difference fails."""
+    dr = np.abs(g["reward"] - o["reward"])
+    off = ok & ~(dr / np.maximum(1.0, np.abs(o["reward"])) < (5e-5 if dtype == "f32" else 1e-9))
+    assert (np.abs(dr[off] - 2.0) < 1e-3).all(), (np.nonzero(off)[0], g["reward"][off], o["reward"][off])
+    return int(off.sum())
+
+
 def rand_actions(rng, n, scale=0.05):
     a = rng.uniform([0.6, -1, -1, -1, -1, -1, -1], [1.4, 1, 1, 1, 1, 1, 1], (n, 7)).astype(np.float32)
     a[:, 1:4] *= scale
@@ -117,7 +127,7 @@ def test_arm_closed_loop_vs_oracle(dtype, tol, kernel):
     f[6:10] = q; f[10:13] = rng.normal(0, 1.0, (3, n)); f[3:6] = rng.normal(0, 0.5, (3, n))
     f[19:22] = rng.uniform(-1, 1, (3, n)); f[22:25] = rng.normal(0, 1.0, (3, n))
     env.set_state(f if dtype == "f64" else f.astype(np.float32), i)
-    worst = 0.0; flips = 0; dones = 0; worst_obs = 0.0
+    worst = 0.0; flips = 0; dones = 0; worst_obs = 0.0; bonus_flips = 0
     for t in range(150):
         a = rand_actions(rng, n)
         a[::9, 0] = 0.0
@@ -126,6 +136,7 @@ def test_arm_closed_loop_vs_oracle(dtype, tol, kernel):
         bad = np.nonzero((g["info"] & 127) != (o["info"] & 127))[0]
         flips += len(bad)
         ok = np.ones(n, bool); ok[bad] = False
+        bonus_flips += reward_flips(g, o, ok, dtype)
         nd = ok & (o["done"] == 0)
         rows = np.r_[0:15, 16:25]   # everything but the running episode return (row 15: reward-threshold flips accumulate there)
         worst = max(worst, rel_err(f2[rows][:, nd], orc.fstate[rows][:, nd]).max())
@@ -137,6 +148,7 @@ def test_arm_closed_loop_vs_oracle(dtype, tol, kernel):
     report_flips(f"test_arm_closed_loop_vs_oracle[{dtype}-{kernel}] (flag bits vs the oracle, env-steps)", flips, 150 * n)
     assert worst < tol, worst
     assert worst_obs < max(tol, 1.3e-7) and flips <= 4 and dones > 100, f"obs {worst_obs}, {flips} threshold flips in {150 * n} env-steps, {dones} episode ends"
+    assert bonus_flips <= 1e-4 * n * 150 + 1, bonus_flips
     env.close()
 
 
@@ -603,7 +615,7 @@ def test_n_link_arm_with_fewer_joints(nj, dtype, kernel, tol):
     f[6:10] = q; f[10:13] = rng.normal(0, 1.0, (3, n)); f[3:6] = rng.normal(0, 0.5, (3, n))
     f[19:19 + nj] = rng.uniform(-1, 1, (nj, n)); f[19 + nj:19 + 2 * nj] = rng.normal(0, 1.0, (nj, n))
     env.set_state(f if dtype == "f64" else f.astype(np.float32), i)
-    worst = 0.0; worst_obs = 0.0; flips = 0; dones = 0
+    worst = 0.0; worst_obs = 0.0; flips = 0; dones = 0; bonus_flips = 0
     for t in range(130):
         a = rng.uniform([0.6] + [-1] * (3 + nj), [1.4] + [1] * (3 + nj), (n, 4 + nj)).astype(np.float32)
         a[:, 1:4] *= 0.05
@@ -613,6 +625,7 @@ def test_n_link_arm_with_fewer_joints(nj, dtype, kernel, tol):
         bad = np.nonzero((g["info"] & 127) != (o["info"] & 127))[0]
         flips += len(bad)
         ok = np.ones(n, bool); ok[bad] = False
+        bonus_flips += reward_flips(g, o, ok, dtype)
         nd = ok & (o["done"] == 0)
         rows = np.r_[0:15, 16:19 + 2 * nj]
         if nd.any():            # (at the time limit every env that has not crashed yet ends in the same step)
@@ -625,6 +638,7 @@ def test_n_link_arm_with_fewer_joints(nj, dtype, kernel, tol):
             tob = env.terminal_obs.cpu().numpy()
             assert np.isfinite(tob[dn]).all() and tob.shape[1] == 23 + 2 * nj
     assert worst < tol and worst_obs < max(tol, 1.3e-7) and flips <= 3 and dones > 50, (worst, worst_obs, flips, dones)
+    assert bonus_flips <= 1e-4 * n * 130 + 1, bonus_flips
     with pytest.raises(amd.AmenvError, match="1 or 2 joints|logic gate"):
         env.rollout(torch.zeros(2, n, 4 + nj, device="cuda"))
     env.close()
@@ -658,7 +672,7 @@ def test_arm_with_several_waypoints(K, dtype, tol):
     f[j0:j0 + 3] = rng.uniform(-0.5, 0.5, (3, n)); f[j0 + 3:j0 + 6] = rng.normal(0, 0.5, (3, n))
     f[0:3, ~park] += rng.normal(0, 0.05, (3, int((~park).sum())))
     env.set_state(f if dtype == "f64" else f.astype(np.float32), i)
-    worst = 0.0; worst_obs = 0.0; flips = 0; switched = 0; dones = 0
+    worst = 0.0; worst_obs = 0.0; flips = 0; switched = 0; dones = 0; bonus_flips = 0
     for t in range(140):
         a = rand_actions(rng, n)
         a[::9, 0] = 0.0
@@ -667,6 +681,7 @@ def test_arm_with_several_waypoints(K, dtype, tol):
         bad = np.nonzero((g["info"] & 127) != (o["info"] & 127))[0]
         flips += len(bad)
         ok = np.ones(n, bool); ok[bad] = False
+        bonus_flips += reward_flips(g, o, ok, dtype)
         nd = ok & (o["done"] == 0)
         rows = np.r_[0:15, 16:16 + 3 * K + 6]
         if nd.any():
@@ -677,6 +692,7 @@ def test_arm_with_several_waypoints(K, dtype, tol):
         dones += int(dn.sum())
         assert np.array_equal(f2[:, dn], orc.fstate[:, dn]) and np.array_equal(i2[:, ok], orc.istate[:, ok])
     assert worst < tol and worst_obs < max(tol, 1.3e-7) and flips <= 3 and switched > 1000 and dones > 50, (worst, worst_obs, flips, switched, dones)
+    assert bonus_flips <= 1e-4 * n * 140 + 1, bonus_flips
     for kernel in ("team", "staged", "helper"):
         with pytest.raises(amd.AmenvError):
             amd.GpuWaypointEnv(64, vehicle="hexa_arm", num_waypoints=K, kernel=kernel)

@@ -1,0 +1,203 @@
+"""Every step-kernel family on every branch of the step state machine, against the fp64 oracle (`pytest -m gpu`).
+
+The state machine (`task_step`, csrc/amenv_model.hpp) is one piece of code, but each family feeds it and publishes its results through plumbing of
+its own (DPP broadcasts and an episode-end helper wave in the lane-team kernel, LDS hand-overs in the stage-wave, two-wave, lane-quad and
+helper-wave kernels, the inline episode-end path in the rollout kernels).  Here each family starts from the blob of tests/state_blob.py -- envs
+in the hold phase with counters on both sides of counter_limit, first arrivals, crashes sinking and rising, out of bounds, the time limit,
+both signs of the progress bonus -- and every output of six teacher-forced steps is compared with the oracle's by `state_blob.compare`
+(gates in that file's docstring); then amenv_rollout and amenv_rollout_policy from the same states against amenv_step, bit for bit.
+
+tests/test_state_blob_cpu.py checks on the oracle alone that these states reach every branch and that the envs a flip could be excused on
+number no more than the cap."""
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from tests import golden_util as G
+from tests import state_blob as B
+from tests.test_state_blob_cpu import ACTION_SEED, ENV_SEED, RESEAT_SEED, ROLLOUT_STEPS, STEPS, start_state
+
+pytestmark = pytest.mark.gpu
+
+ENV_KW = {"hexa_arm": dict(vehicle="hexa_arm"), "hexa_arm_2j": dict(vehicle="hexa_arm", n_joints=2), "hexa_arm_base": dict(vehicle="hexa_arm", ee_task="base"),
+          "hexa": dict(vehicle="hexa"), "quad": dict(vehicle="quad")}
+
+
+def make_env(vehicle, n, dtype="f32", kernel="auto", **kw):
+    import rl_aerial_manipulator_amd as amd
+    return amd.GpuWaypointEnv(n, seed=ENV_SEED, dtype=dtype, kernel=kernel, **ENV_KW[vehicle], **kw)
+
+
+def seat(env, vehicle, n, dtype="f32"):
+    cfg, fs, is_ = start_state(vehicle, n, dtype)
+    env.set_state(fs.copy(), is_.copy())
+    return cfg, fs, is_
+
+
+def gpu_state(env):
+    import torch
+    f, i = env.get_state()
+    torch.cuda.synchronize()
+    return f.cpu().numpy().astype(np.float64), i.cpu().numpy()
+
+
+def gpu_step(env, a):
+    """One amenv_step with every output; the per-episode rows hold a sentinel first, so that a row written for an env that did not end shows."""
+    import torch
+    env.terminal_obs.fill_(float("nan")); env.ep_return.fill_(float("nan")); env.ep_len.fill_(-1)
+    obs, rew, done, info = env.step(torch.from_numpy(a).cuda())
+    torch.cuda.synchronize()
+    g = dict(obs=obs.cpu().numpy().copy(), reward=rew.cpu().numpy().astype(np.float64), done=done.cpu().numpy().copy(),
+             info=info.cpu().numpy().view(np.uint32).copy(), terminal_obs=env.terminal_obs.cpu().numpy().copy(),
+             ep_return=env.ep_return.cpu().numpy().copy(), ep_len=env.ep_len.cpu().numpy().copy())
+    g["fstate"], g["istate"] = gpu_state(env)
+    return g
+
+
+# (vehicle, kernel, dtype, n, substrings of kernel_name, substring that must be absent)
+SWEEP = [
+    ("hexa_arm", "team", "f32", 300, ("step_kernel_team<float", "helper wave per 4"), None),       # 16-env workgroups: four whole tiles and a ragged one
+    ("hexa_arm", "team", "f32", 4100, ("step_kernel_team<float", "episode-end helper wave"), "per 4"),   # past 64 tiles: one integrating wave per helper
+    ("hexa_arm", "team", "f64", 300, ("step_kernel_team<double",), None),
+    ("hexa_arm", "staged", "f32", 300, ("step_kernel_armk<float",), None),
+    ("hexa_arm", "staged", "f64", 300, ("step_kernel_armk<double",), None),
+    ("hexa_arm", "helper", "f32", 300, ("step_kernel_arm2w",), None),
+    ("hexa_arm", "lane", "f32", 300, ("step_kernel<float", "arm3"), None),
+    ("hexa_arm", "lane", "f64", 300, ("step_kernel<double", "arm3"), None),
+    ("hexa_arm_2j", "team", "f32", 300, ("step_kernel_team<float", "2-joint arm"), None),          # the caller's row widths through the pack / unpack kernels
+    ("hexa_arm_base", "team", "f32", 300, ("step_kernel_team<float",), None),                      # the other task point
+    ("hexa", "helper", "f32", 300, ("step_kernel_pw<float,NROT=6",), None),
+    ("hexa", "lane", "f64", 300, ("step_kernel<double,NROT=6",), None),
+    ("hexa", "team", "f32", 300, ("step_kernel_quad<NROT=6",), None),
+    ("quad", "team", "f32", 300, ("step_kernel_quad<NROT=4",), None),
+    ("quad", "helper", "f32", 300, ("step_kernel_pw<float,NROT=4",), None),
+]
+
+
+@pytest.mark.parametrize("vehicle,kernel,dtype,n,names,absent", SWEEP, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in SWEEP])
+def test_every_branch_vs_oracle(vehicle, kernel, dtype, n, names, absent):
+    env = make_env(vehicle, n, dtype, kernel)
+    assert all(s in env.kernel_name for s in names) and (absent is None or absent not in env.kernel_name), env.kernel_name
+    cfg, _, _ = seat(env, vehicle, n, dtype)
+    rng, rng_ld = np.random.RandomState(ACTION_SEED), np.random.RandomState(RESEAT_SEED)
+    seen = {k: 0 for k in B.CLASSES}
+    worst = dict(state=0.0, reward=0.0, obs=0.0, ep_return=0.0, terminal_obs=0.0)
+    tot = dict(episodes=0, terminated=0, truncated=0, success=0, crashed=0, oob=0, length_sum=0)
+    flips = 0; ret_sum = ret_slack = 0.0
+    for t in range(STEPS):
+        if t:    # the last_distance a step leaves is the present distance: drawn afresh, or every slow env would sit on the progress threshold
+            f, i = gpu_state(env)
+            env.set_state(B.reseat_last_distance(cfg, f, rng_ld), i)
+        pre = gpu_state(env)                                        # teacher-forced: the oracle steps the state the handle holds
+        a = B.actions(cfg, pre[0], rng)
+        g = gpu_step(env, a)
+        o, post = B.oracle_step(cfg, pre, a)
+        r = B.compare(g, o, B.margins(cfg, pre, post), dtype)
+        print(f"step {t}:", {k: v for k, v in r.items() if k != "flipped"})
+        flips += r["flips"]
+        for k in worst:
+            worst[k] = max(worst[k], r[k])
+        for k, v in B.classes(cfg, pre, post).items():
+            seen[k] += int(v.sum())
+        d = o["done"] != 0
+        bits = o["info"][d]
+        tot["episodes"] += int(d.sum()); tot["terminated"] += int(((bits & O.INFO_TERMINATED) != 0).sum())
+        tot["truncated"] += int(((bits & O.INFO_TERMINATED) == 0).sum())
+        for k, b in (("success", O.INFO_SUCCESS), ("crashed", O.INFO_CRASHED), ("oob", O.INFO_OOB)):
+            tot[k] += int(((bits & b) != 0).sum())
+        tot["length_sum"] += int(o["ep_len"][d].sum())
+        ret_sum += float(o["ep_return"][d].astype(np.float64).sum())
+        # what the totals may differ by: the return gate and one unit of 2^-10 per episode; all of a flipped env's episode
+        ret_slack += float((B.RET_REL * np.maximum(1.0, np.abs(o["ep_return"][d]))).sum()) + int(d.sum()) / 1024.0
+        fl = r["flipped"]
+        ret_slack += float(np.nan_to_num(np.abs(o["ep_return"][fl])).sum() + np.nan_to_num(np.abs(g["ep_return"][fl])).sum())
+    G.report_flips(f"test_every_branch_vs_oracle[{vehicle}-{kernel}-{dtype}-{n}] (flag bits and rewards vs the oracle, env-steps)", flips, STEPS * n)
+    print("worst errors:", worst, "branches:", seen)
+    assert all(seen[k] >= 1 for k in B.CLASSES), seen
+    st = env.stats()
+    for k, v in tot.items():
+        slack = flips * (cfg.task.max_episode_steps + 3) if k == "length_sum" else flips
+        assert abs(st[k] - v) <= slack, (k, st[k], v, flips)
+    assert st["steps"] == STEPS * n and st["nonfinite"] == 0
+    assert abs(st["return_sum"] - ret_sum) <= ret_slack, (st["return_sum"], ret_sum, ret_slack)
+    env.close()
+
+
+def _arrived(is_):
+    return (is_[O.I_FLAGS] & O.FLAGBIT_FWR) != 0
+
+
+def _assert_hold_phase_reached(is_, info):
+    """info [T, n] uint32 of a run from the blob: envs that had arrived hold in the first step, and a hold ends by its counter."""
+    assert ((info[0] & O.INFO_SUCCESS) != 0)[_arrived(is_)].any()
+    assert (((info & O.INFO_SUCCESS) != 0) & ((info & O.INFO_TERMINATED) != 0)).any()
+
+
+@pytest.mark.parametrize("vehicle,kernel,name", [("hexa_arm", "team", "step_kernel_team"), ("hexa_arm", "lane", "step_kernel<float"),
+                                                 ("hexa", "helper", "step_kernel_pw"), ("quad", "team", "step_kernel_quad")])
+def test_rollout_from_the_blob_equals_steps(vehicle, kernel, name):
+    """amenv_rollout (its kernels carry their own episode-end path) == amenv_step launches, bit for bit, from states in the hold phase."""
+    import torch
+    n, T = 300, ROLLOUT_STEPS
+    e1, e2 = make_env(vehicle, n, kernel=kernel), make_env(vehicle, n, kernel=kernel)
+    assert name in e1.kernel_name
+    cfg, fs, is_ = seat(e1, vehicle, n)
+    seat(e2, vehicle, n)
+    rng = np.random.RandomState(ACTION_SEED)
+    at = torch.from_numpy(np.stack([B.actions(cfg, fs, rng) for _ in range(T)])).cuda()
+    ro = e1.rollout(at)
+    for t in range(T):
+        obs, rew, done, info = e2.step(at[t])
+        assert torch.equal(ro["obs"][t], obs) and torch.equal(ro["reward"][t], rew) and torch.equal(ro["done"][t], done) and torch.equal(ro["info_bits"][t], info), t
+    f1, i1 = e1.get_state(); f2, i2 = e2.get_state()
+    assert torch.equal(f1, f2) and torch.equal(i1, i2)
+    s1, s2 = e1.stats(), e2.stats()
+    assert s1 == s2 and s1["episodes"] == int(ro["done"].sum()) > 0 and s1["steps"] == T * n
+    _assert_hold_phase_reached(is_, ro["info_bits"].cpu().numpy().view(np.uint32))
+    e1.close(); e2.close()
+
+
+# (vehicle, the handle's settings, the twin's settings, substring of the twin's kernel_name): the twin runs the step kernel whose arithmetic the
+# closed-loop kernel of the handle carries
+POLICY = [("hexa_arm", dict(kernel="team"), dict(kernel="team"), "step_kernel_team"),                       # 16 lanes per env
+          ("hexa_arm", dict(kernel="lane"), dict(kernel="lane"), "step_kernel<float"),                      # one lane per env
+          ("quad", dict(), dict(kernel="team"), "step_kernel_quad<NROT=4"),                                # lane-quad form, whatever kernel amenv_step runs
+          ("hexa", dict(kernel="lane", block_size=64), dict(kernel="lane", block_size=64), "step_kernel<float,NROT=6")]   # a set workgroup size: one lane per env
+
+
+@pytest.mark.parametrize("vehicle,kw,twin_kw,twin_name", POLICY, ids=["hexa_arm-team", "hexa_arm-lane", "quad-lane_quad", "hexa-one_lane"])
+def test_closed_loop_rollout_from_the_blob_replays_through_steps(vehicle, kw, twin_kw, twin_name):
+    """amenv_rollout_policy from states in the hold phase: its recorded (clipped) actions through amenv_step on a twin handle give the same
+    observations, rewards, flags, terminal rows and final state bit for bit (both sides are the same fp32 arithmetic: no env is excused)."""
+    import torch
+    import rl_aerial_manipulator_amd as amd
+    n, T = 300, ROLLOUT_STEPS
+    env, twin = make_env(vehicle, n, **kw), make_env(vehicle, n, **twin_kw)
+    assert twin_name in twin.kernel_name, twin.kernel_name
+    cfg, fs, is_ = seat(env, vehicle, n)
+    seat(twin, vehicle, n)
+    od, ad, dev = env.obs_dim, env.act_dim, env.device
+    torch.manual_seed(5)
+    pol = amd.ActorCritic(od, ad).cuda().flatten_()
+    with torch.no_grad():
+        pol.log_std.data.fill_(-1.2)
+        pol.action_net.weight.mul_(30.0)
+    obs = torch.zeros(T + 1, n, od, device=dev); acts = torch.zeros(T, n, ad, device=dev)
+    logp = torch.zeros(T, n, device=dev); vals = torch.zeros(T, n, device=dev); rew = torch.zeros(T, n, device=dev)
+    dones = torch.zeros(T, n, dtype=torch.uint8, device=dev)
+    info = torch.full((T, n), -1, dtype=torch.int32, device=dev)                  # 0xFFFFFFFF
+    tobs = torch.full((T, n, od), float("nan"), device=dev)
+    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, obs=obs, actions=acts, logp=logp, values=vals, rewards=rew, dones=dones, info_bits=info, terminal_obs=tobs)
+    torch.cuda.synchronize()
+    for t in range(T):
+        twin.terminal_obs.fill_(float("nan"))
+        o, r, d, i = twin.step(torch.max(torch.min(acts[t], pol.action_high), pol.action_low))
+        assert torch.equal(o, obs[t + 1]) and torch.equal(r, rew[t]) and torch.equal(d, dones[t]) and torch.equal(i, info[t]), t
+        dn = d.bool()
+        assert torch.equal(twin.terminal_obs[dn], tobs[t][dn]) and bool(torch.isnan(tobs[t][~dn]).all()), t
+    f1, i1 = env.get_state(); f2, i2 = twin.get_state()
+    assert torch.equal(f1, f2) and torch.equal(i1, i2)
+    s1, s2 = env.stats(), twin.stats()
+    assert s1 == s2 and s1["episodes"] == int(dones.sum()) > 0
+    _assert_hold_phase_reached(is_, info.cpu().numpy().view(np.uint32))
+    env.close(); twin.close()

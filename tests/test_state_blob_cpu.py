@@ -1,0 +1,184 @@
+"""The oracle alone on the states of tests/test_gpu_branch_sweep.py: what that sweep relies on, checked where no GPU is needed.
+
+  1. Branch coverage: the blob of tests/state_blob.py reaches every branch of the step state machine on every vehicle, batch size and seed
+     the sweep uses -- at least 8 envs per branch in the first step of the 4100-env case, at least one over the six steps of a 300-env case
+     (and a hold-phase env and a hold termination within the four steps its rollout cases run).
+  2. The cap on threshold flips is a condition, not a measurement: in every step the envs the comparison WOULD excuse (oracle margin below
+     3e-5) number at most the cap, so a disagreement beyond them cannot hide behind it.
+  3. `compare` accepts the oracle against itself and rejects a copy changed in any one field it guards."""
+import copy
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import rl_aerial_manipulator_amd as amd
+from oracle import oracle as O
+from tests import state_blob as B
+from tests.test_arm_cpu import arm_cfg
+
+BLOB_SEED, ACTION_SEED, RESEAT_SEED, ENV_SEED = 11, 12, 13, 21
+STEPS, ROLLOUT_STEPS = 6, 4
+# (vehicle, n, dtype) of every state the sweep starts from
+STATES = [("hexa_arm", 300, "f32"), ("hexa_arm", 300, "f64"), ("hexa_arm", 4100, "f32"), ("hexa_arm_2j", 300, "f32"), ("hexa_arm_base", 300, "f32"),
+          ("hexa", 300, "f32"), ("hexa", 300, "f64"), ("quad", 300, "f32")]
+
+
+def oracle_cfg(vehicle, n):
+    """The oracle's config of a sweep vehicle: the package's vehicle parameters on the reference task, auto-reset on."""
+    if vehicle.startswith("hexa_arm"):
+        if vehicle == "hexa_arm_2j":
+            cfg = arm_cfg(n_joints=2, mass=amd._lib.default_config("hexa_arm", 1, n_joints=2).vehicle.mass)
+        else:
+            cfg = arm_cfg()
+        if vehicle == "hexa_arm_base":
+            cfg.task.ee_task = O.EE_TASK_BASE
+    else:
+        cfg = O.reference_quad_config(1)
+        if vehicle == "hexa":
+            C.memmove(C.byref(cfg.vehicle), C.byref(amd._lib.default_config("hexa", 1).vehicle), C.sizeof(O.Vehicle))
+    cfg.num_envs, cfg.seed, cfg.flags = n, ENV_SEED, O.FLAG_AUTO_RESET
+    return cfg
+
+
+@functools.lru_cache(maxsize=None)
+def start_state(vehicle, n, dtype):
+    """(cfg, fstate, istate): the blob of this vehicle and batch size as a handle of dtype holds it.  Shared: do not write to it."""
+    cfg = oracle_cfg(vehicle, n)
+    fs, is_ = B.blob(cfg, n, np.random.RandomState(BLOB_SEED))
+    if dtype == "f32":
+        fs = B.to_f32(fs)
+    fs.setflags(write=False); is_.setflags(write=False)
+    return cfg, fs, is_
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_run(vehicle, n, dtype):
+    """STEPS steps of the oracle alone, as the sweep runs them (last_distance drawn afresh between the steps): per step (pre, actions, o, post)."""
+    cfg, fs, is_ = start_state(vehicle, n, dtype)
+    rng, rng_ld = np.random.RandomState(ACTION_SEED), np.random.RandomState(RESEAT_SEED)
+    pre, run = (fs, is_), []
+    for t in range(STEPS):
+        a = B.actions(cfg, pre[0], rng)
+        o, post = B.oracle_step(cfg, pre, a)
+        run.append((pre, a, o, post))
+        f = B.reseat_last_distance(cfg, o["fstate"], rng_ld)
+        pre = (B.to_f32(f) if dtype == "f32" else f, o["istate"])
+    return cfg, run
+
+
+@pytest.mark.parametrize("vehicle,n,dtype", STATES)
+def test_blob_reaches_every_branch_and_the_flip_cap_is_a_condition(vehicle, n, dtype):
+    cfg, run = oracle_run(vehicle, n, dtype)
+    per_step = []
+    for t, (pre, a, o, post) in enumerate(run):
+        m = B.margins(cfg, pre, post)
+        n_el = int(B.eligible(m).sum())
+        assert n_el <= B.flip_cap(n), f"step {t}: {n_el} envs within {B.FLIP_MARGIN} of a threshold, the cap is {B.flip_cap(n)}"
+        per_step.append({k: int(v.sum()) for k, v in B.classes(cfg, pre, post).items()})
+        print(f"{vehicle} n={n} {dtype} step {t}: eligible {n_el}", per_step[-1])
+    assert set(per_step[0]) == set(B.CLASSES)
+    over = {k: sum(c[k] for c in per_step) for k in B.CLASSES}
+    assert all(over[k] >= 1 for k in B.CLASSES), over
+    if n >= 4096:
+        assert all(per_step[0][k] >= 8 for k in B.CLASSES), per_step[0]
+    head = {k: sum(c[k] for c in per_step[:ROLLOUT_STEPS]) for k in B.CLASSES}
+    assert per_step[0]["hold_level"] + per_step[0]["hold_tilted"] >= 1 and head["hold_terminated"] >= 1, head
+
+
+def test_blob_fills_every_field_of_a_shorter_arm():
+    cfg, fs, is_ = start_state("hexa_arm_2j", 300, "f32")
+    assert fs.shape == (23, 300) and (fs[19:23] != 0).all() and np.abs(fs[20]).max() <= 1.5 and np.abs(fs[19]).max() > 1.5
+    cfg, fs, is_ = start_state("hexa_arm", 300, "f32")
+    assert fs.shape == (25, 300) and (fs[19:25] != 0).all()
+    cfg, fs, is_ = start_state("quad", 300, "f32")
+    assert fs.shape == (19, 300)
+    arrived = (is_[O.I_FLAGS] & O.FLAGBIT_FWR) != 0
+    assert ((is_[O.I_FLAGS][arrived] & 255) == 1).all() and (is_[O.I_COUNTER][~arrived] == 0).all() and is_[O.I_COUNTER].max() > cfg.task.counter_limit
+    assert is_[O.I_STEP].max() > cfg.task.max_episode_steps
+
+
+# ---- compare() itself ----------------------------------------------------------------------------------------------------------------------
+def _first_step():
+    cfg, run = oracle_run("hexa_arm", 300, "f32")
+    pre, a, o, post = run[0]
+    return o, B.margins(cfg, pre, post)
+
+
+def _pick(mask):
+    k = np.nonzero(mask)[0]
+    assert len(k), "the self-test needs such an env"
+    return int(k[0])
+
+
+def test_compare_accepts_the_oracle_against_itself():
+    o, m = _first_step()
+    for dtype in ("f32", "f64"):
+        r = B.compare(copy.deepcopy(o), o, m, dtype)
+        assert r["flips"] == 0 and r["ended"] > 10 and max(r["state"], r["reward"], r["obs"], r["ep_return"], r["terminal_obs"]) == 0.0
+
+
+def _change(field):
+    """A copy of the oracle's first step changed in one field, on an env far from every threshold."""
+    o, m = _first_step()
+    g = copy.deepcopy(o)
+    clear = m["reward"] > 1e-2
+    done = o["done"] != 0
+    if field == "reward":
+        g["reward"][_pick(clear & (np.abs(o["reward"]) < 10))] += 1e-3
+    elif field == "info":
+        g["info"][_pick(clear)] ^= O.INFO_STOPPED
+    elif field == "ep_len":
+        g["ep_len"][_pick(done)] += 1
+    elif field == "terminal_obs":
+        g["terminal_obs"][_pick(done), 3] += 1e-3
+    elif field == "int field":
+        g["istate"][O.I_COUNTER, _pick(clear & ~done)] += 1
+    elif field == "ep_return":
+        k = _pick(done)
+        g["ep_return"][k] += 1e-3 * max(1.0, abs(g["ep_return"][k]))
+    elif field == "running return":
+        k = _pick(clear & ~done)
+        g["fstate"][O.F_EP_RETURN, k] += 1e-3 * max(1.0, abs(g["fstate"][O.F_EP_RETURN, k]))
+    elif field == "last_distance":
+        g["fstate"][O.F_LAST_DISTANCE, _pick(clear & ~done)] += 1e-4
+    elif field == "reset state":
+        g["fstate"][0, _pick(done)] += 1e-7
+    elif field == "observation":
+        g["obs"][_pick(clear), 28] += 1e-4
+    elif field == "was_reset":
+        g["info"][_pick(done)] &= ~np.uint32(O.INFO_WAS_RESET)
+    elif field == "row of an env that did not end":
+        g["ep_len"][_pick(~done)] = 7
+    elif field == "terminal row of an env that did not end":
+        g["terminal_obs"][_pick(~done), 0] = 0.0
+    elif field == "done":
+        g["done"][_pick(clear & ~done)] = 1
+    else:
+        raise KeyError(field)
+    return g, o, m
+
+
+@pytest.mark.parametrize("field", ["reward", "info", "ep_len", "terminal_obs", "int field", "ep_return", "running return", "last_distance", "reset state",
+                                   "observation", "was_reset", "row of an env that did not end", "terminal row of an env that did not end", "done"])
+def test_compare_rejects_one_changed_field(field):
+    g, o, m = _change(field)
+    with pytest.raises(AssertionError):
+        B.compare(g, o, m, "f32")
+
+
+def test_compare_excuses_a_flip_only_on_a_threshold_and_only_up_to_the_cap():
+    o, m = _first_step()
+    g = copy.deepcopy(o)
+    ks = np.nonzero((m["reward"] > 1e-2) & (o["done"] == 0))[0][:2]
+    g["info"][ks[0]] ^= O.INFO_STOPPED
+    on_threshold = {k: v.copy() for k, v in m.items()}
+    on_threshold["info"][ks] = 1e-6; on_threshold["reward"][ks] = 1e-6
+    r = B.compare(g, o, on_threshold, "f32")
+    assert r["flips"] == 1 and list(r["flipped"]) == [ks[0]]
+    with pytest.raises(AssertionError):            # the fp64 builds take every comparison as the oracle does
+        B.compare(g, o, on_threshold, "f64")
+    g["reward"][ks[1]] += 2.0                      # a second one: 300 envs allow one
+    with pytest.raises(AssertionError):
+        B.compare(g, o, on_threshold, "f32")
