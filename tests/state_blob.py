@@ -1,7 +1,8 @@
-"""Shared by tests/test_state_blob_cpu.py and tests/test_gpu_branch_sweep.py: a random state blob that reaches every branch of the v2 step
-state machine on a rigid or an arm vehicle (hold phase and hold termination included), the oracle's own distance to every threshold a step
-can flip, and the one routine that compares a step of the kernels with the same step of the fp64 oracle.  numpy and the oracle only: no
-GPU, no torch.
+"""Shared by tests/test_state_blob_cpu.py and tests/test_gpu_branch_sweep.py: a random state blob that reaches every branch of the step
+state machine of the config's task -- v2 with 1..4 waypoints on a rigid or an arm vehicle (hold phase and hold termination included,
+intermediate reaches with several waypoints), or v1 (raw or scaled rows) on a rigid vehicle --, the oracle's own distance to every threshold
+a step can flip, and the one routine that compares a step of the kernels with the same step of the fp64 oracle.  numpy and the oracle only:
+no GPU, no torch.
 
 Gates of `compare` (the ones tests/test_gpu_parity.py applies to the quadrotor):
   flags, done, the four int fields           equal
@@ -27,6 +28,25 @@ FLIP_MARGIN = 3e-5
 
 CLASSES = ("truncated", "crashed_sinking", "crashed_rising", "oob", "first_arrival", "hold_level", "hold_tilted", "stopped", "hold_terminated",
            "arrived_outside", "progress_taken", "progress_not_taken", "last_distance_none")
+# v2 with 2..4 waypoints: those, and the branches only an intermediate waypoint has
+CLASSES_MULTI = CLASSES + ("intermediate_reach", "intermediate_reach_then_crash_or_oob", "final_first_arrival", "next_waypoint_columns_nonzero",
+                           "next_waypoint_columns_zero")
+# v1 (both variants): another state machine -- no hold phase, a per-episode waypoint count, +-10 approach shaping, a final reach that returns
+# before the step counter moves
+CLASSES_V1 = ("truncated", "crashed_sinking", "crashed_rising", "oob", "intermediate_reach", "final_reach_stopped", "final_reach_moving",
+              "final_reach_at_time_limit", "shaping_plus", "shaping_minus", "shaping_off", "progress_taken", "progress_not_taken", "last_distance_none",
+              "is_final_0", "is_final_1", "reset_drew_k1", "reset_drew_k2")
+
+
+def is_v1(cfg):
+    return cfg.task.variant in (O.TASK_V1_SCALED17, O.TASK_V1_RAW17)
+
+
+def class_names(cfg):
+    """The classes `classes` reports for cfg's task."""
+    if is_v1(cfg):
+        return CLASSES_V1
+    return CLASSES if cfg.task.num_waypoints == 1 else CLASSES_MULTI
 
 
 def flip_cap(n):
@@ -61,13 +81,34 @@ def _qmul(a, b):
                      w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
 
 
+def current_waypoint(cfg, fstate, istate):
+    """([3, n] the waypoint each env flies to, its slot [n], the waypoint count [n]): slot = min(index, K - 1), K from flag bits 4-7 on the
+    v1 tasks (drawn per episode) and from the config on v2."""
+    n = fstate.shape[1]
+    fl = istate[O.I_FLAGS]
+    K = ((fl >> 4) & 15) if is_v1(cfg) else np.full(n, cfg.task.num_waypoints)
+    slot = np.minimum(fl & 15, K - 1)
+    cols = np.arange(n)
+    return np.stack([fstate[O.F_WP0 + 3 * slot + c, cols] for c in range(3)]), slot, K
+
+
 def blob(cfg, n, rng):
-    """(fstate [NF, n] fp64, istate [4, n] int32) for an oracle config: rigid vehicle or arm with 1..3 joints, v2 task, one waypoint.
+    """(fstate [NF, n] fp64, istate [4, n] int32) for an oracle config: rigid vehicle or arm with 1..3 joints on the v2 task with 1..4
+    waypoints, or a rigid vehicle on a v1 task.
     Generalises random_blob of tests/test_gpu_parity.py: the near-waypoint envs sit around the TASK point, a share of them has arrived
     already with counters on both sides of counter_limit, attitudes on both sides of the 0.2 rad roll / pitch bonuses, step counters on both
-    sides of the time limit, last_distance far enough from the new distance that the +2 progress bonus is decided by the step's travel."""
-    assert cfg.task.num_waypoints == 1 and cfg.task.variant == O.TASK_V2_SCALED20
+    sides of the time limit, last_distance far enough from the new distance that the +2 progress bonus is decided by the step's travel.
+    The draws common to all tasks come first and in one order, the task's own after them: with one waypoint on v2 the states are those of
+    the first version of this file bit for bit (tests/test_state_blob_cpu.py pins their checksums).
+      v2, K > 1: every slot filled, the index spread over 0..K-1 (arrived envs: K with both phase bits), near envs around the task point of
+        their CURRENT waypoint, a few of those that will reach an intermediate waypoint moved below z = 0.1 (waypoint moved along).
+      v1: a waypoint count of 1 or 2 per env in flag bits 4-7 (one: second slot zero, as the reset leaves it), index below it, no phase
+        bits and no counter; near envs up to 0.6 m from the current waypoint (both sides of 0.1 and of 0.5), the fast ones flying toward it,
+        away from it or as drawn; final reaches with the step counter at and past the time limit."""
+    v1 = is_v1(cfg)
+    K = cfg.task.num_waypoints
     nj = cfg.vehicle.n_joints
+    assert (v1 and K == 2 and nj == 0) or (cfg.task.variant == O.TASK_V2_SCALED20 and 1 <= K <= O.MAX_WAYPOINTS), (cfg.task.variant, K, nj)
     nf = O.lib().orc_n_float_fields(C.byref(cfg))
     fs = np.zeros((nf, n)); is_ = np.zeros((4, n), np.int32)
     fs[0:3] = rng.uniform(-3, 3, (3, n)); fs[2] = rng.uniform(0.05, 4, n)
@@ -88,7 +129,7 @@ def blob(cfg, n, rng):
     tilt = np.stack([np.ones(n), rng.normal(0, 0.08, n), rng.normal(0, 0.08, n), np.zeros(n)]); tilt /= np.linalg.norm(tilt, axis=0)
     level = _qmul(np.stack([np.cos(psi / 2), np.zeros(n), np.zeros(n), np.sin(psi / 2)]), tilt)
     fs[6:10] = np.where(rng.rand(n) < 0.5, level, q)
-    j0 = O.F_WP0 + 3
+    j0 = O.F_WP0 + 3 * K
     if nj:
         lim = np.array([3.1, 1.5, 1.5])[:nj, None]
         fs[j0:j0 + nj] = rng.uniform(-lim, lim, (nj, n))
@@ -106,12 +147,12 @@ def blob(cfg, n, rng):
     fs[3:6, slow] *= 0.03; fs[10:13, slow] *= 0.02
     if nj:
         fs[j0 + nj:j0 + 2 * nj, slow] *= 0.02
-    wp = rng.uniform(-1, 1, (3, n)); wp[2] = rng.uniform(0.5, 3, n)
+    wps = np.zeros((K, 3, n))
+    wps[0] = rng.uniform(-1, 1, (3, n)); wps[0, 2] = rng.uniform(0.5, 3, n)
     tp = task_point(cfg, fs)
-    wp[:, near] = (tp + _unit(rng, n) * rng.uniform(0.0, 0.2, n))[:, near]
-    fs[O.F_WP0:O.F_WP0 + 3] = wp
+    off_dir = _unit(rng, n); off_len = rng.uniform(0.0, 0.2, n)      # near envs: from the task point to the current waypoint
     fs[O.F_FINAL_YAW] = rng.uniform(-np.pi, np.pi, n)
-    fs[O.F_LAST_DISTANCE] = _last_distance(np.linalg.norm(tp - wp, axis=0), rng, none_share=0.10)
+    ld = _last_distance_draws(rng, n)
     # Running return: a few units, not hundreds.  The row is gated at 1e-5 of max(1, |x|) after the step, x = return + reward, and an fp32
     # reward is a few ulp of ITS size off (measured: 1.5e-5 at r = -43, every kernel family alike).  With returns of +-100 some envs cancel to
     # |x| < 1 against a reward of 30..70 and no fp32 kernel can meet the gate there; with |return| < ~10 the sum cancels to less than 1 only
@@ -120,30 +161,84 @@ def blob(cfg, n, rng):
     arrived = near & (rng.rand(n) < 0.6)
     cl, ms = cfg.task.counter_limit, cfg.task.max_episode_steps
     counter = np.where(rng.rand(n) < 0.15, rng.randint(cl - 2, cl + 4, n), rng.randint(0, cl - 2, n))
-    is_[O.I_COUNTER] = np.where(arrived, counter, 0)
-    is_[O.I_FLAGS] = np.where(arrived, 1 | O.FLAGBIT_FWR | O.FLAGBIT_COUNTER_ACTIVE, 0)
     is_[O.I_STEP] = np.where(rng.rand(n) < 0.05, rng.randint(ms - 3, ms + 3, n), rng.randint(0, ms - 10, n))
     is_[O.I_EPISODE] = rng.randint(1, 50, n)
+    # ---- the task's own part
+    cols = np.arange(n)
+    for k in range(1, K):
+        wps[k] = rng.uniform(-1, 1, (3, n)); wps[k, 2] = rng.uniform(0.5, 3, n)
+    if v1:
+        arrived[:] = False                                # no hold phase
+        kep = rng.randint(1, 3, n)
+        slot = rng.randint(0, 2, n) % kep
+        wps[1][:, kep == 1] = 0.0
+        # Distance of the near envs: up to 0.6 m, and not below 2e-3 (slow envs) / 2e-2 (the others).  The shaping compares
+        # vtw = v . d / |d| with 0.1, d = waypoint - position: an fp32 position of 1..4 m carries ~1.2e-7, so the direction d / |d| carries
+        # 1.2e-7 / |d| and vtw that times the speed.  Measured on the post-step states of this blob (numpy: state within one fp32 rounding
+        # of the oracle's, vtw formed in fp32 as the kernels form it, against the oracle's fp64 value): 2.2e-5 at |d| = 2.3e-2 and
+        # |v| = 2.8, i.e. 1.8e-7 |v| / |d|, just below FLIP_MARGIN -- at 2e-3 it would be 2.5e-4, and a flip there would be the oracle's own
+        # conditioning and no kernel's fault; the slow envs (|v| < 0.07) stay below 1.5e-6 down to 4e-3.  At |d| = 0 vtw is NaN in the
+        # reference too and neither branch is taken.
+        dmin = np.where(slow, 2e-3, 2e-2)
+        off_len = dmin + off_len * (0.6 - dmin) / 0.2
+        # the fast near envs by thirds: flying toward the waypoint, away from it, as drawn -- both signs of the shaping
+        mode = rng.randint(0, 3, n)
+        fast = near & ~slow
+        speed = np.linalg.norm(fs[3:6], axis=0)
+        for m, sign in ((0, 1.0), (1, -1.0)):
+            sel = fast & (mode == m)
+            fs[3:6, sel] = (sign * speed * off_dir + 0.1 * fs[3:6])[:, sel]
+        fs[O.F_FINAL_YAW] = 0.0                           # as the v1 reset leaves it
+    else:
+        slot = np.where(arrived, K - 1, rng.randint(0, K, n) if K > 1 else 0)
+    cur = (tp + off_dir * off_len)
+    wps[slot[near], :, cols[near]] = cur[:, near].T
+    if v1:
+        # final reaches at and past the time limit: the step counter stays and no TRUNCATED bit is set
+        last = np.nonzero(near & (off_len < 0.07) & (slot == kep - 1))[0][:3]
+        is_[O.I_STEP, last] = ms + np.arange(len(last))
+        is_[O.I_FLAGS] = slot | (kep << 4)
+    else:
+        if K > 1:
+            # a few envs about to reach an intermediate waypoint go below z = 0.1, waypoint and all: reach and crash in one step
+            sink = np.nonzero(near & ~arrived & (slot < K - 1) & (off_len < 0.08))[0][:4]
+            dz = rng.uniform(0.05, 0.085, len(sink)) - fs[2, sink]
+            fs[2, sink] += dz; tp[2, sink] += dz; wps[slot[sink], 2, sink] += dz
+        is_[O.I_COUNTER] = np.where(arrived, counter, 0)
+        is_[O.I_FLAGS] = np.where(arrived, K | O.FLAGBIT_FWR | O.FLAGBIT_COUNTER_ACTIVE, slot)
+    fs[O.F_WP0:O.F_WP0 + 3 * K] = wps.reshape(3 * K, n)
+    fs[O.F_LAST_DISTANCE] = _apply_last_distance(np.linalg.norm(tp - wps[slot, :, cols].T, axis=0), ld, none_share=0.10)
     return fs, is_
+
+
+def _last_distance_draws(rng, n):
+    u = rng.rand(n)
+    wide = rng.uniform(0.04, 0.06, n) * np.where(rng.rand(n) < 0.5, -1.0, 1.0)
+    tight = rng.normal(0, 0.01, n).clip(-0.02, 0.02)
+    return u, wide, tight
+
+
+def _apply_last_distance(dist, draws, none_share):
+    u, wide, tight = draws
+    return np.where(u < none_share, -1.0, np.maximum(0.0, np.where(u < none_share + 0.05 * (1 - none_share) / 0.9, dist + tight, dist + wide)))
 
 
 def _last_distance(dist, rng, none_share):
     """last_distance for envs at distance dist: None (-1) for none_share of them; of the rest 1 in 18 within +-0.02 of dist (around the threshold
     of the +2 progress bonus), the others 0.04..0.06 away on either side: a step travels ~0.005 m, so the oracle's own margin to that
     threshold stays far above the fp32 error and the bonus still goes both ways."""
-    n = len(dist)
-    u = rng.rand(n)
-    wide = dist + rng.uniform(0.04, 0.06, n) * np.where(rng.rand(n) < 0.5, -1.0, 1.0)
-    tight = dist + rng.normal(0, 0.01, n).clip(-0.02, 0.02)
-    return np.where(u < none_share, -1.0, np.maximum(0.0, np.where(u < none_share + 0.05 * (1 - none_share) / 0.9, tight, wide)))
+    return _apply_last_distance(dist, _last_distance_draws(rng, len(dist)), none_share)
 
 
-def reseat_last_distance(cfg, fstate, rng):
+def reseat_last_distance(cfg, fstate, rng, istate=None):
     """A copy of fstate with last_distance drawn afresh around each env's present distance, as blob() does (None stays None).  Between the
     steps of a multi-step sweep: the last_distance a step leaves IS the present distance, so that without this every slow env -- every env
-    that was just reset above all -- would sit on the threshold of the progress bonus in the next step."""
+    that was just reset above all -- would sit on the threshold of the progress bonus in the next step.  istate: which waypoint is the
+    current one (needed with more than one slot)."""
     f = fstate.copy()
-    dist = np.linalg.norm(task_point(cfg, f) - f[O.F_WP0:O.F_WP0 + 3], axis=0)
+    assert istate is not None or (cfg.task.num_waypoints == 1 and not is_v1(cfg))
+    wp = f[O.F_WP0:O.F_WP0 + 3] if istate is None else current_waypoint(cfg, f, istate)[0]
+    dist = np.linalg.norm(task_point(cfg, f) - wp, axis=0)
     f[O.F_LAST_DISTANCE] = np.where(f[O.F_LAST_DISTANCE] < 0, -1.0, _last_distance(dist, rng, none_share=0.0))
     return f
 
@@ -166,7 +261,7 @@ def actions(cfg, fstate, rng):
 
 def oracle_step(cfg, pre, acts):
     """One step of the oracle from pre = (fstate, istate).  Returns (o, post): o the outputs of the oracle as cfg has it (auto-reset as
-    configured) with its state after the step under "fstate" / "istate"; post = (fstate, istate, info) of a second oracle WITHOUT
+    configured) with its state after the step under "fstate" / "istate"; post = (fstate, istate, info, obs) of a second oracle WITHOUT
     auto-reset: the post-step, pre-reset state, where the threshold margins live."""
     n = pre[0].shape[1]
     outs = []
@@ -177,7 +272,7 @@ def oracle_step(cfg, pre, acts):
         o["fstate"], o["istate"] = e.fstate, e.istate
         outs.append(o)
     o, nr = outs
-    return o, (nr["fstate"], nr["istate"], nr["info"])
+    return o, (nr["fstate"], nr["istate"], nr["info"], nr["obs"])
 
 
 def _rpy(q):
@@ -186,25 +281,46 @@ def _rpy(q):
 
 
 def _geometry(cfg, pre, post):
+    """Of the step from pre to post: the distance the step measured -- post-step task point to the waypoint that was current BEFORE the
+    step (the state machine moves the index after the reward) --, roll, pitch, arrived before the step, last_distance before the step."""
     f0, i0 = pre
     f1 = post[0]
-    d = np.linalg.norm(task_point(cfg, f1) - f1[O.F_WP0:O.F_WP0 + 3], axis=0)
+    d = np.linalg.norm(task_point(cfg, f1) - current_waypoint(cfg, f1, i0)[0], axis=0)      # the waypoints stay: post is not reset
     roll, pitch = _rpy(f1[6:10])
     fwr = (i0[O.I_FLAGS] & O.FLAGBIT_FWR) != 0
     return d, roll, pitch, fwr, f0[O.F_LAST_DISTANCE]
 
 
+def _vtw(cfg, pre, post):
+    """v1: the velocity component toward the waypoint, as the reference forms it (NaN at distance 0)."""
+    f1 = post[0]
+    to_wp = current_waypoint(cfg, f1, pre[1])[0] - f1[0:3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (f1[3:6] * (to_wp / np.linalg.norm(to_wp, axis=0))).sum(axis=0)
+
+
 def margins(cfg, pre, post):
-    """The oracle's own distance to every threshold the step from pre to post (see oracle_step) can flip, per env:
+    """The oracle's own distance to every threshold the step from pre to post (see oracle_step) can flip, per env; dist is the distance
+    to the waypoint that was current before the step.
+    v2:
       "info":   min of |dist - 0.1|, |p_z - 0.1|, ||p| - 10|, ||v| - 0.1|, ||w| - 0.1|      (flag bits, and the reward with them)
       "reward": min of those and of the reward-only thresholds: |last_distance - dist| where the progress term counts (last_distance >= 0,
-                not arrived before the step), ||roll| - 0.2| and ||pitch| - 0.2| on envs that hold after the step."""
+                not arrived before the step), ||roll| - 0.2| and ||pitch| - 0.2| on envs that hold after the step.
+    v1:
+      "info":   min of |dist - 0.1|, |p_z - 0.1|, ||p| - 10|, ||v| - 0.1|
+      "reward": min of those and of ||w| - 0.1|, |dist - 0.5|, |vtw - 0.1| where dist < 0.5, |last_distance - dist| where
+                last_distance >= 0."""
     f1 = post[0]
     d, roll, pitch, fwr, ld = _geometry(cfg, pre, post)
     p, v, w = f1[0:3], f1[3:6], f1[10:13]
-    info = np.minimum.reduce([np.abs(d - 0.1), np.abs(p[2] - 0.1), np.abs(np.linalg.norm(p, axis=0) - 10), np.abs(np.linalg.norm(v, axis=0) - 0.1),
-                              np.abs(np.linalg.norm(w, axis=0) - 0.1)])
     inf = np.full(d.shape, np.inf)
+    wn = np.abs(np.linalg.norm(w, axis=0) - 0.1)
+    info = np.minimum.reduce([np.abs(d - 0.1), np.abs(p[2] - 0.1), np.abs(np.linalg.norm(p, axis=0) - 10), np.abs(np.linalg.norm(v, axis=0) - 0.1)])
+    if is_v1(cfg):
+        shaping = np.where(d < 0.5, np.nan_to_num(np.abs(_vtw(cfg, pre, post) - 0.1), nan=0.0), inf)
+        progress = np.where(ld >= 0, np.abs(ld - d), inf)
+        return dict(info=info, reward=np.minimum.reduce([info, wn, np.abs(d - 0.5), shaping, progress]))
+    info = np.minimum(info, wn)
     progress = np.where((ld >= 0) & ~fwr, np.abs(ld - d), inf)
     holds = fwr & (d < 0.1)
     tilt = np.where(holds, np.minimum(np.abs(np.abs(roll) - 0.2), np.abs(np.abs(pitch) - 0.2)), inf)
@@ -216,17 +332,41 @@ def eligible(m):
     return m["reward"] < FLIP_MARGIN
 
 
-def classes(cfg, pre, post):
-    """{class: bool [n]}: the branch of the step state machine each env took in the step from pre to post (oracle_step)."""
-    f1, _, info = post
+def classes(cfg, pre, post, o=None):
+    """{class: bool [n]}: the branch of the step state machine each env took in the step from pre to post (oracle_step); the names are
+    class_names(cfg).  o (oracle_step's first result, the step WITH auto-reset) is needed on the v1 tasks only: what the reset drew."""
+    f1, i1, info, obs = post
+    i0 = pre[1]
     d, roll, _, fwr, ld = _geometry(cfg, pre, post)
     bit = lambda b: (info & b) != 0  # noqa: E731
     success, crashed = bit(O.INFO_SUCCESS), bit(O.INFO_CRASHED)
+    idx0, idx1 = i0[O.I_FLAGS] & 15, i1[O.I_FLAGS] & 15
+    if is_v1(cfg):
+        K = (i0[O.I_FLAGS] >> 4) & 15
+        vtw = _vtw(cfg, pre, post)
+        ended = np.asarray(o["done"]) != 0
+        drew = (np.asarray(o["istate"])[O.I_FLAGS] >> 4) & 15
+        return dict(truncated=bit(O.INFO_TRUNCATED), crashed_sinking=crashed & (f1[5] < 0), crashed_rising=crashed & (f1[5] >= 0), oob=bit(O.INFO_OOB),
+                    intermediate_reach=(idx1 == idx0 + 1) & ~success, final_reach_stopped=success & bit(O.INFO_STOPPED),
+                    final_reach_moving=success & ~bit(O.INFO_STOPPED),
+                    final_reach_at_time_limit=success & (i0[O.I_STEP] >= cfg.task.max_episode_steps) & (i1[O.I_STEP] == i0[O.I_STEP]) & ~bit(O.INFO_TRUNCATED),
+                    shaping_plus=(d < 0.5) & (vtw > 0.1), shaping_minus=(d < 0.5) & (vtw < 0.1), shaping_off=~(d < 0.5),
+                    progress_taken=(ld >= 0) & (ld - d > 0), progress_not_taken=(ld >= 0) & (ld - d <= 0), last_distance_none=ld < 0,
+                    is_final_0=(obs[:, 16] == 0) & (idx1 < K - 1), is_final_1=(obs[:, 16] == 1) & (idx1 >= K - 1),
+                    reset_drew_k1=ended & (drew == 1), reset_drew_k2=ended & (drew == 2))
     counts = (ld >= 0) & ~fwr
-    return dict(truncated=bit(O.INFO_TRUNCATED), crashed_sinking=crashed & (f1[5] < 0), crashed_rising=crashed & (f1[5] >= 0), oob=bit(O.INFO_OOB),
-                first_arrival=success & ~fwr, hold_level=success & fwr & (np.abs(roll) < 0.2), hold_tilted=success & fwr & (np.abs(roll) >= 0.2),
-                stopped=bit(O.INFO_STOPPED), hold_terminated=success & bit(O.INFO_TERMINATED), arrived_outside=fwr & ~success,
-                progress_taken=counts & (ld - d > 0), progress_not_taken=counts & (ld - d <= 0), last_distance_none=ld < 0)
+    c = dict(truncated=bit(O.INFO_TRUNCATED), crashed_sinking=crashed & (f1[5] < 0), crashed_rising=crashed & (f1[5] >= 0), oob=bit(O.INFO_OOB),
+             first_arrival=success & ~fwr, hold_level=success & fwr & (np.abs(roll) < 0.2), hold_tilted=success & fwr & (np.abs(roll) >= 0.2),
+             stopped=bit(O.INFO_STOPPED), hold_terminated=success & bit(O.INFO_TERMINATED), arrived_outside=fwr & ~success,
+             progress_taken=counts & (ld - d > 0), progress_not_taken=counts & (ld - d <= 0), last_distance_none=ld < 0)
+    K = cfg.task.num_waypoints
+    if K > 1:
+        reach = (idx1 == idx0 + 1) & ~success
+        nxt = (obs[:, 16:19] != 0).any(axis=1)
+        c.update(intermediate_reach=reach, intermediate_reach_then_crash_or_oob=reach & (crashed | bit(O.INFO_OOB)),
+                 final_first_arrival=success & ~fwr & (idx0 == K - 1) & (idx1 == K),
+                 next_waypoint_columns_nonzero=(idx1 < K - 1) & nxt, next_waypoint_columns_zero=(idx1 >= K - 1) & ~nxt)
+    return c
 
 
 def rel_err(a, b):

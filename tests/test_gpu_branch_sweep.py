@@ -7,6 +7,18 @@ in the hold phase with counters on both sides of counter_limit, first arrivals, 
 both signs of the progress bonus -- and every output of six teacher-forced steps is compared with the oracle's by `state_blob.compare`
 (gates in that file's docstring); then amenv_rollout and amenv_rollout_policy from the same states against amenv_step, bit for bit.
 
+The kernels are built in three compile-time task forms, and the sweep runs all three:
+  VAR_V2, KW=1   one waypoint (SWEEP: every family)
+  VAR_V1, KW=2   v1_raw / v1_scaled (TASK_SWEEP): `task_step_v1` -- the waypoint count per episode in flag bits 4-7, +-10 approach shaping, a
+                 final reach that returns before the step counter moves and before the time-limit test, the is_final column, what the reset drew
+  VAR_V2, KW=4   2..4 waypoints (TASK_SWEEP), rigid vehicles and the arm: an intermediate reach that falls through to the crash and
+                 out-of-bounds tests, the next-waypoint columns, last_distance across a switch, the hold phase at index K
+On the last two the rigid helper-wave kernel is its 128-thread form (the main wave forms the rows, draws the next episode and writes the Monitor
+rows and totals itself) and the arm runs its KW=4 lane kernel; the families built for one waypoint only must refuse these tasks.
+Worst errors measured on the TASK_SWEEP cases (MI355X, 12 cases x 6 steps x 300 envs, 0 threshold flips), v1 / several waypoints:
+  fp32: state 4.6e-6 / 4.8e-6, reward 5.2e-6 / 6.1e-6, observation rows 2.4e-7 / 1.8e-7, ep_return 1.2e-6 / 1.8e-6, terminal rows 1.2e-7 / 1.2e-7
+  fp64: state 4.3e-14 / 1.1e-13, reward 7.2e-15 / 1.3e-14, observation rows 6.6e-17 / 1.3e-17, ep_return 0 / 0, terminal rows 0 / 0
+
 tests/test_state_blob_cpu.py checks on the oracle alone that these states reach every branch and that the envs a flip could be excused on
 number no more than the cap."""
 import numpy as np
@@ -23,13 +35,18 @@ ENV_KW = {"hexa_arm": dict(vehicle="hexa_arm"), "hexa_arm_2j": dict(vehicle="hex
           "hexa": dict(vehicle="hexa"), "quad": dict(vehicle="quad")}
 
 
-def make_env(vehicle, n, dtype="f32", kernel="auto", **kw):
+TASK_KW = {"v2": dict(), "v2k2": dict(num_waypoints=2), "v2k3": dict(num_waypoints=3), "v2k4": dict(num_waypoints=4), "v1_raw": dict(task="v1_raw"),
+           "v1_scaled": dict(task="v1_scaled")}
+
+
+def make_env(vehicle, n, dtype="f32", kernel="auto", task="v2", **kw):
     import rl_aerial_manipulator_amd as amd
-    return amd.GpuWaypointEnv(n, seed=ENV_SEED, dtype=dtype, kernel=kernel, **ENV_KW[vehicle], **kw)
+    return amd.GpuWaypointEnv(n, seed=ENV_SEED, dtype=dtype, kernel=kernel, **ENV_KW[vehicle], **TASK_KW[task], **kw)
 
 
-def seat(env, vehicle, n, dtype="f32"):
-    cfg, fs, is_ = start_state(vehicle, n, dtype)
+def seat(env, vehicle, n, dtype="f32", task="v2"):
+    cfg, fs, is_ = start_state(vehicle, n, dtype, task)
+    assert fs.shape[0] == env.n_float_fields and env.obs_dim == O.lib().orc_obs_dim(cfg)
     env.set_state(fs.copy(), is_.copy())
     return cfg, fs, is_
 
@@ -76,18 +93,57 @@ SWEEP = [
 
 @pytest.mark.parametrize("vehicle,kernel,dtype,n,names,absent", SWEEP, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in SWEEP])
 def test_every_branch_vs_oracle(vehicle, kernel, dtype, n, names, absent):
-    env = make_env(vehicle, n, dtype, kernel)
+    _sweep(f"test_every_branch_vs_oracle[{vehicle}-{kernel}-{dtype}-{n}]", vehicle, "v2", kernel, dtype, n, names, absent)
+
+
+# (vehicle, task, kernel, dtype, substrings of kernel_name).  Rigid vehicles on these tasks run the 128-thread form of step_kernel_pw: the
+# main wave forms the rows, draws the next episode and writes the Monitor rows and totals itself
+TASK_SWEEP = [
+    ("quad", "v1_raw", "helper", "f32", ("step_kernel_pw<float,NROT=4,KW=2,v1>",)),
+    ("quad", "v1_raw", "lane", "f32", ("step_kernel<float,NROT=4,KW=2,v1>",)),
+    ("quad", "v1_raw", "lane", "f64", ("step_kernel<double,NROT=4,KW=2,v1>",)),
+    ("quad", "v1_scaled", "helper", "f32", ("step_kernel_pw<float,NROT=4,KW=2,v1>",)),
+    ("hexa", "v1_scaled", "lane", "f32", ("step_kernel<float,NROT=6,KW=2,v1>",)),
+    ("quad", "v2k3", "helper", "f32", ("step_kernel_pw<float,NROT=4,KW=4,v2>",)),
+    ("quad", "v2k3", "lane", "f64", ("step_kernel<double,NROT=4,KW=4,v2>",)),
+    ("hexa", "v2k4", "lane", "f32", ("step_kernel<float,NROT=6,KW=4,v2>",)),
+    ("hexa", "v2k2", "helper", "f32", ("step_kernel_pw<float,NROT=6,KW=4,v2>",)),
+    ("hexa_arm", "v2k3", "lane", "f32", ("step_kernel<float,NROT=6,KW=4,v2+arm3>",)),
+    ("hexa_arm", "v2k3", "lane", "f64", ("step_kernel<double,NROT=6,KW=4,v2+arm3>",)),
+    ("hexa_arm_2j", "v2k2", "lane", "f32", ("step_kernel<float,NROT=6,KW=4,v2+arm3>", "2-joint arm", "pack / unpack")),   # the caller's row widths beside KW = 4
+]
+
+
+@pytest.mark.parametrize("vehicle,task,kernel,dtype,names", TASK_SWEEP, ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in TASK_SWEEP])
+def test_every_branch_of_the_v1_and_multi_waypoint_tasks_vs_oracle(vehicle, task, kernel, dtype, names):
+    """The same sweep on the other two compile-time task forms: VAR_V1 with KW = 2 (v1_raw, v1_scaled: another state machine, the waypoint
+    count per episode in the flag bits) and VAR_V2 with KW = 4 (2..4 waypoints: intermediate reaches, next-waypoint columns, hold at index K)."""
+    _sweep(f"test_every_branch_of_the_v1_and_multi_waypoint_tasks_vs_oracle[{vehicle}-{task}-{kernel}-{dtype}]", vehicle, task, kernel, dtype, 300, names, None)
+
+
+@pytest.mark.parametrize("vehicle,task,kernel", [("quad", "v1_raw", "team"), ("hexa", "v1_scaled", "team"), ("quad", "v2k3", "team"), ("hexa", "v2k2", "team"),
+                                                 ("hexa_arm", "v2k3", "team"), ("hexa_arm", "v2k3", "staged")])
+def test_families_not_built_for_these_tasks_are_refused(vehicle, task, kernel):
+    """The lane-quad, lane-team and stage-wave kernels exist for the one-waypoint v2 task only: asking for them on another task is an error
+    at creation, not another kernel."""
+    import rl_aerial_manipulator_amd as amd
+    with pytest.raises(amd.AmenvError, match=f"AMENV_KERNEL_{kernel.upper()} is built for"):
+        make_env(vehicle, 300, "f32", kernel, task)
+
+
+def _sweep(label, vehicle, task, kernel, dtype, n, names, absent):
+    env = make_env(vehicle, n, dtype, kernel, task)
     assert all(s in env.kernel_name for s in names) and (absent is None or absent not in env.kernel_name), env.kernel_name
-    cfg, _, _ = seat(env, vehicle, n, dtype)
+    cfg, _, _ = seat(env, vehicle, n, dtype, task)
     rng, rng_ld = np.random.RandomState(ACTION_SEED), np.random.RandomState(RESEAT_SEED)
-    seen = {k: 0 for k in B.CLASSES}
+    seen = {k: 0 for k in B.class_names(cfg)}
     worst = dict(state=0.0, reward=0.0, obs=0.0, ep_return=0.0, terminal_obs=0.0)
     tot = dict(episodes=0, terminated=0, truncated=0, success=0, crashed=0, oob=0, length_sum=0)
     flips = 0; ret_sum = ret_slack = 0.0
     for t in range(STEPS):
         if t:    # the last_distance a step leaves is the present distance: drawn afresh, or every slow env would sit on the progress threshold
             f, i = gpu_state(env)
-            env.set_state(B.reseat_last_distance(cfg, f, rng_ld), i)
+            env.set_state(B.reseat_last_distance(cfg, f, rng_ld, i), i)
         pre = gpu_state(env)                                        # teacher-forced: the oracle steps the state the handle holds
         a = B.actions(cfg, pre[0], rng)
         g = gpu_step(env, a)
@@ -97,7 +153,7 @@ def test_every_branch_vs_oracle(vehicle, kernel, dtype, n, names, absent):
         flips += r["flips"]
         for k in worst:
             worst[k] = max(worst[k], r[k])
-        for k, v in B.classes(cfg, pre, post).items():
+        for k, v in B.classes(cfg, pre, post, o).items():
             seen[k] += int(v.sum())
         d = o["done"] != 0
         bits = o["info"][d]
@@ -111,9 +167,9 @@ def test_every_branch_vs_oracle(vehicle, kernel, dtype, n, names, absent):
         ret_slack += float((B.RET_REL * np.maximum(1.0, np.abs(o["ep_return"][d]))).sum()) + int(d.sum()) / 1024.0
         fl = r["flipped"]
         ret_slack += float(np.nan_to_num(np.abs(o["ep_return"][fl])).sum() + np.nan_to_num(np.abs(g["ep_return"][fl])).sum())
-    G.report_flips(f"test_every_branch_vs_oracle[{vehicle}-{kernel}-{dtype}-{n}] (flag bits and rewards vs the oracle, env-steps)", flips, STEPS * n)
+    G.report_flips(f"{label} (flag bits and rewards vs the oracle, env-steps)", flips, STEPS * n)
     print("worst errors:", worst, "branches:", seen)
-    assert all(seen[k] >= 1 for k in B.CLASSES), seen
+    assert all(v >= 1 for v in seen.values()), seen
     st = env.stats()
     for k, v in tot.items():
         slack = flips * (cfg.task.max_episode_steps + 3) if k == "length_sum" else flips
@@ -133,16 +189,36 @@ def _assert_hold_phase_reached(is_, info):
     assert (((info & O.INFO_SUCCESS) != 0) & ((info & O.INFO_TERMINATED) != 0)).any()
 
 
-@pytest.mark.parametrize("vehicle,kernel,name", [("hexa_arm", "team", "step_kernel_team"), ("hexa_arm", "lane", "step_kernel<float"),
-                                                 ("hexa", "helper", "step_kernel_pw"), ("quad", "team", "step_kernel_quad")])
-def test_rollout_from_the_blob_equals_steps(vehicle, kernel, name):
-    """amenv_rollout (its kernels carry their own episode-end path) == amenv_step launches, bit for bit, from states in the hold phase."""
+def _assert_task_branches_reached(cfg, is_, obs, done, info, is_after):
+    """Of a run from a blob of another task, obs [T, n, D], done [T, n], info [T, n] uint32, is_after the int state after it.  v1 (no hold
+    phase): a final reach, and an intermediate one -- the is_final column of an env that goes on turns from 0 to 1.  v2 with several
+    waypoints: the hold phase as above, and an env that went on to a later waypoint in its episode.  Both: an episode ended with a step behind it."""
+    assert done[:-1].any()
+    if B.is_v1(cfg):
+        fl = is_[O.I_FLAGS]
+        before = np.concatenate([((fl & 15) >= ((fl >> 4) & 15) - 1)[None], obs[:-1, :, 16] == 1.0])
+        assert ((info & O.INFO_SUCCESS) != 0).any() and (~before & (obs[:, :, 16] == 1.0) & (done == 0)).any()
+    else:
+        _assert_hold_phase_reached(is_, info)
+        i0, i1 = is_[O.I_FLAGS] & 15, is_after[O.I_FLAGS] & 15
+        assert ((is_after[O.I_EPISODE] == is_[O.I_EPISODE]) & (i1 > i0) & (i1 < cfg.task.num_waypoints)).any()
+
+
+ROLLOUT = [("hexa_arm", "v2", "team", "step_kernel_team"), ("hexa_arm", "v2", "lane", "step_kernel<float"), ("hexa", "v2", "helper", "step_kernel_pw"),
+           ("quad", "v2", "team", "step_kernel_quad"), ("quad", "v1_raw", "helper", "step_kernel_pw<float,NROT=4,KW=2,v1>"),
+           ("hexa", "v2k3", "lane", "step_kernel<float,NROT=6,KW=4,v2>"), ("hexa_arm", "v2k3", "lane", "step_kernel<float,NROT=6,KW=4,v2+arm3>")]
+
+
+@pytest.mark.parametrize("vehicle,task,kernel,name", ROLLOUT, ids=[f"{c[0]}-{c[2]}-{c[3]}" if c[1] == "v2" else f"{c[0]}-{c[1]}-{c[2]}" for c in ROLLOUT])
+def test_rollout_from_the_blob_equals_steps(vehicle, task, kernel, name):
+    """amenv_rollout (its kernels carry their own episode-end path) == amenv_step launches, bit for bit, from states in the hold phase (v1:
+    from states about to make their intermediate and final reaches)."""
     import torch
     n, T = 300, ROLLOUT_STEPS
-    e1, e2 = make_env(vehicle, n, kernel=kernel), make_env(vehicle, n, kernel=kernel)
+    e1, e2 = make_env(vehicle, n, kernel=kernel, task=task), make_env(vehicle, n, kernel=kernel, task=task)
     assert name in e1.kernel_name
-    cfg, fs, is_ = seat(e1, vehicle, n)
-    seat(e2, vehicle, n)
+    cfg, fs, is_ = seat(e1, vehicle, n, task=task)
+    seat(e2, vehicle, n, task=task)
     rng = np.random.RandomState(ACTION_SEED)
     at = torch.from_numpy(np.stack([B.actions(cfg, fs, rng) for _ in range(T)])).cuda()
     ro = e1.rollout(at)
@@ -153,7 +229,11 @@ def test_rollout_from_the_blob_equals_steps(vehicle, kernel, name):
     assert torch.equal(f1, f2) and torch.equal(i1, i2)
     s1, s2 = e1.stats(), e2.stats()
     assert s1 == s2 and s1["episodes"] == int(ro["done"].sum()) > 0 and s1["steps"] == T * n
-    _assert_hold_phase_reached(is_, ro["info_bits"].cpu().numpy().view(np.uint32))
+    info = ro["info_bits"].cpu().numpy().view(np.uint32)
+    if task == "v2":
+        _assert_hold_phase_reached(is_, info)
+    else:
+        _assert_task_branches_reached(cfg, is_, ro["obs"].cpu().numpy(), ro["done"].cpu().numpy(), info, i1.cpu().numpy())
     e1.close(); e2.close()
 
 
@@ -162,20 +242,27 @@ def test_rollout_from_the_blob_equals_steps(vehicle, kernel, name):
 POLICY = [("hexa_arm", dict(kernel="team"), dict(kernel="team"), "step_kernel_team"),                       # 16 lanes per env
           ("hexa_arm", dict(kernel="lane"), dict(kernel="lane"), "step_kernel<float"),                      # one lane per env
           ("quad", dict(), dict(kernel="team"), "step_kernel_quad<NROT=4"),                                # lane-quad form, whatever kernel amenv_step runs
-          ("hexa", dict(kernel="lane", block_size=64), dict(kernel="lane", block_size=64), "step_kernel<float,NROT=6")]   # a set workgroup size: one lane per env
+          ("hexa", dict(kernel="lane", block_size=64), dict(kernel="lane", block_size=64), "step_kernel<float,NROT=6"),   # a set workgroup size: one lane per env
+          # the other task forms (every one of the rollout cases above: amenv_rollout_policy serves them all at 300 envs); one lane per env
+          ("quad", dict(kernel="helper", task="v1_raw"), dict(kernel="lane", task="v1_raw"), "step_kernel<float,NROT=4,KW=2,v1>"),
+          ("hexa", dict(kernel="lane", task="v2k3"), dict(kernel="lane", task="v2k3"), "step_kernel<float,NROT=6,KW=4,v2>"),
+          ("hexa_arm", dict(kernel="lane", task="v2k3"), dict(kernel="lane", task="v2k3"), "step_kernel<float,NROT=6,KW=4,v2+arm3>")]
 
 
-@pytest.mark.parametrize("vehicle,kw,twin_kw,twin_name", POLICY, ids=["hexa_arm-team", "hexa_arm-lane", "quad-lane_quad", "hexa-one_lane"])
+@pytest.mark.parametrize("vehicle,kw,twin_kw,twin_name", POLICY, ids=["hexa_arm-team", "hexa_arm-lane", "quad-lane_quad", "hexa-one_lane", "quad-v1_raw-helper",
+                                                                     "hexa-v2k3-lane", "hexa_arm-v2k3-lane"])
 def test_closed_loop_rollout_from_the_blob_replays_through_steps(vehicle, kw, twin_kw, twin_name):
-    """amenv_rollout_policy from states in the hold phase: its recorded (clipped) actions through amenv_step on a twin handle give the same
-    observations, rewards, flags, terminal rows and final state bit for bit (both sides are the same fp32 arithmetic: no env is excused)."""
+    """amenv_rollout_policy from states in the hold phase (v1: about to make their reaches): its recorded (clipped) actions through amenv_step
+    on a twin handle give the same observations, rewards, flags, terminal rows and final state bit for bit (both sides are the same fp32
+    arithmetic: no env is excused)."""
     import torch
     import rl_aerial_manipulator_amd as amd
     n, T = 300, ROLLOUT_STEPS
+    task = kw.get("task", "v2")
     env, twin = make_env(vehicle, n, **kw), make_env(vehicle, n, **twin_kw)
     assert twin_name in twin.kernel_name, twin.kernel_name
-    cfg, fs, is_ = seat(env, vehicle, n)
-    seat(twin, vehicle, n)
+    cfg, fs, is_ = seat(env, vehicle, n, task=task)
+    seat(twin, vehicle, n, task=task)
     od, ad, dev = env.obs_dim, env.act_dim, env.device
     torch.manual_seed(5)
     pol = amd.ActorCritic(od, ad).cuda().flatten_()
@@ -199,5 +286,8 @@ def test_closed_loop_rollout_from_the_blob_replays_through_steps(vehicle, kw, tw
     assert torch.equal(f1, f2) and torch.equal(i1, i2)
     s1, s2 = env.stats(), twin.stats()
     assert s1 == s2 and s1["episodes"] == int(dones.sum()) > 0
-    _assert_hold_phase_reached(is_, info.cpu().numpy().view(np.uint32))
+    if task == "v2":
+        _assert_hold_phase_reached(is_, info.cpu().numpy().view(np.uint32))
+    else:
+        _assert_task_branches_reached(cfg, is_, obs[1:].cpu().numpy(), dones.cpu().numpy(), info.cpu().numpy().view(np.uint32), i1.cpu().numpy())
     env.close(); twin.close()

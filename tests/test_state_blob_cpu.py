@@ -5,10 +5,13 @@
      (and a hold-phase env and a hold termination within the four steps its rollout cases run).
   2. The cap on threshold flips is a condition, not a measurement: in every step the envs the comparison WOULD excuse (oracle margin below
      3e-5) number at most the cap, so a disagreement beyond them cannot hide behind it.
-  3. `compare` accepts the oracle against itself and rejects a copy changed in any one field it guards."""
+  3. `compare` accepts the oracle against itself and rejects a copy changed in any one field it guards.
+  4. The same for the states of the other two task forms (TASK_STATES: v1, and v2 with 2..4 waypoints), with the classes of those tasks; and
+     the one-waypoint states are still, by checksum, the ones the sweep started from before the blob learnt the other tasks."""
 import copy
 import ctypes as C
 import functools
+import zlib
 
 import numpy as np
 import pytest
@@ -25,8 +28,31 @@ STATES = [("hexa_arm", 300, "f32"), ("hexa_arm", 300, "f64"), ("hexa_arm", 4100,
           ("hexa", 300, "f32"), ("hexa", 300, "f64"), ("quad", 300, "f32")]
 
 
-def oracle_cfg(vehicle, n):
+# The other two task forms the kernels are built in (KW = 4 on v2, KW = 2 on v1): (vehicle, n, dtype, task) of every state the sweep's cases
+# for them start from.  task: "v2" (one waypoint, the states above), "v2k2".."v2k4", "v1_raw", "v1_scaled"
+TASK_STATES = [("quad", 300, "f32", "v1_raw"), ("quad", 300, "f64", "v1_raw"), ("quad", 300, "f32", "v1_scaled"), ("hexa", 300, "f32", "v1_scaled"),
+               ("quad", 300, "f32", "v2k3"), ("quad", 300, "f64", "v2k3"), ("hexa", 300, "f32", "v2k4"), ("hexa", 300, "f32", "v2k2"),
+               ("hexa", 300, "f32", "v2k3"), ("hexa_arm", 300, "f32", "v2k3"), ("hexa_arm", 300, "f64", "v2k3"), ("hexa_arm_2j", 300, "f32", "v2k2")]
+V1_VARIANT = {"v1_scaled": O.TASK_V1_SCALED17, "v1_raw": O.TASK_V1_RAW17}
+# zlib.crc32(fstate.tobytes() + istate.tobytes()) of every entry of STATES, taken before blob() learnt the other tasks: the one-waypoint
+# sweep still starts from the same states
+STATE_CRC = {("hexa_arm", 300, "f32"): 0x180aced9, ("hexa_arm", 300, "f64"): 0xf453e011, ("hexa_arm", 4100, "f32"): 0x483d7431,
+             ("hexa_arm_2j", 300, "f32"): 0x81c8b385, ("hexa_arm_base", 300, "f32"): 0x9d8d7d3f, ("hexa", 300, "f32"): 0x8fdd3bde,
+             ("hexa", 300, "f64"): 0x6aa8787a, ("quad", 300, "f32"): 0x8fdd3bde}       # (a rigid vehicle's blob does not depend on its rotors)
+
+
+def oracle_cfg(vehicle, n, task="v2"):
     """The oracle's config of a sweep vehicle: the package's vehicle parameters on the reference task, auto-reset on."""
+    if task != "v2":
+        veh = oracle_cfg(vehicle, n)
+        if task in V1_VARIANT:
+            cfg = O.reference_quad_config(1, variant=V1_VARIANT[task])
+        else:
+            cfg = O.reference_quad_config(1, num_waypoints=int(task[3:]))
+        C.memmove(C.byref(cfg.vehicle), C.byref(veh.vehicle), C.sizeof(O.Vehicle))
+        cfg.task.ee_task = veh.task.ee_task
+        cfg.num_envs, cfg.seed, cfg.flags = n, ENV_SEED, O.FLAG_AUTO_RESET
+        return cfg
     if vehicle.startswith("hexa_arm"):
         if vehicle == "hexa_arm_2j":
             cfg = arm_cfg(n_joints=2, mass=amd._lib.default_config("hexa_arm", 1, n_joints=2).vehicle.mass)
@@ -43,9 +69,9 @@ def oracle_cfg(vehicle, n):
 
 
 @functools.lru_cache(maxsize=None)
-def start_state(vehicle, n, dtype):
-    """(cfg, fstate, istate): the blob of this vehicle and batch size as a handle of dtype holds it.  Shared: do not write to it."""
-    cfg = oracle_cfg(vehicle, n)
+def start_state(vehicle, n, dtype, task="v2"):
+    """(cfg, fstate, istate): the blob of this vehicle, batch size and task as a handle of dtype holds it.  Shared: do not write to it."""
+    cfg = oracle_cfg(vehicle, n, task)
     fs, is_ = B.blob(cfg, n, np.random.RandomState(BLOB_SEED))
     if dtype == "f32":
         fs = B.to_f32(fs)
@@ -54,16 +80,16 @@ def start_state(vehicle, n, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_run(vehicle, n, dtype):
+def oracle_run(vehicle, n, dtype, task="v2"):
     """STEPS steps of the oracle alone, as the sweep runs them (last_distance drawn afresh between the steps): per step (pre, actions, o, post)."""
-    cfg, fs, is_ = start_state(vehicle, n, dtype)
+    cfg, fs, is_ = start_state(vehicle, n, dtype, task)
     rng, rng_ld = np.random.RandomState(ACTION_SEED), np.random.RandomState(RESEAT_SEED)
     pre, run = (fs, is_), []
     for t in range(STEPS):
         a = B.actions(cfg, pre[0], rng)
         o, post = B.oracle_step(cfg, pre, a)
         run.append((pre, a, o, post))
-        f = B.reseat_last_distance(cfg, o["fstate"], rng_ld)
+        f = B.reseat_last_distance(cfg, o["fstate"], rng_ld, o["istate"])
         pre = (B.to_f32(f) if dtype == "f32" else f, o["istate"])
     return cfg, run
 
@@ -85,6 +111,58 @@ def test_blob_reaches_every_branch_and_the_flip_cap_is_a_condition(vehicle, n, d
         assert all(per_step[0][k] >= 8 for k in B.CLASSES), per_step[0]
     head = {k: sum(c[k] for c in per_step[:ROLLOUT_STEPS]) for k in B.CLASSES}
     assert per_step[0]["hold_level"] + per_step[0]["hold_tilted"] >= 1 and head["hold_terminated"] >= 1, head
+
+
+def test_one_waypoint_states_are_the_ones_the_sweep_always_ran():
+    assert set(STATE_CRC) == set(STATES)
+    for key in STATES:
+        _, fs, is_ = start_state(*key)
+        assert zlib.crc32(fs.tobytes() + is_.tobytes()) == STATE_CRC[key], key
+
+
+@pytest.mark.parametrize("vehicle,n,dtype,task", TASK_STATES)
+def test_task_blob_reaches_every_branch_and_the_flip_cap_is_a_condition(vehicle, n, dtype, task):
+    """The same two conditions on the states of the v1 and the multi-waypoint cases: every class of the task within the six steps (what the
+    rollout cases rely on within theirs), and in every step no more envs within FLIP_MARGIN of a threshold than the cap."""
+    cfg, run = oracle_run(vehicle, n, dtype, task)
+    names = B.class_names(cfg)
+    per_step = []
+    for t, (pre, a, o, post) in enumerate(run):
+        m = B.margins(cfg, pre, post)
+        n_el = int(B.eligible(m).sum())
+        assert n_el <= B.flip_cap(n), f"step {t}: {n_el} envs within {B.FLIP_MARGIN} of a threshold, the cap is {B.flip_cap(n)}"
+        per_step.append({k: int(v.sum()) for k, v in B.classes(cfg, pre, post, o).items()})
+        print(f"{vehicle} {task} n={n} {dtype} step {t}: eligible {n_el}", per_step[-1])
+    assert set(per_step[0]) == set(names)
+    over = {k: sum(c[k] for c in per_step) for k in names}
+    assert all(over[k] >= 1 for k in names), over
+    head = {k: sum(c[k] for c in per_step[:ROLLOUT_STEPS]) for k in names}
+    ended_early = sum(int((o["done"] != 0).sum()) for _, _, o, _ in run[:ROLLOUT_STEPS - 1])
+    assert head["intermediate_reach"] >= 1 and ended_early >= 1, head
+    if task in V1_VARIANT:
+        assert head["final_reach_stopped"] + head["final_reach_moving"] >= 1 and head["final_reach_at_time_limit"] >= 1, head
+        assert head["reset_drew_k1"] >= 1 and head["reset_drew_k2"] >= 1, head
+    else:
+        assert per_step[0]["hold_level"] + per_step[0]["hold_tilted"] >= 1 and head["hold_terminated"] >= 1, head
+        assert head["final_first_arrival"] >= 1 and head["intermediate_reach_then_crash_or_oob"] >= 1, head
+
+
+def test_task_blobs_hold_what_their_tasks_store():
+    cfg, fs, is_ = start_state("quad", 300, "f32", "v1_raw")
+    fl = is_[O.I_FLAGS]
+    kep, idx = (fl >> 4) & 15, fl & 15
+    assert fs.shape == (22, 300) and set(kep) == {1, 2} and (idx < kep).all() and (fl >> 8 == 0).all() and (is_[O.I_COUNTER] == 0).all()
+    assert (fs[19:22, kep == 1] == 0).all() and (fs[19:22, kep == 2] != 0).all() and set(idx[kep == 2]) == {0, 1}
+    d = np.linalg.norm(fs[0:3] - B.current_waypoint(cfg, fs, is_)[0], axis=0)
+    assert d.min() > 1e-3 and (d < 0.1).sum() > 5 and ((d > 0.1) & (d < 0.5)).sum() > 20 and ((d > 0.5) & (d < 0.6)).sum() > 5
+    ms = cfg.task.max_episode_steps
+    assert ms == 1200 and ((d < 0.1) & (idx == kep - 1) & (is_[O.I_STEP] >= ms)).sum() >= 2 and (is_[O.I_STEP] < ms).any()
+    for vehicle, task, K, nf in (("quad", "v2k3", 3, 25), ("hexa", "v2k4", 4, 28), ("hexa_arm", "v2k3", 3, 31), ("hexa_arm_2j", "v2k2", 2, 26)):
+        cfg, fs, is_ = start_state(vehicle, 300, "f32", task)
+        fl = is_[O.I_FLAGS]
+        arrived = (fl & O.FLAGBIT_FWR) != 0
+        assert fs.shape == (nf, 300) and (fs[16:nf] != 0).all()
+        assert ((fl[arrived] & 1023) == (K | O.FLAGBIT_FWR | O.FLAGBIT_COUNTER_ACTIVE)).all() and set(fl[~arrived]) == set(range(K))
 
 
 def test_blob_fills_every_field_of_a_shorter_arm():
@@ -182,3 +260,35 @@ def test_compare_excuses_a_flip_only_on_a_threshold_and_only_up_to_the_cap():
     g["reward"][ks[1]] += 2.0                      # a second one: 300 envs allow one
     with pytest.raises(AssertionError):
         B.compare(g, o, on_threshold, "f32")
+
+
+# ---- compare() on a step of the v1 state machine ---------------------------------------------------------------------------------------------
+def _v1_step():
+    cfg, run = oracle_run("quad", 300, "f32", "v1_raw")
+    pre, a, o, post = run[0]
+    return o, B.margins(cfg, pre, post)
+
+
+def test_compare_accepts_a_v1_step_of_the_oracle_against_itself():
+    o, m = _v1_step()
+    for dtype in ("f32", "f64"):
+        r = B.compare(copy.deepcopy(o), o, m, dtype)
+        assert r["flips"] == 0 and r["ended"] > 10 and max(r["state"], r["reward"], r["obs"], r["ep_return"], r["terminal_obs"]) == 0.0
+
+
+@pytest.mark.parametrize("field", ["is_final column", "waypoint count of an env that goes on", "shaping-sized reward error"])
+def test_compare_rejects_one_changed_field_of_a_v1_step(field):
+    o, m = _v1_step()
+    g = copy.deepcopy(o)
+    clear = m["reward"] > 1e-2
+    on = o["done"] == 0
+    if field == "is_final column":
+        k = _pick(clear)
+        g["obs"][k, 16] = 1.0 - g["obs"][k, 16]
+    elif field == "waypoint count of an env that goes on":
+        g["istate"][O.I_FLAGS, _pick(clear & on)] ^= 0x30          # flag bits 4-7: one waypoint <-> two
+    else:
+        g["reward"][_pick(clear & on)] -= 10.0
+    for dtype in ("f32", "f64"):
+        with pytest.raises(AssertionError):
+            B.compare(g, o, m, dtype)
