@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--task", default="v2", choices=["v2", "v1_scaled", "v1_raw"],
                     help="v2: rl_train.py's env; v1_scaled / v1_raw: the v1 env files (rl_train_vecN.py imports rl_env = v1_raw) with rl_train_vecN.py's recipe")
     ap.add_argument("--normalize-obs", action="store_true", help="observation normaliser (VecNormalize(norm_obs=True, norm_reward=False), rl_train_vecN.py:10-11)")
+    ap.add_argument("--norm-reward", action="store_true", help="return-based reward scaling (VecNormalize(norm_reward=True), SB3's default: gamma .99, clip 10); "
+                    "the statistics travel inside the saved zip; ep_rew_mean and the final evaluation stay raw")
     ap.add_argument("--seed", type=int, default=0, help="env reset stream, initial weights and action noise (one run = one seed: PPO on this task is seed-sensitive)")
     ap.add_argument("--moment-scale", type=float, default=None, help="N m per unit moment action (amenv_vehicle.moment_scale; the reference quadrotor: 0.1)")
     ap.add_argument("--fused-rollout", action="store_true", help="collect every rollout as ONE launch (amenv_rollout_policy: the policy on bf16 matrix cores inside the env loop; "
@@ -86,7 +88,7 @@ def main():
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
                     gae_lambda=0.9, clip_range=0.2, ent_coef=0.01 if v1 else (1e-4 if a.resume else 5e-4), dist=dist, fused_rollout=a.fused_rollout,
-                    seed=a.seed, obs_normalizer=norm)
+                    seed=a.seed, obs_normalizer=norm, reward_normalizer=amd.RewardNormalizer(env.num_envs, device=local) if a.norm_reward else None)
     if a.resume:
         model.load_policy(a.resume)
     elif a.warm_start_pid is not None:

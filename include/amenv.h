@@ -304,6 +304,36 @@ int amenv_obsnorm_apply(amenv_obsnorm* h, const float* in, float* out, int64_t n
 int amenv_obsnorm_get(amenv_obsnorm* h, double* mean, double* var, double* count, void* stream);
 int amenv_obsnorm_set(amenv_obsnorm* h, const double* mean, const double* var, double count, void* stream);
 
+/* ---- reward normaliser: the reward half of VecNormalize(norm_reward=True) -------------------------------------------
+ * SB3's default, and the half amenv_obsnorm leaves out (the reference trains with norm_reward=False, v1/rl_train_vecN.py:11).
+ * SB3 2.6.0 semantics restated, third-party, parity unpinned, checked against a numpy restatement.  A handle holds the discounted
+ * return of every env, returns[N] (fp64, zero at creation and after reset_returns), and ONE scalar running mean / population variance /
+ * count of those returns (initial 0 / 1 / 1e-4, as amenv_obsnorm).  Per env step t, training:
+ *   1. returns = returns * gamma + r_t
+ *   2. merge the batch (mean, population variance, N) of returns into the running statistics (the parallel-moments formula)
+ *   3. out_t = clip(r_t / sqrt(var + eps), -clip, clip), var AFTER step 2
+ *   4. returns[done_t] = 0
+ * amenv_retnorm_rollout does this for the n_steps rows of a time-major block, in the order of t.  update != 0 is training; update == 0
+ * is frozen: steps 1, 2 and 4 are skipped, every row is scaled with the variance at entry, the handle does not change (dones may then be
+ * NULL).  Chunking guarantee: normalised rewards never feed back into a rollout, and the batch moments of a step depend on that step's
+ * returns and N alone, so n_steps calls of one row, one call of n_steps rows and every other split of the same rows give bit-identical
+ * outputs, statistics and returns; no floating-point atomics, so two runs from the same state are bit-identical too.  Blocks of any
+ * length are accepted (the workspace, sized at creation, is reused every 128 rows).  fp64 returns and statistics.
+ * SB3 defaults: gamma = .99, clip = 10, eps = 1e-8.  Refused with AMENV_ERR_INVALID before the device is queried or anything is
+ * launched: num_envs <= 0, gamma outside [0, 1] or not finite, NULL out / handle / buffers, n_steps <= 0, clip <= 0, eps < 0;
+ * AMENV_ERR_NO_DEVICE: no such HIP device. */
+typedef struct amenv_retnorm amenv_retnorm;
+int amenv_retnorm_create(int64_t num_envs, double gamma, int device, amenv_retnorm** out);
+int amenv_retnorm_destroy(amenv_retnorm* h);
+/* rewards_in / rewards_out [n_steps, N] f32 device buffers (may be the same), dones [n_steps, N] u8 (episode ended AT step t). */
+int amenv_retnorm_rollout(amenv_retnorm* h, int32_t n_steps, const float* rewards_in, const uint8_t* dones, float* rewards_out, int32_t update,
+                          float clip, double eps, void* stream);
+/* VecNormalize.reset(): returns = 0; the statistics stay. */
+int amenv_retnorm_reset_returns(amenv_retnorm* h, void* stream);
+/* mean, var, count and (unless NULL) returns[N] to / from HOST memory (synchronises): save / load.  set with returns == NULL keeps them. */
+int amenv_retnorm_get(amenv_retnorm* h, double* mean, double* var, double* count, double* returns, void* stream);
+int amenv_retnorm_set(amenv_retnorm* h, double mean, double var, double count, const double* returns, void* stream);
+
 /* ---- GPU-resident PPO helpers (SURVEY 8 row f3 / BASELINE config 5) ---------------------------------------------------
  * The reference trains with SB3 PPO (v2/rl_train.py:38-56).  The MLP stays in PyTorch-ROCm; these two entry points are
  * the per-env elementwise pieces of SB3's loop, on caller-owned device buffers of the CURRENT device.

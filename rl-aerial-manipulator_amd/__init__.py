@@ -17,8 +17,9 @@ from .action_delay import ActionDelay
 from .action_history import ActionHistory
 from .vec_env import GpuVecEnv
 from .obs_norm import GpuVecNormalize, ObsNormalizer
+from .reward_norm import RewardNormalizer
 from . import baselines, ppo
 from .baselines import MinSnapTrajectory, PidController, PidWaypointPolicy
 from .ppo import PPO, ActorCritic, evaluate_policy, clone_pid_policy
 
-__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]
+__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "RewardNormalizer", "PPO", "ActorCritic", "evaluate_policy", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]

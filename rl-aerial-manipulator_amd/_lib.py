@@ -132,6 +132,12 @@ SYMBOLS = {
     "amenv_obsnorm_apply": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_double, _P]),
     "amenv_obsnorm_get": (C.c_int, [_P, _P, _P, _P, _P]),
     "amenv_obsnorm_set": (C.c_int, [_P, _P, _P, C.c_double, _P]),
+    "amenv_retnorm_create": (C.c_int, [C.c_int64, C.c_double, C.c_int, C.POINTER(_P)]),
+    "amenv_retnorm_destroy": (C.c_int, [_P]),
+    "amenv_retnorm_rollout": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_float, C.c_double, _P]),
+    "amenv_retnorm_reset_returns": (C.c_int, [_P, _P]),
+    "amenv_retnorm_get": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "amenv_retnorm_set": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
     "amenv_gae": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P]),
     "amenv_policy_forward": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P]),
     "amenv_policy_forward_mfma": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),

@@ -24,6 +24,7 @@
 #include "amenv_lane_policy.hpp"
 #include "amenv_rigid_policy.hpp"
 #include "amenv_obsnorm.hpp"
+#include "amenv_retnorm.hpp"
 #include "amenv_policy.hpp"
 #include "amenv_train.hpp"
 #include "amenv_mlp_train.hpp"
@@ -1616,6 +1617,88 @@ int amenv_rollout_policy_norm(amenv* e, amenv_obsnorm* h, int32_t update, float 
     hipLaunchKernelGGL(obsnorm_merge_kernel, dim3(1), dim3(((d + 63) / 64) * 64), 0, s, h->buf, d, double(n_steps) * double(e->cfg.num_envs));
   AMENV_HIP(e, hipGetLastError());
   e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
+  return AMENV_OK;
+}
+
+// ---- reward normaliser (VecNormalize norm_reward; csrc/amenv_retnorm.hpp) ---------------------------------------------
+struct amenv_retnorm {
+  int64_t n = 0;
+  double gamma = 0.0;
+  int device = 0;
+  double* buf = nullptr;   // retnorm_words(n) doubles on the device: statistics | inv_sigma | returns | partials
+};
+
+int amenv_retnorm_create(int64_t num_envs, double gamma, int device, amenv_retnorm** out) {
+  if (!out) return fail(nullptr, AMENV_ERR_INVALID, "amenv_retnorm_create: out is NULL");
+  if (num_envs <= 0 || num_envs > (int64_t(1) << 31)) return fail(nullptr, AMENV_ERR_INVALID, "amenv_retnorm_create: num_envs must be in 1 .. 2^31");
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(nullptr, AMENV_ERR_INVALID, "amenv_retnorm_create: gamma must be in [0, 1]");   // NaN fails the comparison
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(nullptr, AMENV_ERR_NO_DEVICE, "amenv_retnorm_create: no such HIP device");
+  amenv_retnorm* h = new (std::nothrow) amenv_retnorm();
+  if (!h) return fail(nullptr, AMENV_ERR_ALLOC, "amenv_retnorm_create: out of host memory");
+  h->n = num_envs; h->gamma = gamma; h->device = device;
+  DeviceGuard g(device);
+  const size_t bytes = sizeof(double) * size_t(retnorm_words(num_envs));
+  if (hipMalloc((void**)&h->buf, bytes) != hipSuccess) { delete h; return fail(nullptr, AMENV_ERR_ALLOC, "amenv_retnorm_create: hipMalloc failed"); }
+  const double init[3] = {0.0, 1.0, 1e-4};   // mean, var, count (sb3 RunningMeanStd defaults)
+  if (hipMemset(h->buf, 0, bytes) != hipSuccess || hipMemcpy(h->buf, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(h->buf); delete h;
+    return fail(nullptr, AMENV_ERR_HIP, "amenv_retnorm_create: init copy failed");
+  }
+  *out = h;
+  return AMENV_OK;
+}
+
+int amenv_retnorm_destroy(amenv_retnorm* h) {
+  if (!h) return AMENV_OK;
+  { DeviceGuard g(h->device); if (h->buf) (void)hipFree(h->buf); }
+  delete h;
+  return AMENV_OK;
+}
+
+int amenv_retnorm_rollout(amenv_retnorm* h, int32_t n_steps, const float* rewards_in, const uint8_t* dones, float* rewards_out, int32_t update,
+                          float clip, double eps, void* stream) {
+  if (!h || n_steps <= 0 || !rewards_in || !rewards_out || (update && !dones)) return fail(nullptr, AMENV_ERR_INVALID, "amenv_retnorm_rollout: NULL argument or n_steps <= 0");
+  if (!(clip > 0.0f) || !(eps >= 0.0) || !std::isfinite(eps)) return fail(nullptr, AMENV_ERR_INVALID, "amenv_retnorm_rollout: clip must be > 0 and eps finite and >= 0");
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = h->n, waves = retnorm_waves(n);
+  for (int32_t t0 = 0; t0 < n_steps; t0 += kRetnormChunk) {   // consecutive chunks: the same bytes as one pass (the header's chunking property)
+    const int tc = std::min<int32_t>(kRetnormChunk, n_steps - t0);
+    const int64_t o = int64_t(t0) * n;
+    if (update) {
+      hipLaunchKernelGGL(retnorm_scan_kernel, dim3((unsigned)waves), dim3(64), 0, s, rewards_in + o, dones + o, tc, n, h->gamma,
+                         h->buf + retnorm_off_returns(), h->buf + retnorm_off_partials(n));
+      hipLaunchKernelGGL(retnorm_merge_kernel, dim3(1), dim3(kRetnormMergeBlock), 0, s, h->buf, tc, n, eps);
+    }
+    hipLaunchKernelGGL(retnorm_apply_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)tc), dim3(256), 0, s, rewards_in + o, rewards_out + o, n,
+                       (const double*)h->buf, update ? 0 : 1, clip, eps);
+  }
+  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
+}
+
+int amenv_retnorm_reset_returns(amenv_retnorm* h, void* stream) {
+  if (!h) return AMENV_ERR_INVALID;
+  DeviceGuard g(h->device);
+  return hipMemsetAsync(h->buf + retnorm_off_returns(), 0, sizeof(double) * size_t(h->n), (hipStream_t)stream) == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
+}
+
+int amenv_retnorm_get(amenv_retnorm* h, double* mean, double* var, double* count, double* returns, void* stream) {
+  if (!h || !mean || !var || !count) return AMENV_ERR_INVALID;
+  DeviceGuard g(h->device);
+  double st[3];
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(st, h->buf, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return AMENV_ERR_HIP;
+  if (returns && hipMemcpy(returns, h->buf + retnorm_off_returns(), sizeof(double) * size_t(h->n), hipMemcpyDeviceToHost) != hipSuccess) return AMENV_ERR_HIP;
+  *mean = st[0]; *var = st[1]; *count = st[2];
+  return AMENV_OK;
+}
+
+int amenv_retnorm_set(amenv_retnorm* h, double mean, double var, double count, const double* returns, void* stream) {
+  if (!h || !std::isfinite(mean) || !(var >= 0.0) || !std::isfinite(var) || !(count > 0.0) || !std::isfinite(count)) return AMENV_ERR_INVALID;
+  DeviceGuard g(h->device);
+  const double st[3] = {mean, var, count};
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(h->buf, st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) return AMENV_ERR_HIP;
+  if (returns && hipMemcpy(h->buf + retnorm_off_returns(), returns, sizeof(double) * size_t(h->n), hipMemcpyHostToDevice) != hipSuccess) return AMENV_ERR_HIP;
   return AMENV_OK;
 }
 

@@ -22,6 +22,7 @@ import math
 import os
 import zipfile
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -521,11 +522,20 @@ def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *
 class PPO:
     """The reference's training loop (`model = PPO(...); model.learn(...)`, v2/rl_train.py:38-56) with the rollout resident
     on the GPU.  `env` is a `GpuWaypointEnv` (auto-reset on); defaults are the reference's hyper-parameters -- with thousands
-    of envs scale `n_steps` down and `batch_size` up."""
+    of envs scale `n_steps` down and `batch_size` up.
+
+    `reward_normalizer` (a `RewardNormalizer` over the env's num_envs; None = raw rewards, the reference's set-up): what an SB3 loop over
+    `VecNormalize(norm_reward=True)` feeds its buffer.  On both rollout paths the [n_steps, N] pass runs ONCE after the rollout on the raw
+    `buffer.rewards` / `buffer.dones` (normalised rewards never feed back into the rollout, so this equals the per-step wrapper bit for
+    bit), THEN the time-limit bootstrap gamma * V(terminal_observation) is added, then GAE -- SB3's order, where the bootstrap is added to
+    the already normalised reward.  Its discount is the normaliser's own `gamma` (SB3's VecNormalize default .99, not PPO's).  With `dist`
+    the return statistics are per rank, as the observation normaliser's are: every rank scales with the statistics of its own shard.
+    `env.stats()` and the logged `ep_rew_mean` stay raw."""
 
     def __init__(self, env, policy=None, learning_rate=2e-4, n_steps=2048, batch_size=128, n_epochs=12, gamma=0.995,
                  gae_lambda=0.9, clip_range=0.2, ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True,
-                 net_arch=(128, 64, 64), seed=0, obs_normalizer=None, bootstrap_truncated=True, dist=None, use_graph=None, fused_rollout=False, fused_mlp=None, fused_rollout_fp32_stats=True):
+                 net_arch=(128, 64, 64), seed=0, obs_normalizer=None, bootstrap_truncated=True, dist=None, use_graph=None, fused_rollout=False, fused_mlp=None, fused_rollout_fp32_stats=True,
+                 reward_normalizer=None):
         if env.state_dtype != torch.float32:
             raise L.AmenvError("PPO needs the fp32 environment")
         self.env, self.dist = env, dist
@@ -551,7 +561,11 @@ class PPO:
                                    max_grad_norm=self.max_grad_norm, normalize_advantage=self.normalize_advantage,
                                    dist=dist if self.world > 1 else None, use_graph=use_graph, fused_mlp=fused_mlp)
         self.obs_normalizer = obs_normalizer
-        self.buffer = RolloutBuffer(self.n_steps, env.num_envs, env.obs_dim, env.act_dim, self.device)
+        self.reward_normalizer = reward_normalizer
+        if reward_normalizer is not None and int(reward_normalizer.num_envs) != int(env.num_envs):
+            raise L.AmenvError(f"reward_normalizer holds {reward_normalizer.num_envs} envs, the env has {env.num_envs}")
+        self._boot = None   # [n_steps, N] V(terminal_observation) at the truncated entries of the step-by-step rollout, added after the reward pass
+        self.buffer =RolloutBuffer(self.n_steps, env.num_envs, env.obs_dim, env.act_dim, self.device)
         self._clipped = torch.zeros(env.num_envs, env.act_dim, dtype=torch.float32, device=self.device)
         self._raw_obs = torch.zeros(env.num_envs, env.obs_dim, dtype=torch.float32, device=self.device) if obs_normalizer else None
         self._gen = torch.Generator(device=self.device)
@@ -592,6 +606,9 @@ class PPO:
         else:
             b.obs[0].copy_(b.obs[self.n_steps])
         gid0 = int(env.cfg.env_id_offset)
+        rnorm = self.reward_normalizer
+        if rnorm is not None and self.bootstrap_truncated and self._boot is None:
+            self._boot = torch.zeros(self.n_steps, env.num_envs, dtype=torch.float32, device=self.device)
         for t in range(self.n_steps):
             obs_t = b.obs[t]
             mean_t, value_t = pol.actor_critic(obs_t)
@@ -610,7 +627,14 @@ class PPO:
             if self.bootstrap_truncated:
                 # SB3: reward += gamma * V(terminal_observation) where the episode was cut by the time limit only
                 trunc = ((env.info_bits & (L.INFO_TERMINATED | L.INFO_TRUNCATED)) == L.INFO_TRUNCATED) & (b.dones[t] != 0)
-                b.rewards[t].addcmul_(pol.critic(term_obs), trunc.to(torch.float32), value=self.gamma)
+                if rnorm is None:
+                    b.rewards[t].addcmul_(pol.critic(term_obs), trunc.to(torch.float32), value=self.gamma)
+                else:   # deferred: the bootstrap joins the NORMALISED reward (SB3's order), so the rewards stay raw until the pass below
+                    torch.mul(pol.critic(term_obs), trunc.to(torch.float32), out=self._boot[t])
+        if rnorm is not None:
+            rnorm.normalize(b.rewards, b.dones, out=b.rewards)
+            if self.bootstrap_truncated:
+                b.rewards.add_(self._boot, alpha=self.gamma)
         b.last_values.copy_(pol.critic(b.obs[self.n_steps]))
         compute_gae(b, self.gamma, self.gae_lambda)
         self.num_timesteps += self.n_steps * env.num_envs * self.world
@@ -651,6 +675,8 @@ class PPO:
             zz = (b.actions.reshape(T * env.num_envs, -1) - mean) * torch.exp(-ls)
             b.logp.copy_((-0.5 * zz * zz - ls - 0.918938533204672742).sum(1).reshape(T, env.num_envs))
             b.values.copy_(value.reshape(T, env.num_envs))
+        if self.reward_normalizer is not None:   # the kernel wrote raw rewards; the bootstrap below joins the normalised ones (SB3's order)
+            self.reward_normalizer.normalize(b.rewards, b.dones, out=b.rewards)
         if self.bootstrap_truncated:
             trunc = ((self._info & (L.INFO_TERMINATED | L.INFO_TRUNCATED)) == L.INFO_TRUNCATED) & (b.dones != 0)
             idx = trunc.reshape(-1).nonzero().reshape(-1)
@@ -705,7 +731,8 @@ class PPO:
     # ---- checkpoints ----------------------------------------------------------------------------
     def save(self, path):
         """A zip with SB3's member names: `policy.pth` (SB3 keys: loadable into an SB3 `ActorCriticPolicy`),
-        `policy.optimizer.pth` (this class's Adam state) and `data` (hyper-parameters as plain JSON).  It is NOT a complete
+        `policy.optimizer.pth` (this class's Adam state) and `data` (hyper-parameters as plain JSON); with a reward normaliser one more
+        member, `reward_normalizer.npz` (its `state_dict`), which `load` restores into this model's normaliser.  It is NOT a complete
         SB3 archive (SB3's `data` holds cloudpickled objects); use `policy.pth` to move weights either way."""
         path = path if str(path).endswith(".zip") else str(path) + ".zip"
         data = {k: getattr(self, k) for k in ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef",
@@ -719,6 +746,10 @@ class PPO:
                 torch.save(obj, buf)
                 z.writestr(name, buf.getvalue())
             z.writestr("data", json.dumps(data))
+            if self.reward_normalizer is not None:   # return statistics + carried returns, plain numpy arrays (no pickle)
+                buf = io.BytesIO()
+                np.savez(buf, **self.reward_normalizer.state_dict())
+                z.writestr("reward_normalizer.npz", buf.getvalue())
         return path
 
     def load_policy(self, path_or_state_dict):
@@ -761,6 +792,9 @@ class PPO:
                     g["lr"] = gs["lr"]
             self.num_timesteps = int(data.get("num_timesteps", self.num_timesteps))
             self._draw = int(data.get("draw", self._draw))   # action-noise counter: resumed rollouts draw fresh noise
+            if "reward_normalizer.npz" in names and self.reward_normalizer is not None:
+                with np.load(io.BytesIO(z.read("reward_normalizer.npz")), allow_pickle=False) as sd:
+                    self.reward_normalizer.load_state_dict({k: sd[k] for k in sd.files})
         return self
 
 
