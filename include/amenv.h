@@ -285,7 +285,8 @@ int amenv_stats_read(amenv* env, amenv_stats* host_out, int reset, void* stream)
  * pattern of the kernel under test, for calibrating the PMC counters FETCH_SIZE / WRITE_SIZE (tools/pmc_traffic.py). */
 int amenv_calibration_copy(const void* src, void* dst, size_t bytes, int32_t bytes_per_lane, void* stream);
 
-/* Name, VGPR count etc. of the step kernel chosen for this handle (for bench/profiles). */
+/* Name, VGPR count etc. of the step kernel chosen for this handle (for bench/profiles), formed from the handle's state at the time of
+ * the call; the pointer is valid until the next call on the handle. */
 const char* amenv_kernel_name(const amenv* env);
 
 /* ---- observation normaliser: VecNormalize(norm_obs=True, norm_reward=False) (v1/rl_train_vecN.py:10-11) ------------
@@ -354,8 +355,9 @@ int amenv_gaussian_act(const float* mean, const float* log_std, const float* low
  * v2/rl_train.py:27-30) in ONE launch: mean_out [n, act_dim] = action_net(pi trunk(obs)), value_out [n] = value_net(vf trunk(obs));
  * either output may be NULL.  flat_params = the policy's parameters in SB3 state-dict order in one contiguous fp32 buffer
  * (log_std, mlp_extractor.policy_net.{0,2,4}.{weight,bias}, mlp_extractor.value_net.{0,2,4}.{weight,bias}, action_net, value_net:
- * 30,537 floats for 20-D / 4-D).  (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6)} (v2 | hexacopter + 3-link arm | v1 |
- * hexacopter + 1- / 2-link arm). */
+ * 30,537 floats for 20-D / 4-D).  (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6), (24,4), (28,4), (21,4), (25,4)}: v2 |
+ * hexacopter + 3-link arm | v1 | hexacopter + 1- / 2-link arm | the rigid vehicles' v2 rows with one / two action rows of history
+ * (amenv_set_action_history) | their v1 rows with one / two.  Any other pair: AMENV_ERR_INVALID, nothing enqueued. */
 int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out,
                          float* value_out, void* stream);
 
@@ -593,7 +595,8 @@ int amenv_ppo_loss_grad(const float* mean, const float* value, const float* log_
  * (v_mfma_f32_32x32x16_bf16, fp32 accumulation; what is dropped is below one fp32 rounding), so the result is as close to the same loss in
  * fp64 as autograd on the fp32 torch modules is (tests/test_gpu_ppo.py).  flat_params / flat_grad: the policy's parameters / their gradients in SB3 state-dict order (see
  * amenv_policy_forward); obs [n, obs_dim], actions [n, act_dim], old_logp / advantages / returns [n] f32; stats4 as amenv_ppo_loss_grad.
- * (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6)}.  index: NULL, or n row numbers -- minibatch sample s is row index[s] of obs / actions /
+ * (obs_dim, act_dim) in {(20,4), (29,7), (17,4), (25,5), (27,6), (24,4), (28,4), (21,4), (25,4)} -- amenv_policy_forward's nine, the last four being the
+ * rigid vehicles' rows with action history; any other pair: AMENV_ERR_INVALID, nothing enqueued.  index: NULL, or n row numbers -- minibatch sample s is row index[s] of obs / actions /
  * old_logp / advantages / returns (SB3 draws its minibatches as slices of a permutation of the rollout buffer, RolloutBuffer.get: the
  * gather happens inside the kernel, the rollout tensors stay where they are).  Deterministic: no atomics on the gradient path.
  * workspace: amenv_ppo_mlp_workspace_bytes() bytes, 16-byte aligned. */

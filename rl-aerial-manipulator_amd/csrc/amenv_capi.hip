@@ -78,7 +78,7 @@ struct amenv {
   bool delay_path() const { return delay || hist > 0; }   // the DELAY instantiations run: the latency, the history (range (0, 0) without the latency) or both
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
-  std::string kname;
+  mutable std::string kname;       // amenv_kernel_name forms it from the state above when it is asked for
 };
 
 static thread_local std::string g_create_err;
@@ -624,9 +624,33 @@ hipError_t with_task(const amenv& e, F f) {
   if (e.cfg.task.num_waypoints == 1) return f(const_c<1>{}, const_c<VAR_V2>{});
   return f(const_c<AMENV_MAX_WAYPOINTS>{}, const_c<VAR_V2>{});
 }
+// the kernels built for 4 and 6 rotors alone (the caller has refused every other count): f(const_c<NROT>)
+template <typename F>
+auto with_rotors46(int nr, F f) { return nr == 4 ? f(const_c<4>{}) : f(const_c<6>{}); }
 
+// The (obs_dim, act_dim) pairs the policy kernels are built for (amenv_policy_forward, amenv_policy_forward_mfma, amenv_ppo_mlp_step), stated once here
+// for the library; ActorCritic._FUSED_DIMS (ppo.py) and the comments in include/amenv.h name the same nine, tests/test_gpu_policy_shapes.py holds them together
+template <int D, int A> struct shape_c {};
+template <typename... S> struct shape_list {};
+using PolicyShapes = shape_list<shape_c<20, 4>, shape_c<29, 7>, shape_c<17, 4>, shape_c<25, 5>, shape_c<27, 6>,   // v2 | hexacopter + 3-link arm | v1 | hexacopter + 1- / 2-link arm
+                                shape_c<24, 4>, shape_c<28, 4>, shape_c<21, 4>, shape_c<25, 4>>;                  // v2 / v1 rows of the rigid vehicles with one or two action rows of history
+// the action widths amenv_gaussian_act and amenv_ppo_loss_grad are built for: 4 = quad / hexa, 4 + n = hexa + n joints (the rows' width plays no part: 0)
+using ActionWidths = shape_list<shape_c<0, 4>, shape_c<0, 5>, shape_c<0, 6>, shape_c<0, 7>>;
+// f(const_c<D>, const_c<A>) for the listed pair that equals (d, a); hipErrorInvalidValue when none does
+template <typename F, int... D, int... A>
+hipError_t with_shape(shape_list<shape_c<D, A>...>, int d, int a, const F& f) {
+  hipError_t st = hipErrorInvalidValue;
+  (void)((d == D && a == A && (st = f(const_c<D>{}, const_c<A>{}), true)) || ...);
+  return st;
+}
+template <typename F> hipError_t with_policy_shape(int obs_dim, int act_dim, const F& f) { return with_shape(PolicyShapes{}, obs_dim, act_dim, f); }
+template <typename F> hipError_t with_act_dim(int act_dim, const F& f) { return with_shape(ActionWidths{}, 0, act_dim, [&](auto, auto a) { return f(a); }); }
+bool policy_shape_built(int obs_dim, int act_dim) { return with_policy_shape(obs_dim, act_dim, [](auto, auto) { return hipSuccess; }) == hipSuccess; }
+bool act_dim_built(int act_dim) { return with_act_dim(act_dim, [](auto) { return hipSuccess; }) == hipSuccess; }
+
+// The launchers below pick the handle's arithmetic type themselves: behind each template a plain overload that the entry points call
 template <typename T>
-hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed = false) {
+hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
   if (e.cfg.vehicle.n_joints == 3) {
     if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
     return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
@@ -637,6 +661,7 @@ hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStrea
     });
   });
 }
+hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed = false) { return e.cfg.dtype == AMENV_F64 ? dispatch_step<double>(e, io, T_steps, s, timed) : dispatch_step<float>(e, io, T_steps, s, timed); }
 
 template <typename T>
 hipError_t launch_reset(const amenv& e, const uint8_t* mask, float* obs, int pad_only, hipStream_t s) {
@@ -645,6 +670,7 @@ hipError_t launch_reset(const amenv& e, const uint8_t* mask, float* obs, int pad
                      e.cfg.task.ee_task, e.tile_bytes, make_cold(e), make_arm<T>(e), e.blob, mask, obs, pad_only, make_noise_rt(e));
   return hipGetLastError();
 }
+hipError_t launch_reset(const amenv& e, const uint8_t* mask, float* obs, int pad_only, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_reset<double>(e, mask, obs, pad_only, s) : launch_reset<float>(e, mask, obs, pad_only, s); }
 
 template <typename T>
 hipError_t launch_observe(const amenv& e, float* obs, float* ee, hipStream_t s) {
@@ -654,6 +680,7 @@ hipError_t launch_observe(const amenv& e, float* obs, float* ee, hipStream_t s) 
   if (ee) hipLaunchKernelGGL((ee_position_kernel<T>), dim3((n + bs - 1) / bs), dim3(bs), 0, s, n, K, nj, e.tile_bytes, make_arm<T>(e), (const void*)e.blob, ee);
   return hipGetLastError();
 }
+hipError_t launch_observe(const amenv& e, float* obs, float* ee, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_observe<double>(e, obs, ee, s) : launch_observe<float>(e, obs, ee, s); }
 
 template <typename T>
 hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hipStream_t s) {
@@ -661,6 +688,7 @@ hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hip
   hipLaunchKernelGGL((transpose_state_kernel<T>), dim3((n + bs - 1) / bs), dim3(bs), 0, s, n, e.nf, e.cfg.task.num_waypoints, e.pub_nj /* the caller's joint fields: th[0..n), thd[0..n) */, e.tile_bytes, e.blob, (T*)f, i, to_api);
   return hipGetLastError();
 }
+hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_transpose<double>(e, f, i, to_api, s) : launch_transpose<float>(e, f, i, to_api, s); }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -750,10 +778,12 @@ template <typename T>
 hipError_t launch_lag_reset(const amenv& e, const uint8_t* mask, hipStream_t s) {
   const int n = e.cfg.num_envs;
   const dim3 grid(e.n_tiles / 4), block(256);
-  if (e.cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((lag_reset_kernel<T, 4>), grid, block, 0, s, n, make_lag<T, 4>(e), mask);
-  else hipLaunchKernelGGL((lag_reset_kernel<T, 6>), grid, block, 0, s, n, make_lag<T, 6>(e), mask);
+  with_rotors46(e.cfg.vehicle.n_rotors, [&](auto nrot) {
+    hipLaunchKernelGGL((lag_reset_kernel<T, decltype(nrot)::value>), grid, block, 0, s, n, make_lag<T, decltype(nrot)::value>(e), mask);
+  });
   return hipGetLastError();
 }
+hipError_t launch_lag_reset(const amenv& e, const uint8_t* mask, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(e, mask, s) : launch_lag_reset<float>(e, mask, s); }
 template <typename T>
 hipError_t launch_lag_transpose(const amenv& e, void* api, int to_api, hipStream_t s) {
   const int n = e.cfg.num_envs;
@@ -761,6 +791,7 @@ hipError_t launch_lag_transpose(const amenv& e, void* api, int to_api, hipStream
                      static_cast<T*>(api), to_api);
   return hipGetLastError();
 }
+hipError_t launch_lag_transpose(const amenv& e, void* api, int to_api, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_lag_transpose<double>(e, api, to_api, s) : launch_lag_transpose<float>(e, api, to_api, s); }
 
 // amenv_set_action_delay (off -> on) / amenv_reset: the masked envs (mask null = all; padding lanes always, as reset_kernel does) draw d for
 // the episode the blob holds by now and get 8 hover rows
@@ -1042,7 +1073,7 @@ int amenv_create(const amenv_config* cfg, int device, amenv** out) {
       (s = hipMemset(e->blob, 0, e->blob_bytes)) != hipSuccess ||
       (s = hipMemset(e->stats, 0, sizeof(unsigned long long) * kStatsWords)) != hipSuccess ||
       // give the padding lanes of the last tile a valid state (real envs stay untouched: episode 0)
-      (s = (cfg->dtype == AMENV_F64 ? launch_reset<double>(*e, nullptr, nullptr, 1, nullptr) : launch_reset<float>(*e, nullptr, nullptr, 1, nullptr))) != hipSuccess ||
+      (s = launch_reset(*e, nullptr, nullptr, 1, nullptr)) != hipSuccess ||
       (s = hipDeviceSynchronize()) != hipSuccess)
     return alloc_failed("device allocation failed", s);
   // the lane-quad / fp32 lane-team constants (every kernel of theirs: step, rollout, closed-loop rollout) + the packed policy of amenv_rollout_policy
@@ -1082,7 +1113,7 @@ int amenv_destroy(amenv* e) {
 }
 
 const char* amenv_last_error(const amenv* e) { return e ? e->err.c_str() : g_create_err.c_str(); }
-const char* amenv_kernel_name(const amenv* e) { return e ? e->kname.c_str() : ""; }
+const char* amenv_kernel_name(const amenv* e) { return e ? (e->kname = kernel_name(*e)).c_str() : ""; }   // of the handle's state by now: no setter keeps it current
 
 namespace {
 hipError_t pad_actions(const amenv& e, const float* actions, hipStream_t s) {
@@ -1124,7 +1155,6 @@ int amenv_set_randomization(amenv* e, const amenv_randomization* r) {
   if (!r) {
     e->dr = false;
     e->dr_r = DrRanges{{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
-    e->kname = kernel_name(*e);
     return AMENV_OK;
   }
   if (r->struct_size != sizeof(amenv_randomization)) return fail(e, AMENV_ERR_INVALID, "amenv_set_randomization: struct_size must be sizeof(amenv_randomization)");
@@ -1140,7 +1170,6 @@ int amenv_set_randomization(amenv* e, const amenv_randomization* r) {
   for (int q = 0; q < 3; q++) { R.lo[q] = rg[q][0]; R.span[q] = rg[q][1] - rg[q][0]; }
   e->dr = true;
   e->dr_r = R;
-  e->kname = kernel_name(*e);
   return AMENV_OK;
 }
 
@@ -1152,8 +1181,7 @@ int amenv_dynamics_factors(amenv* e, float* out, void* stream) {
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((n + 255) / 256), block(256);
-  if (nr == 4) hipLaunchKernelGGL(dr_factors_kernel<4>, grid, block, 0, s, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->dr_r, out);
-  else hipLaunchKernelGGL(dr_factors_kernel<6>, grid, block, 0, s, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->dr_r, out);
+  with_rotors46(nr, [&](auto nrot) { hipLaunchKernelGGL(dr_factors_kernel<decltype(nrot)::value>, grid, block, 0, s, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->dr_r, out); });
   AMENV_HIP(e, hipGetLastError());
   return AMENV_OK;
 }
@@ -1163,7 +1191,6 @@ int amenv_set_sensor_noise(amenv* e, const amenv_sensor_noise* z) {
   const NoiseSig off = {0.0f, 0.0f, 0.0f, 0.0f};
   if (!z) {   // off: the handle launches the kernels it launched before
     e->noise = false; e->noise_s = off;
-    e->kname = kernel_name(*e);
     return AMENV_OK;
   }
   if (z->struct_size != sizeof(amenv_sensor_noise)) return fail(e, AMENV_ERR_INVALID, "amenv_set_sensor_noise: struct_size must be sizeof(amenv_sensor_noise)");
@@ -1178,7 +1205,6 @@ int amenv_set_sensor_noise(amenv* e, const amenv_sensor_noise* z) {
   const bool any = sg[0] != 0.0f || sg[1] != 0.0f || sg[2] != 0.0f || sg[3] != 0.0f;   // all zeros: the same as off
   e->noise = any;
   e->noise_s = any ? NoiseSig{sg[0], sg[1], sg[2], sg[3]} : off;
-  e->kname = kernel_name(*e);
   return AMENV_OK;
 }
 
@@ -1197,7 +1223,6 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   if (!e) return AMENV_ERR_INVALID;
   if (!lag) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused)
     e->lag = false;
-    e->kname = kernel_name(*e);
     return AMENV_OK;
   }
   const amenv_vehicle& v = e->cfg.vehicle;
@@ -1225,9 +1250,8 @@ int amenv_set_rotor_lag(amenv* e, const amenv_rotor_lag* lag) {
   const bool was_on = e->lag;
   for (int q = 0; q < 2; q++) e->lag_a[q] = -std::expm1(-e->cfg.task.dt / tau[q]);
   e->lag = true;
-  e->kname = kernel_name(*e);
   if (!was_on) {     // off -> on: every rotor at the nominal hover command; on -> on keeps the states (curricula)
-    AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, nullptr, nullptr) : launch_lag_reset<float>(*e, nullptr, nullptr));
+    AMENV_HIP(e, launch_lag_reset(*e, nullptr, nullptr));
     AMENV_HIP(e, hipDeviceSynchronize());
   }
   return AMENV_OK;
@@ -1251,7 +1275,6 @@ int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
   if (!z) {   // off: the handle launches the kernels it launched before (the side buffer stays allocated, unused) -- or, while the action history is
     // on, the DELAY kernels with range (0, 0): every env keeps its d and its rows, the episodes that start from now on draw 0
     e->delay = false;
-    e->kname = kernel_name(*e);
     return AMENV_OK;
   }
   if (z->struct_size != sizeof(amenv_action_delay)) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_delay: struct_size must be sizeof(amenv_action_delay)");
@@ -1263,7 +1286,6 @@ int amenv_set_action_delay(amenv* e, const amenv_action_delay* z) {
   const bool was_on = e->delay;
   e->delay_lo = z->min_steps; e->delay_hi = z->max_steps;
   e->delay = true;
-  e->kname = kernel_name(*e);
   if (!was_on) {     // off -> on: every env draws d for its current episode and gets hover rows; on -> on keeps d and the rows (curricula)
     AMENV_HIP(e, launch_delay_reset(*e, nullptr, nullptr));
     AMENV_HIP(e, hipDeviceSynchronize());
@@ -1276,7 +1298,6 @@ int amenv_set_action_history(amenv* e, int32_t rows) {
   if (rows < 0 || rows > 2) return fail(e, AMENV_ERR_INVALID, "amenv_set_action_history: rows must be 0 (off), 1 or 2");
   if (rows == 0) {   // off: base-width rows again; without the delay the handle launches the kernels it launched before (the buffers stay allocated, unused)
     e->hist = 0;
-    e->kname = kernel_name(*e);
     return AMENV_OK;
   }
   if (int rc = rigid_switch_served(e, "amenv_set_action_history", true)) return rc;
@@ -1290,7 +1311,6 @@ int amenv_set_action_history(amenv* e, int32_t rows) {
   }
   const bool buffer_live = e->delay_path();   // the delay or the history has kept the buffer current
   e->hist = rows;
-  e->kname = kernel_name(*e);
   if (!buffer_live) {   // neither was on: hover rows, and d = 0 from the range (0, 0)
     AMENV_HIP(e, launch_delay_reset(*e, nullptr, nullptr));
     AMENV_HIP(e, hipDeviceSynchronize());
@@ -1331,7 +1351,7 @@ int amenv_get_rotor_state(amenv* e, void* out, void* stream) {
   if (!e->lag) return fail(e, AMENV_ERR_INVALID, "amenv_get_rotor_state: the rotor lag is off (amenv_set_rotor_lag)");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_transpose<double>(*e, out, 1, s) : launch_lag_transpose<float>(*e, out, 1, s));
+  AMENV_HIP(e, launch_lag_transpose(*e, out, 1, s));
   return AMENV_OK;
 }
 
@@ -1341,7 +1361,7 @@ int amenv_set_rotor_state(amenv* e, const void* in, void* stream) {
   if (!e->lag) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_state: the rotor lag is off (amenv_set_rotor_lag)");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_transpose<double>(*e, const_cast<void*>(in), 0, s) : launch_lag_transpose<float>(*e, const_cast<void*>(in), 0, s));
+  AMENV_HIP(e, launch_lag_transpose(*e, const_cast<void*>(in), 0, s));
   return AMENV_OK;
 }
 
@@ -1350,8 +1370,8 @@ int amenv_reset(amenv* e, const uint8_t* mask, float* obs_out, void* stream) {
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
   float* o = (e->io_obs && obs_out) ? e->io_obs : (e->hist && obs_out) ? e->hist_obs : obs_out;   // (the history is refused on the arms: at most one of the two)
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_reset<double>(*e, mask, o, 0, s) : launch_reset<float>(*e, mask, o, 0, s));
-  if (e->lag) AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_lag_reset<double>(*e, mask, s) : launch_lag_reset<float>(*e, mask, s));
+  AMENV_HIP(e, launch_reset(*e, mask, o, 0, s));
+  if (e->lag) AMENV_HIP(e, launch_lag_reset(*e, mask, s));
   if (e->delay_path()) AMENV_HIP(e, launch_delay_reset(*e, mask, s));
   if (o == e->hist_obs && o) AMENV_HIP(e, launch_hist_widen(*e, obs_out, s));   // hover rows for the masked envs, the current history for the others
   else if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
@@ -1363,7 +1383,7 @@ int amenv_observe(amenv* e, float* obs_out, void* stream) {
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
   float* o = e->io_obs ? e->io_obs : e->hist ? e->hist_obs : obs_out;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_observe<double>(*e, o, nullptr, s) : launch_observe<float>(*e, o, nullptr, s));
+  AMENV_HIP(e, launch_observe(*e, o, nullptr, s));
   if (e->hist) AMENV_HIP(e, launch_hist_widen(*e, obs_out, s));
   else if (o != obs_out) AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs_out, s));
   return AMENV_OK;
@@ -1373,7 +1393,7 @@ int amenv_ee_position(amenv* e, float* ee_out, void* stream) {
   if (!e || !ee_out) return fail(e, AMENV_ERR_INVALID, "amenv_ee_position: NULL argument");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_observe<double>(*e, nullptr, ee_out, s) : launch_observe<float>(*e, nullptr, ee_out, s));
+  AMENV_HIP(e, launch_observe(*e, nullptr, ee_out, s));
   return AMENV_OK;
 }
 
@@ -1386,7 +1406,7 @@ int step_launch(amenv* e, const char* who, const float* actions, float* obs, voi
   DeviceGuard g(e->device);
   StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, e->stats};
   if (e->io_act) { AMENV_HIP(e, pad_actions(*e, actions, s)); io.actions = reinterpret_cast<const float4*>(e->io_act); io.obs = e->io_obs; io.terminal_obs = terminal_obs ? e->io_term : nullptr; }
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? dispatch_step<double>(*e, io, 0, s, timed) : dispatch_step<float>(*e, io, 0, s, timed));
+  AMENV_HIP(e, dispatch_step(*e, io, 0, s, timed));
   if (e->io_act) { AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs, s)); if (terminal_obs) AMENV_HIP(e, cut_obs(*e, e->io_term, done, terminal_obs, s)); }
   e->steps += uint64_t(e->cfg.num_envs);
   return AMENV_OK;
@@ -1424,8 +1444,7 @@ int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, v
   if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: arms with 1 or 2 joints are served through amenv_step (the adapters at the C ABI are per step)");
   DeviceGuard g(e->device);
   StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, nullptr, nullptr, nullptr, e->stats};
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t st = e->cfg.dtype == AMENV_F64 ? dispatch_step<double>(*e, io, n_steps, s) : dispatch_step<float>(*e, io, n_steps, s);
+  hipError_t st = dispatch_step(*e, io, n_steps, (hipStream_t)stream);
   AMENV_HIP(e, st);
   e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
   return AMENV_OK;
@@ -1450,8 +1469,9 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
   if (quad) {   // rigid vehicle, single-waypoint v2 task, default workgroup size: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
     const QuadParams QP = make_quad(*e);
     const dim3 gq(e->n_tiles * 4), bq(256);
-    if (e->cfg.vehicle.n_rotors == 4) hipLaunchKernelGGL((rollout_policy_kernel_quad<4>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
-    else hipLaunchKernelGGL((rollout_policy_kernel_quad<6>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
+    with_rotors46(e->cfg.vehicle.n_rotors, [&](auto nrot) {
+      hipLaunchKernelGGL((rollout_policy_kernel_quad<decltype(nrot)::value>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
+    });
   } else if (rigid) {   // every other rigid config (v1 tasks, 2..4 waypoints, a set workgroup size): one lane per env (amenv_rigid_policy.hpp)
     AMENV_HIP(e, launch_rigid_policy<false>(*e, (int)n_steps, io, NormArg{nullptr, 0.0f, 0.0, 0}, s));
   } else if (e->family == StepFamily::Team && !e->io_act) {   // the caller's vehicle is the 3-joint z,x,x arm on one waypoint
@@ -1473,7 +1493,7 @@ int amenv_get_state(amenv* e, void* fstate, int32_t* istate, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_transpose<double>(*e, fstate, istate, 1, s) : launch_transpose<float>(*e, fstate, istate, 1, s));
+  AMENV_HIP(e, launch_transpose(*e, fstate, istate, 1, s));
   return AMENV_OK;
 }
 
@@ -1481,8 +1501,7 @@ int amenv_set_state(amenv* e, const void* fstate, const int32_t* istate, void* s
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, e->cfg.dtype == AMENV_F64 ? launch_transpose<double>(*e, const_cast<void*>(fstate), const_cast<int32_t*>(istate), 0, s)
-                                          : launch_transpose<float>(*e, const_cast<void*>(fstate), const_cast<int32_t*>(istate), 0, s));
+  AMENV_HIP(e, launch_transpose(*e, const_cast<void*>(fstate), const_cast<int32_t*>(istate), 0, s));
   return AMENV_OK;
 }
 
@@ -1716,44 +1735,32 @@ int amenv_gae(const float* rewards, const float* values, const uint8_t* dones, c
 
 int amenv_gaussian_act(const float* mean, const float* log_std, const float* low, const float* high, float* raw, float* clipped,
                        float* logp, int64_t n_envs, int32_t act_dim, uint64_t seed, uint32_t draw, int64_t env_id_offset, void* stream) {
-  if (!mean || !log_std || !low || !high || !raw || !clipped || !logp || n_envs <= 0 || env_id_offset < 0) return AMENV_ERR_INVALID;
+  if (!mean || !log_std || !low || !high || !raw || !clipped || !logp || n_envs <= 0 || env_id_offset < 0 || !act_dim_built(act_dim)) return AMENV_ERR_INVALID;
   const int bs = n_envs <= 65536 ? 64 : 256;
   const dim3 grid((unsigned)((n_envs + bs - 1) / bs)), block(bs);
   const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
-  switch (act_dim) {
-    case 4: hipLaunchKernelGGL(gaussian_act_kernel<4>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
-    case 5: hipLaunchKernelGGL(gaussian_act_kernel<5>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
-    case 6: hipLaunchKernelGGL(gaussian_act_kernel<6>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
-    case 7: hipLaunchKernelGGL(gaussian_act_kernel<7>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset); break;
-    default: return AMENV_ERR_INVALID;   // 4 = quad/hexa, 4 + n = hexa + n joints
-  }
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
+  const hipError_t st = with_act_dim(act_dim, [&](auto a) {
+    hipLaunchKernelGGL(gaussian_act_kernel<decltype(a)::value>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset);
+    return hipGetLastError();
+  });
+  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
 int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out,
                          float* value_out, void* stream) {
-  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out)) return AMENV_ERR_INVALID;
+  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !policy_shape_built(obs_dim, act_dim)) return AMENV_ERR_INVALID;
   const dim3 grid((unsigned)((n + 63) / 64), 2), block(64 * kPolWaves);
   hipStream_t s = (hipStream_t)stream;
-  if (obs_dim == 20 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<20, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 29 && act_dim == 7) hipLaunchKernelGGL((policy_forward_kernel<29, 7>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 17 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<17, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 25 && act_dim == 5) hipLaunchKernelGGL((policy_forward_kernel<25, 5>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 27 && act_dim == 6) hipLaunchKernelGGL((policy_forward_kernel<27, 6>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  // the rigid vehicles' rows with one or two action rows of history
-  else if (obs_dim == 24 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<24, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 28 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<28, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 21 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<21, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 25 && act_dim == 4) hipLaunchKernelGGL((policy_forward_kernel<25, 4>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-  else return AMENV_ERR_INVALID;   // (20,4) v2 | (29,7) hexacopter + arm | (17,4) v1 | (25,5) / (27,6) hexacopter + 1- / 2-link arm
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
+  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((policy_forward_kernel<decltype(d)::value, decltype(a)::value>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
+    return hipGetLastError();
+  });
+  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
 int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out, float* value_out,
                               void* workspace, void* stream) {
-  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return AMENV_ERR_INVALID;
-  if (!((obs_dim == 20 && act_dim == 4) || (obs_dim == 29 && act_dim == 7) || (obs_dim == 17 && act_dim == 4) || (obs_dim == 25 && act_dim == 5) ||
-        (obs_dim == 27 && act_dim == 6) || (act_dim == 4 && (obs_dim == 24 || obs_dim == 28 || obs_dim == 21 || obs_dim == 25))))
+  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u) || !policy_shape_built(obs_dim, act_dim))
     return AMENV_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   uint16_t* WS = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + kMlpWsAdv);   // the split-weight area of amenv_ppo_mlp_step's workspace
@@ -1762,16 +1769,11 @@ int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t
   const int nets = (mean_out ? 1 : 0) + (value_out ? 1 : 0);   // two wavefronts per SIMD (242 registers): 512 workgroups fill the chip
   const dim3 grid((unsigned)std::min<int64_t>(512 / nets, (ntiles + 3) / 4), 2), block(256);
   const u32x4* ws = reinterpret_cast<const u32x4*>(WS);
-  if (obs_dim == 20) hipLaunchKernelGGL((mlp_forward_kernel<20, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 29) hipLaunchKernelGGL((mlp_forward_kernel<29, 7>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 17) hipLaunchKernelGGL((mlp_forward_kernel<17, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 25 && act_dim == 5) hipLaunchKernelGGL((mlp_forward_kernel<25, 5>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 24) hipLaunchKernelGGL((mlp_forward_kernel<24, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 28) hipLaunchKernelGGL((mlp_forward_kernel<28, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 21) hipLaunchKernelGGL((mlp_forward_kernel<21, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else if (obs_dim == 25) hipLaunchKernelGGL((mlp_forward_kernel<25, 4>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  else hipLaunchKernelGGL((mlp_forward_kernel<27, 6>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
+  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    hipLaunchKernelGGL((mlp_forward_kernel<decltype(d)::value, decltype(a)::value>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
+    return hipGetLastError();   // (of the pack kernel's launch too)
+  });
+  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
 size_t amenv_ppo_workspace_bytes(void) { return size_t(kPpoMaxBlocks) * (2 * sizeof(double) + kPpoPartial * sizeof(float)); }
@@ -1781,24 +1783,18 @@ int amenv_ppo_loss_grad(const float* mean, const float* value, const float* log_
                         float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
                         void* workspace, void* stream) {
   if (!mean || !value || !log_std || !actions || !old_logp || !advantages || !returns || !d_mean || !d_value || !d_log_std || !stats4 ||
-      !workspace || n <= 0 || !(clip_range >= 0.0f) || (reinterpret_cast<uintptr_t>(workspace) & 7u))
+      !workspace || n <= 0 || !(clip_range >= 0.0f) || (reinterpret_cast<uintptr_t>(workspace) & 7u) || !act_dim_built(act_dim))
     return AMENV_ERR_INVALID;
   const int blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
   double* adv_part = static_cast<double*>(workspace);
   float* part = reinterpret_cast<float*>(adv_part + 2 * kPpoMaxBlocks);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ppo_adv_partials, dim3(blocks), dim3(kPpoBlock), 0, s, advantages, (int64_t)n, adv_part);
-  switch (act_dim) {
-    case 4: hipLaunchKernelGGL(ppo_loss_grad<4>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
-                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
-    case 7: hipLaunchKernelGGL(ppo_loss_grad<7>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
-                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
-    case 5: hipLaunchKernelGGL(ppo_loss_grad<5>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
-                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
-    case 6: hipLaunchKernelGGL(ppo_loss_grad<6>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
-                               (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part); break;
-    default: return AMENV_ERR_INVALID;
-  }
+  (void)with_act_dim(act_dim, [&](auto a) {   // (a launch error is read below)
+    hipLaunchKernelGGL(ppo_loss_grad<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
+                       (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part);
+    return hipSuccess;
+  });
   hipLaunchKernelGGL(ppo_finalize, dim3(1), dim3(64), 0, s, (const float*)part, blocks, (int)act_dim, (int64_t)n, log_std, ent_coef, d_log_std, stats4);
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
@@ -1820,7 +1816,7 @@ int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_di
                        const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
                        int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, void* stream) {
   if (!flat_params || !obs || !actions || !old_logp || !advantages || !returns || !flat_grad || !stats4 || !workspace || n <= 0 || !(clip_range >= 0.0f) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15u))
+      (reinterpret_cast<uintptr_t>(workspace) & 15u) || !policy_shape_built(obs_dim, act_dim))
     return AMENV_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
@@ -1832,17 +1828,10 @@ int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_di
   const int blocks = int(std::min<int64_t>(128, (ntiles + 3) / 4));   // 128 x 2 nets x 4 wavefronts = one wavefront per SIMD
   hipLaunchKernelGGL(ppo_mlp_prologue_kernel, dim3(adv_blocks + (2 * kMlpPackThreadsPerNet + kPpoBlock - 1) / kPpoBlock), dim3(kPpoBlock), 0, s, advantages, (int64_t)n, adv_part, index,
                      adv_blocks, flat_params, (int)obs_dim, (int)act_dim, WS);
-  hipError_t st;
-  if (obs_dim == 20 && act_dim == 4) st = launch_mlp_step<20, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 29 && act_dim == 7) st = launch_mlp_step<29, 7>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 17 && act_dim == 4) st = launch_mlp_step<17, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 25 && act_dim == 5) st = launch_mlp_step<25, 5>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 27 && act_dim == 6) st = launch_mlp_step<27, 6>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 24 && act_dim == 4) st = launch_mlp_step<24, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 28 && act_dim == 4) st = launch_mlp_step<28, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 21 && act_dim == 4) st = launch_mlp_step<21, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else if (obs_dim == 25 && act_dim == 4) st = launch_mlp_step<25, 4>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks, part, blocks, s);
-  else return AMENV_ERR_INVALID;
+  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
+    return launch_mlp_step<decltype(d)::value, decltype(a)::value>(flat_params, reinterpret_cast<const u32x4*>(WS), obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef,
+                                                                   normalize_advantage, adv_part, adv_blocks, part, blocks, s);
+  });
   if (st != hipSuccess) return AMENV_ERR_HIP;
   const int trunk = kH1 * obs_dim + kH1 + kH2 * kH1 + kH2 + kH3 * kH2 + kH3;
   const int total = act_dim + 2 * trunk + act_dim * kH3 + act_dim + kH3 + 1;

@@ -10,6 +10,21 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .action_delay import ActionDelay
+from .action_history import ActionHistory
+from .randomization import DynamicsRandomization
+from .rotor_lag import RotorLag
+from .sensor_noise import SensorNoise
+
+# The opt-in switches, in the order the constructor applies them: keyword = attribute = the <name> of set_<name> and amenv_set_<name> ->
+# (class, the method that gives its C struct; the history's argument is its row count)
+_SWITCHES = {"randomization": (DynamicsRandomization, "to_c"), "rotor_lag": (RotorLag, "to_c"), "sensor_noise": (SensorNoise, "to_c"),
+             "action_delay": (ActionDelay, "_as_c"), "action_history": (ActionHistory, None)}
+
+
+def _typed(who, x, cls):
+    if x is not None and not isinstance(x, cls):
+        raise L.AmenvError(f"{who}: expected {'an' if cls.__name__[0] in 'AEIOU' else 'a'} {cls.__name__} or None, got {type(x).__name__}")
 
 
 def _dev_index(device):
@@ -34,18 +49,10 @@ class GpuWaypointEnv:
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
                  rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
                  sensor_noise=None, action_delay=None, action_history=None):
-        from .action_delay import ActionDelay
-        from .action_history import ActionHistory
-        from .rotor_lag import RotorLag
-        from .sensor_noise import SensorNoise
-        if rotor_lag is not None and not isinstance(rotor_lag, RotorLag):   # before any device is touched
-            raise L.AmenvError(f"rotor_lag: expected a RotorLag or None, got {type(rotor_lag).__name__}")
-        if sensor_noise is not None and not isinstance(sensor_noise, SensorNoise):
-            raise L.AmenvError(f"sensor_noise: expected a SensorNoise or None, got {type(sensor_noise).__name__}")
-        if action_delay is not None and not isinstance(action_delay, ActionDelay):
-            raise L.AmenvError(f"action_delay: expected an ActionDelay or None, got {type(action_delay).__name__}")
-        if action_history is not None and not isinstance(action_history, ActionHistory):
-            raise L.AmenvError(f"action_history: expected an ActionHistory or None, got {type(action_history).__name__}")
+        switches = {"randomization": randomization, "rotor_lag": rotor_lag, "sensor_noise": sensor_noise, "action_delay": action_delay,
+                    "action_history": action_history}
+        for name, x in switches.items():   # before any device is touched
+            _typed(name, x, _SWITCHES[name][0])
         self.lib = L.load()
         self.device_index = _dev_index(device)
         self.device = torch.device("cuda", self.device_index)
@@ -96,21 +103,10 @@ class GpuWaypointEnv:
         self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
         self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
         self.n_rotors = int(cfg.vehicle.n_rotors)
-        self.randomization = None
-        if randomization is not None:
-            self.set_randomization(randomization)
-        self.rotor_lag = None
-        if rotor_lag is not None:
-            self.set_rotor_lag(rotor_lag)
-        self.sensor_noise = None
-        if sensor_noise is not None:
-            self.set_sensor_noise(sensor_noise)
-        self.action_delay = None
-        if action_delay is not None:
-            self.set_action_delay(action_delay)
-        self.action_history = None
-        if action_history is not None:
-            self.set_action_history(action_history)
+        for name, x in switches.items():
+            setattr(self, name, None)
+            if x is not None:
+                getattr(self, "set_" + name)(x)
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -119,6 +115,16 @@ class GpuWaypointEnv:
     def _check(self, rc, what):
         if rc != 0:
             raise L.AmenvError(f"{what} failed ({rc}): {self.lib.amenv_last_error(self._h).decode()}")
+
+    def _set_switch(self, name, x):
+        """set_<name>(x) of a struct-valued switch: the type check, amenv_set_<name> with x's C struct (NULL for None), the attribute, the
+        kernel's name."""
+        cls, to_c = _SWITCHES[name]
+        _typed("set_" + name, x, cls)
+        c = None if x is None else getattr(x, to_c)()
+        self._check(getattr(self.lib, "amenv_set_" + name)(self._h, None if c is None else C.byref(c)), "amenv_set_" + name)
+        setattr(self, name, x)
+        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
 
     def _actions(self, actions, lead=()):
         want = tuple(lead) + (self.num_envs, self.act_dim)
@@ -137,13 +143,7 @@ class GpuWaypointEnv:
         """Per-episode dynamics randomisation (a `DynamicsRandomization`, or None = the nominal vehicle; rigid vehicles with 4 or 6 rotors,
         not with kernel="team").  The factors are a pure function of (seed, env id, episode, ranges): new ranges apply from the next
         launch on, to the episodes already running too."""
-        from .randomization import DynamicsRandomization
-        if r is not None and not isinstance(r, DynamicsRandomization):
-            raise L.AmenvError(f"set_randomization: expected a DynamicsRandomization or None, got {type(r).__name__}")
-        c = None if r is None else r.to_c()
-        self._check(self.lib.amenv_set_randomization(self._h, None if c is None else C.byref(c)), "amenv_set_randomization")
-        self.randomization = r
-        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+        self._set_switch("randomization", r)
 
     def dynamics_factors(self):
         """[N, 2 + n_rotors] f32 on this env's device: km, kI, s_0.. of every env's current episode (all 1 without randomisation)."""
@@ -155,13 +155,7 @@ class GpuWaypointEnv:
         """First-order rotor lag (a `RotorLag`, or None = rotors deliver their command at once; rigid vehicles with 4 or 6 rotors, not
         with kernel="team").  Turning it on sets every env's rotor state to the nominal hover command; new time constants on an env where
         it is on keep the states and apply from the next launch.  A configuration call: it may allocate and synchronise."""
-        from .rotor_lag import RotorLag
-        if lag is not None and not isinstance(lag, RotorLag):
-            raise L.AmenvError(f"set_rotor_lag: expected a RotorLag or None, got {type(lag).__name__}")
-        c = None if lag is None else lag.to_c()
-        self._check(self.lib.amenv_set_rotor_lag(self._h, None if c is None else C.byref(c)), "amenv_set_rotor_lag")
-        self.rotor_lag = lag
-        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+        self._set_switch("rotor_lag", lag)
 
     def rotor_state(self):
         """[N, n_rotors] of the state dtype: every rotor's state w = sqrt(delivered thrust).  Needs the rotor lag on."""
@@ -181,13 +175,7 @@ class GpuWaypointEnv:
         """Sensor noise on every observation row (a `SensorNoise`, or None = exact observations; fp32 rigid vehicles with 4 or 6 rotors,
         not with kernel="team").  A pure function of (seed, env id, episode, step): nothing is stored, it applies from the next launch,
         and observe() repeats the row the last step returned.  Reward, termination, get_state() and stats() stay exact."""
-        from .sensor_noise import SensorNoise
-        if noise is not None and not isinstance(noise, SensorNoise):
-            raise L.AmenvError(f"set_sensor_noise: expected a SensorNoise or None, got {type(noise).__name__}")
-        c = None if noise is None else noise.to_c()
-        self._check(self.lib.amenv_set_sensor_noise(self._h, None if c is None else C.byref(c)), "amenv_set_sensor_noise")
-        self.sensor_noise = noise
-        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+        self._set_switch("sensor_noise", noise)
 
     def sensor_noise_samples(self):
         """[N, 12] f32 on this env's device: the unit samples of every env's current (episode, step) -- position 0..2, velocity 3..5,
@@ -201,13 +189,7 @@ class GpuWaypointEnv:
         vehicles with 4 or 6 rotors, not with kernel="team").  Turning it on draws every env's delay for its current episode and fills its
         history with hover rows; a new range on an env where it is on keeps both and applies to the episodes that start afterwards.  A
         configuration call: it may allocate and synchronise."""
-        from .action_delay import ActionDelay
-        if delay is not None and not isinstance(delay, ActionDelay):
-            raise L.AmenvError(f"set_action_delay: expected an ActionDelay or None, got {type(delay).__name__}")
-        c = None if delay is None else delay._as_c()
-        self._check(self.lib.amenv_set_action_delay(self._h, None if c is None else C.byref(c)), "amenv_set_action_delay")
-        self.action_delay = delay
-        self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+        self._set_switch("action_delay", delay)
 
     def set_action_history(self, history):
         """Action history in the observation rows (an `ActionHistory`, or None = the task's rows; fp32 rigid vehicles with 4 or 6 rotors, not
@@ -215,9 +197,7 @@ class GpuWaypointEnv:
         was given, most recent first (hover rows where the episode is younger): `obs_dim` = 20 (17 on the v1 tasks) + 4 rows.  `obs` and
         `terminal_obs` are re-allocated at the new width (zeros: `observe()` returns the current rows).  A configuration call: it may
         allocate and synchronise."""
-        from .action_history import ActionHistory
-        if history is not None and not isinstance(history, ActionHistory):
-            raise L.AmenvError(f"set_action_history: expected an ActionHistory or None, got {type(history).__name__}")
+        _typed("set_action_history", history, ActionHistory)
         self._check(self.lib.amenv_set_action_history(self._h, 0 if history is None else history.rows), "amenv_set_action_history")
         self.action_history = history
         self.obs_dim = int(self.lib.amenv_obs_dim(self._h))
