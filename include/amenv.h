@@ -50,7 +50,12 @@ extern "C" {
 
 /* amenv_config.flags */
 #define AMENV_FLAG_AUTO_RESET 1u /* SB3 VecEnv semantics: done envs are reset inside step()      */
-#define AMENV_FLAG_NAN_GUARD 2u  /* non-finite state => terminated|NONFINITE (documented deviation) */
+/* AMENV_FLAG_NAN_GUARD (documented deviation): a step ends the episode with TERMINATED | NONFINITE (and TRUNCATED when the time limit was
+ * reached), reward exactly -100, ep_return += -100, step += 1, when (a) any of the 13 + 2 n_joints state entries is non-finite after the
+ * dynamics, or (b) any entry of the action row the step applies is non-finite (with an action delay: the delayed row that is applied, on
+ * the step that applies it).  The terminal observation row of such an env is unspecified, and so is its float state when it is not reset.
+ * Without the flag nothing is tested: a non-finite action entry is clamped to a rotor limit, which one is unspecified. */
+#define AMENV_FLAG_NAN_GUARD 2u
 
 /* amenv_config.step_kernel: which implementation of the SAME step amenv_step() launches.  All of them meet the parity
  * gate; LANE and HELPER are bit-identical to each other.  AUTO picks by batch size (latency regime vs throughput regime). */

@@ -488,6 +488,15 @@ static void quat_to_rpy(const double* q, double* rpy) {
 
 static double norm3(const double* a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 
+/* AMENV_FLAG_NAN_GUARD, case (b): is any entry of the action row the step applies non-finite?  The rotor clamp swallows such an entry
+ * (fmax(fmin(NaN, hi), lo) is a rotor limit, and which one depends on the build), and the joint servo's acceleration limit swallows an
+ * infinite joint command, so that the state after the dynamics can be finite. */
+static int nonfinite_action(const amenv_config* cfg, const float* action) {
+  int bad = 0;
+  for (int k = 0; k < act_dim(cfg); k++) bad |= !isfinite(action[k]);
+  return bad;
+}
+
 /* One WaypointQuadEnv.step, rl_env_scaledObs.py:123-196 (+ _calculate_reward :198-231).
  * Returns info bits; *reward_out the f64 reward.  No auto-reset here. */
 static uint32_t env_step_v2(const amenv_config* cfg, env_t* e, const float* action, double* reward_out) {
@@ -497,7 +506,8 @@ static uint32_t env_step_v2(const amenv_config* cfg, env_t* e, const float* acti
 
   uint32_t bits = 0;
   if (cfg->flags & AMENV_FLAG_NAN_GUARD) {   /* deviation from the reference, documented in DESIGN.md */
-    int bad = 0; for (int k = 0; k < 13 + 2 * cfg->vehicle.n_joints; k++) bad |= !isfinite(e->s[k]);
+    int bad = nonfinite_action(cfg, action);                               /* (b) the action row the step applied */
+    for (int k = 0; k < 13 + 2 * cfg->vehicle.n_joints; k++) bad |= !isfinite(e->s[k]);   /* (a) the state after the dynamics */
     if (bad) {
       bits = AMENV_INFO_TERMINATED | AMENV_INFO_NONFINITE;
       if (e->step >= cfg->task.max_episode_steps) bits |= AMENV_INFO_TRUNCATED;
@@ -587,7 +597,8 @@ static uint32_t env_step_v1(const amenv_config* cfg, env_t* e, const float* acti
   orc_dynamics_step(cfg, e->s, action, NULL);                              /* :87-90 */
   uint32_t bits = 0;
   if (cfg->flags & AMENV_FLAG_NAN_GUARD) {
-    int bad = 0; for (int k = 0; k < 13; k++) bad |= !isfinite(e->s[k]);
+    int bad = nonfinite_action(cfg, action);
+    for (int k = 0; k < 13; k++) bad |= !isfinite(e->s[k]);
     if (bad) {
       bits = AMENV_INFO_TERMINATED | AMENV_INFO_NONFINITE;
       if (e->step >= cfg->task.max_episode_steps) bits |= AMENV_INFO_TRUNCATED;

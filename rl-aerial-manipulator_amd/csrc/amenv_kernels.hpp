@@ -347,7 +347,13 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
   if constexpr (EE) update_tool_offset<T, KW, ROLE == ARM_ROLE_MAIN || ROLE == ARM_ROLE_HELPER || ROLE == ARM_ROLE_STAGED>(AA.p, e);
   const bool ee_task = EE && P.ee_task != 0;
   uint32_t bits;
-  if constexpr (VAR == VAR_V1) { bits = task_step_v1<T, KW>(P, e, reward); } else { bits = task_step<T, KW, EE>(P, e, reward); }
+  const auto act_nf = [&]() {   // of the applied row (the DELAY forms hand the delayed one in); runs inside the guard's branch
+    float m = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kActDim + NJ; j++) m += nonfinite_mark(act[j]);
+    return T(m);
+  };
+  if constexpr (VAR == VAR_V1) { bits = task_step_v1<T, KW>(P, e, reward, act_nf); } else { bits = task_step<T, KW, EE>(P, e, reward, act_nf); }
   e.ep_return += reward;
   // two-wave kernel: the helper wave computes and publishes the observation of every lane; this (main) wave forms one only in the
   // cold path below (terminal observation / post-reset observation of the lanes whose episode ended)
@@ -971,8 +977,7 @@ __global__ __launch_bounds__(320) void step_kernel_armk(void* __restrict__ blob,
   load_env<T, KW, 0>(1, tile, lane, e);    // the joints arrive integrated from wave 3
   float act[AD];
 #pragma unroll
-  for (int j = 0; j < 4; j++) act[j] = ap[j];
-  act[4] = act[5] = act[6] = 0.0f;
+  for (int j = 0; j < AD; j++) act[j] = ap[j];   // (the stage waves apply the joint commands; here the NaN guard alone reads them)
   const StagedXchg<T> x{agg, jn, words, lane};
   T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
   uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, ARM_ROLE_STAGED, StagedXchg<T>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,

@@ -103,6 +103,12 @@ __device__ __forceinline__ float abs_(float a) { return fabsf(a); }
 __device__ __forceinline__ double abs_(double a) { return fabs(a); }
 __device__ __forceinline__ bool finite_(float a) { return __builtin_isfinite(a); }
 __device__ __forceinline__ bool finite_(double a) { return __builtin_isfinite(a); }
+// AMENV_FLAG_NAN_GUARD, case (b): +0 for a finite action entry, NaN for a NaN or an infinite one (no overflow, whatever its size).  The
+// marks of a row are summed and the sum joins the state sum the guard tests: the rotor clamp and the joint servo's acceleration limit
+// swallow a non-finite entry, so the state after the dynamics need not show it.
+__device__ __forceinline__ float nonfinite_mark(float a) { return a * 0.0f; }
+__device__ __forceinline__ double nonfinite_mark(double a) { return a * 0.0; }
+template <typename T> struct NoActionMark { __device__ __forceinline__ T operator()() const { return T(0); } };
 
 // ---- per-env registers ------------------------------------------------------------------------
 template <typename T, int KW>
@@ -418,8 +424,10 @@ __device__ __forceinline__ void observe(int K, const Env<T, KW>& e, float* o, bo
 
 // One WaypointQuadEnv.step (rl_env_scaledObs.py:123-196) after the dynamics update.
 // Returns info bits; reward in `reward`.  Mutates the episode registers.
-template <typename T, int KW, bool EE = false, typename PT>
-__device__ __forceinline__ uint32_t task_step(const PT& P, Env<T, KW>& e, T& reward) {
+// act_nf(): the summed nonfinite_mark of the action row the step applied; called inside the guard's branch only, so that a handle without
+// AMENV_FLAG_NAN_GUARD runs none of it.
+template <typename T, int KW, bool EE = false, typename PT, typename AF = NoActionMark<T>>
+__device__ __forceinline__ uint32_t task_step(const PT& P, Env<T, KW>& e, T& reward, const AF& act_nf = AF{}) {
   const int K = KW == 1 ? 1 : P.K;
   uint32_t bits = 0;
   int idx = e.flags & 15;
@@ -429,8 +437,10 @@ __device__ __forceinline__ uint32_t task_step(const PT& P, Env<T, KW>& e, T& rew
   e.step += 1;                                                          // :145
   if (truncated) bits |= AMENV_INFO_TRUNCATED;
 
+  // (the oracle tests the joint angles and rates too; they are not summed here: a non-finite one reaches the base rows within the step it
+  // is integrated in -- tests/test_gpu_flag_sweep.py puts NaN, +Inf and -Inf into each of them on every arm kernel)
   if (P.flags & AMENV_FLAG_NAN_GUARD) {                                 // deviation, see DESIGN.md
-    const T sum = e.px + e.py + e.pz + e.vx + e.vy + e.vz + e.qw + e.qx + e.qy + e.qz + e.wx + e.wy + e.wz;
+    const T sum = e.px + e.py + e.pz + e.vx + e.vy + e.vz + e.qw + e.qx + e.qy + e.qz + e.wx + e.wy + e.wz + act_nf();
     if (!finite_(sum)) { reward = T(-100); return bits | AMENV_INFO_TERMINATED | AMENV_INFO_NONFINITE; }
   }
   T cx, cy, cz;
@@ -524,13 +534,13 @@ __device__ __forceinline__ void observe_v1(bool raw, const Env<T, KW>& e, float*
 }
 
 // One v1 step after the dynamics update: v1/rl_env_scaledObs.py:93-140 (+ _calculate_reward :142-168).
-template <typename T, int KW, typename PT>
-__device__ __forceinline__ uint32_t task_step_v1(const PT& P, Env<T, KW>& e, T& reward) {
+template <typename T, int KW, typename PT, typename AF = NoActionMark<T>>
+__device__ __forceinline__ uint32_t task_step_v1(const PT& P, Env<T, KW>& e, T& reward, const AF& act_nf = AF{}) {
   uint32_t bits = 0;
   int idx = e.flags & 15;
   const int K = (e.flags >> 4) & 15;
   if (P.flags & AMENV_FLAG_NAN_GUARD) {
-    const T sum = e.px + e.py + e.pz + e.vx + e.vy + e.vz + e.qw + e.qx + e.qy + e.qz + e.wx + e.wy + e.wz;
+    const T sum = e.px + e.py + e.pz + e.vx + e.vy + e.vz + e.qw + e.qx + e.qy + e.qz + e.wx + e.wy + e.wz + act_nf();
     if (!finite_(sum)) {
       if (e.step >= P.max_steps) bits |= AMENV_INFO_TRUNCATED;
       e.step += 1; reward = T(-100);

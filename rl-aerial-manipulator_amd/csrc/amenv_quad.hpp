@@ -144,7 +144,7 @@ __device__ __forceinline__ QuadOut quad_advance(const QuadParams& P, const QuadL
   e.final_yaw = E.final_yaw; e.last_distance = E.last_distance; e.ep_return = E.ep_return;
   e.step = E.step; e.counter = E.counter; e.flags = E.flags; e.episode = E.episode;
   QuadOut o;
-  o.bits = task_step<float, 1, false>(P, e, o.reward);
+  o.bits = task_step<float, 1, false>(P, e, o.reward, [&]() { return sum4(nonfinite_mark(act)); });   // (the quad's four lanes hold the action row)
   e.ep_return += o.reward;
   o.ended = (o.bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
   o.ep_len = e.step; o.ep_ret = e.ep_return;

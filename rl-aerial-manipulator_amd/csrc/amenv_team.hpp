@@ -270,7 +270,7 @@ __device__ __forceinline__ TeamOutT<X> team_advance(const TeamParamsT<X>& P, con
   e.final_yaw = E.final_yaw; e.last_distance = E.last_distance; e.ep_return = E.ep_return;
   e.step = E.step; e.counter = E.counter; e.flags = E.flags; e.episode = E.episode;
   TeamOutT<X> o;
-  o.bits = task_step<X, 1, true>(P, e, o.reward);
+  o.bits = task_step<X, 1, true>(P, e, o.reward, [&]() { return sum4(nonfinite_mark(act) + nonfinite_mark(actj)); });   // (every quad of the row holds the whole action row)
   e.ep_return += o.reward;
   E.last_distance = e.last_distance; E.ep_return = e.ep_return;
   E.step = e.step; E.counter = e.counter; E.flags = e.flags;

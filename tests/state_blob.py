@@ -12,7 +12,14 @@ Gates of `compare` (the ones tests/test_gpu_parity.py applies to the quadrotor):
   observation rows, terminal rows            fp32: 1e-5 of max(1, |x|)   fp64: 1.3e-7 (one fp32 ulp: the rows are fp32)
   ep_return relative to max(1, |x|)          5e-5;  ep_len equal;  INFO_WAS_RESET exactly on the envs that ended
 An env whose flag bits or reward differ is a threshold flip: allowed on fp32 only, only where the oracle's own margin to the matching
-threshold is below FLIP_MARGIN, and at most flip_cap(n) per step."""
+threshold is below FLIP_MARGIN, and at most flip_cap(n) per step.
+
+The flag word (tests/test_gpu_flag_sweep.py).  `compare` takes the handle's flags: without AMENV_FLAG_AUTO_RESET an env that ended is not
+reset and is gated like one that goes on.  With AMENV_FLAG_NAN_GUARD, `poison` puts NaN, +Inf and -Inf into every guarded state row and every
+action column, one env each; an env the oracle or the kernels flag NONFINITE is never an excusable flip: flag bits, done, the int fields,
+ep_len equal, reward exactly -100, ep_return within RET_REL where the oracle's is finite, reset state bit-equal and post-reset row within
+the row gate when it was reset.  Its terminal row, its row and its float state when it was not reset are unspecified (include/amenv.h) and
+skipped."""
 import ctypes as C
 
 import numpy as np
@@ -49,8 +56,71 @@ def class_names(cfg):
     return CLASSES if cfg.task.num_waypoints == 1 else CLASSES_MULTI
 
 
+# the guard's own classes (tests/test_state_blob_cpu.py reaches each on the oracle alone); v1 has no hold phase
+CLASSES_NONFINITE = ("nonfinite_state", "nonfinite_action", "nonfinite_at_time_limit", "nonfinite_while_holding", "nonfinite_that_would_have_reached")
+POISON_VALUES = (np.nan, np.inf, -np.inf)
+POISON_SHARE = 0.25          # poisoned envs are at most this share of the batch: the branch classes live on the others
+EDGE_ENVS = (0, 15, 16, 63, 64, -1)   # workgroup, wave and tile edges of the 16-, 64- and 256-lane forms, and the ragged tail
+
+
+def nonfinite_class_names(cfg):
+    return tuple(k for k in CLASSES_NONFINITE if not (is_v1(cfg) and k == "nonfinite_while_holding"))
+
+
 def flip_cap(n):
     return max(1, n // 500)
+
+
+def guarded_rows(cfg):
+    """The float-state rows AMENV_FLAG_NAN_GUARD tests: the 13 base entries, joint angles and joint rates."""
+    j0 = O.F_WP0 + 3 * cfg.task.num_waypoints
+    return list(range(13)) + list(range(j0, j0 + 2 * cfg.vehicle.n_joints))
+
+
+def poison(cfg, fstate, acts, rng, must=(), avoid=None):
+    """(fstate, acts, masks): copies with NaN, +Inf and -Inf in every guarded state row and every action column, one env per (row, value)
+    and per (column, value).  The state-poisoned envs include EDGE_ENVS and `must` (envs the caller wants flagged: at the time limit,
+    holding, about to reach); the others are drawn from the envs outside `avoid` (bool [n]: envs a branch class needs).  masks: "state" /
+    "action" bool [n], "clean" = neither; "state_env" / "action_env" the envs in (row, value) / (column, value) order."""
+    n = fstate.shape[1]
+    rows, cols = guarded_rows(cfg), range(acts.shape[1])
+    ns, na = len(rows) * len(POISON_VALUES), len(cols) * len(POISON_VALUES)
+    assert ns + na <= POISON_SHARE * n, f"{ns + na} poisoned envs of {n}: more than {POISON_SHARE:.0%} (raise n)"
+    fixed = list(dict.fromkeys([e % n for e in EDGE_ENVS] + [int(e) for e in must]))
+    free = np.ones(n, bool) if avoid is None else ~np.asarray(avoid)
+    free[fixed] = False
+    drawn = rng.choice(np.nonzero(free)[0], ns + na - len(fixed), replace=False)
+    state_env = np.array(fixed + list(drawn[:ns - len(fixed)])); action_env = drawn[ns - len(fixed):]
+    state_env = state_env[rng.permutation(ns)]                # which (row, value) an edge env gets is drawn too
+    f = fstate.copy()
+    k = 0
+    for r in rows:
+        for v in POISON_VALUES:
+            f[r, state_env[k]] = v; k += 1
+    ms, ma = np.zeros(n, bool), np.zeros(n, bool)
+    ms[state_env] = True; ma[action_env] = True
+    masks = dict(state=ms, action=ma, clean=~(ms | ma), state_env=state_env, action_env=action_env)
+    return f, poison_actions(acts, masks), masks
+
+
+def poison_actions(acts, masks):
+    """A copy of acts with the action poison of `poison` put in: the same (column, value) on the same envs, on another step's rows."""
+    a = acts.copy()
+    k = 0
+    for c in range(acts.shape[1]):
+        for v in POISON_VALUES:
+            a[masks["action_env"][k], c] = v; k += 1
+    return a
+
+
+def nonfinite_classes(cfg, pre, acts, info, clean_distance):
+    """{class: bool [n]} of the guard's own branches in one step: info the step's flag bits, acts the rows it applied, clean_distance the
+    distance the same step of the unpoisoned twin measured (NaN where there is none)."""
+    nf = (np.asarray(info).view(np.uint32) & O.INFO_NONFINITE) != 0
+    bad_a = ~np.isfinite(acts).all(axis=1)
+    c = dict(nonfinite_state=nf & ~bad_a, nonfinite_action=nf & bad_a, nonfinite_at_time_limit=nf & ((info & O.INFO_TRUNCATED) != 0),
+             nonfinite_while_holding=nf & ((pre[1][O.I_FLAGS] & O.FLAGBIT_FWR) != 0), nonfinite_that_would_have_reached=nf & (clean_distance < 0.1))
+    return {k: c[k] for k in nonfinite_class_names(cfg)}
 
 
 def _cfg_for(cfg, n, flags=None):
@@ -378,19 +448,27 @@ def _worst(x):
     return float(x.max()) if x.size else 0.0
 
 
-def compare(g, o, m, dtype):
+def compare(g, o, m, dtype, flags=O.FLAG_AUTO_RESET):
     """Assert that one step of the kernels (g) is the oracle's (o: oracle_step's first result) within the gates at the top of this file,
-    m = margins(...) of that step.  Both hold obs, reward, done, info, terminal_obs, ep_return, ep_len of the step and the state after it
-    under "fstate" / "istate"; rows of terminal_obs / ep_return / ep_len must have been NaN / NaN / -1 before the step (the oracle binding
-    does that itself).  Returns the flip count, the flipped envs and the worst error of every gated quantity."""
+    m = margins(...) of that step, flags the handle's flag word.  Both hold obs, reward, done, info, terminal_obs, ep_return, ep_len of the
+    step and the state after it under "fstate" / "istate"; rows of terminal_obs / ep_return / ep_len must have been NaN / NaN / -1 before
+    the step (the oracle binding does that itself).  Returns the flip count, the flipped envs and the worst error of every gated quantity."""
     f32 = dtype == "f32"
+    auto = (flags & O.FLAG_AUTO_RESET) != 0
     n = len(o["done"])
     gi, oi = np.asarray(g["info"]).view(np.uint32), np.asarray(o["info"]).view(np.uint32)
     gr, orw = np.asarray(g["reward"], np.float64), np.asarray(o["reward"], np.float64)
     gf, of = np.asarray(g["fstate"], np.float64), np.asarray(o["fstate"], np.float64)
-    e_rew = np.abs(gr - orw) / np.maximum(1.0, np.abs(orw))
-    flip_info = (gi & 127) != (oi & 127)
-    flip_rew = ~flip_info & ~(e_rew < (REW32 if f32 else REW64))
+    # ---- NONFINITE envs (either side says so): never a flip; every flag bit equal, reward exactly -100
+    nf = ((gi | oi) & O.INFO_NONFINITE) != 0
+    assert (flags & O.FLAG_NAN_GUARD) or not nf.any(), ("NONFINITE without the guard", np.nonzero(nf)[0][:8])
+    bad = nf & (gi != oi)
+    assert not bad.any(), ("flag bits of NONFINITE envs", np.nonzero(bad)[0][:8], gi[bad][:8], oi[bad][:8])
+    assert (gr[nf] == -100.0).all() and (orw[nf] == -100.0).all(), ("reward of NONFINITE envs", gr[nf][:8])
+    with np.errstate(invalid="ignore"):
+        e_rew = np.abs(gr - orw) / np.maximum(1.0, np.abs(orw))
+    flip_info = ~nf & ((gi & 127) != (oi & 127))
+    flip_rew = ~nf & ~flip_info & ~(e_rew < (REW32 if f32 else REW64))
     flips = flip_info | flip_rew
     for k in np.nonzero(flips)[0]:
         which = "info" if flip_info[k] else "reward"
@@ -402,25 +480,30 @@ def compare(g, o, m, dtype):
     assert np.array_equal(np.asarray(g["done"])[ok] != 0, done[ok]), "done"
     bad = ok & (np.asarray(g["istate"]) != np.asarray(o["istate"])).any(axis=0)
     assert not bad.any(), ("int fields", np.nonzero(bad)[0][:8], np.asarray(g["istate"])[:, bad][:, :8], np.asarray(o["istate"])[:, bad][:, :8])
-    on, ended = ok & ~done, ok & done
+    # envs whose state the step leaves (all that were not reset; a NONFINITE env's float state is unspecified), envs that were reset, envs that ended
+    on, reset, ended = ok & ~(done & auto) & ~nf, ok & done & auto, ok & done
     e_state = np.abs(gf - of)[:, on] if not f32 else rel_err(gf, of)[:, on]
-    assert _worst(e_state) < (REL32 if f32 else ABS64), ("state of envs that go on: worst per row", e_state.max(axis=1))
-    assert np.array_equal(gf[:, ended], of[:, ended]), "reset states are bit-equal"
+    assert _worst(e_state) < (REL32 if f32 else ABS64) and not np.isnan(e_state).any(), ("state of envs that go on: worst per row", e_state.max(axis=1))
+    assert np.array_equal(gf[:, reset], of[:, reset]), "reset states are bit-equal"
     go, oo = np.asarray(g["obs"], np.float64), np.asarray(o["obs"], np.float64)
     obs_err = (lambda a, b: rel_err(a, b)) if f32 else (lambda a, b: np.abs(a - b))
     obs_gate = REL32 if f32 else OBS64
-    e_obs = obs_err(go[ok], oo[ok])
-    assert _worst(e_obs) < obs_gate, ("observation rows", _worst(e_obs))
+    rows = ok & ~(nf & (not auto))                                    # (a NONFINITE env that is not reset: the row is its terminal row)
+    e_obs = obs_err(go[rows], oo[rows])
+    assert _worst(e_obs) < obs_gate and not np.isnan(e_obs).any(), ("observation rows", _worst(e_obs))
     # ---- envs that ended, and the rows of those that did not
     was_reset = (gi & O.INFO_WAS_RESET) != 0
-    assert np.array_equal(was_reset[ok], (oi[ok] & O.INFO_WAS_RESET) != 0), "INFO_WAS_RESET"
+    assert np.array_equal(was_reset[ok], (oi[ok] & O.INFO_WAS_RESET) != 0) and np.array_equal(was_reset[ok], reset[ok]), "INFO_WAS_RESET"
     assert np.array_equal(np.asarray(g["ep_len"])[ended], np.asarray(o["ep_len"])[ended]), "ep_len"
-    e_ret = rel_err(np.asarray(g["ep_return"])[ended], np.asarray(o["ep_return"])[ended])
-    assert _worst(e_ret) < RET_REL, ("ep_return", _worst(e_ret))
-    e_tobs = obs_err(np.asarray(g["terminal_obs"], np.float64)[ended], np.asarray(o["terminal_obs"], np.float64)[ended])
+    ret = ended & np.isfinite(np.asarray(o["ep_return"], np.float64))        # (a non-finite running return with finite state: out of scope)
+    assert not (ended & ~ret & ~nf).any(), "the oracle's ep_return of a finite env is not finite"
+    e_ret = rel_err(np.asarray(g["ep_return"])[ret], np.asarray(o["ep_return"])[ret])
+    assert _worst(e_ret) < RET_REL and not np.isnan(e_ret).any(), ("ep_return", _worst(e_ret))
+    trows = ended & ~nf
+    e_tobs = obs_err(np.asarray(g["terminal_obs"], np.float64)[trows], np.asarray(o["terminal_obs"], np.float64)[trows])
     assert _worst(e_tobs) < obs_gate and not np.isnan(e_tobs).any(), ("terminal rows", _worst(e_tobs))
     kept = np.asarray(g["done"]) == 0
     assert np.isnan(np.asarray(g["terminal_obs"])[kept]).all() and np.isnan(np.asarray(g["ep_return"])[kept]).all() and (np.asarray(g["ep_len"])[kept] == -1).all(), \
         "rows of envs that did not end were written"
-    return dict(flips=int(flips.sum()), flipped=np.nonzero(flips)[0], ended=int(ended.sum()), state=_worst(e_state), reward=_worst(e_rew[ok]), obs=_worst(e_obs),
-                ep_return=_worst(e_ret), terminal_obs=_worst(e_tobs))
+    return dict(flips=int(flips.sum()), flipped=np.nonzero(flips)[0], ended=int(ended.sum()), nonfinite=int(nf.sum()), state=_worst(e_state), reward=_worst(e_rew[ok & ~nf]),
+                obs=_worst(e_obs), ep_return=_worst(e_ret), terminal_obs=_worst(e_tobs))

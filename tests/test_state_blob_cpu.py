@@ -292,3 +292,184 @@ def test_compare_rejects_one_changed_field_of_a_v1_step(field):
     for dtype in ("f32", "f64"):
         with pytest.raises(AssertionError):
             B.compare(g, o, m, dtype)
+
+
+# ---- the flag word: NaN guard and auto-reset off (tests/test_gpu_flag_sweep.py) ----------------------------------------------------------------
+POISON_SEED = 14
+GUARD_AUTO, GUARD, PLAIN = O.FLAG_NAN_GUARD | O.FLAG_AUTO_RESET, O.FLAG_NAN_GUARD, 0
+FLAG_WORDS = {"guard_auto": GUARD_AUTO, "guard": GUARD, "plain": PLAIN}
+ACTION_POISON_STEPS = (0, 3)
+
+
+def flag_n(vehicle, n):
+    """The batch size of a flag-sweep case: the 3-joint arm poisons 78 envs (57 state, 21 action), a quarter of 312, so it runs at 600."""
+    return max(n, 600) if vehicle in ("hexa_arm", "hexa_arm_base") else n
+
+
+# every (vehicle, n, dtype, task) the flag sweep starts from: the states of both branch sweeps at flag_n
+FLAG_STATES = sorted({(v, flag_n(v, n), d, "v2") for v, n, d in STATES} | {(v, flag_n(v, n), d, t) for v, n, d, t in TASK_STATES})
+
+
+@functools.lru_cache(maxsize=None)
+def poisoned_start(vehicle, n, dtype, task="v2"):
+    """(cfg, fstate, istate, masks): start_state with B.poison's state poison in it.  Envs the branch classes need (the first three of every
+    class in the clean oracle run) are left alone; one env at the time limit, one in the hold phase and one about to reach its waypoint in
+    the first step are among the poisoned ones.  Shared: do not write to it."""
+    cfg, fs, is_ = start_state(vehicle, n, dtype, task)
+    _, run = oracle_run(vehicle, n, dtype, task)
+    avoid = np.zeros(n, bool)
+    for name in B.class_names(cfg):
+        hits = np.concatenate([np.nonzero(B.classes(cfg, pre, post, o)[name])[0] for pre, _, o, post in run])
+        avoid[list(dict.fromkeys(hits.tolist()))[:3]] = True
+    pre, _, o, post = run[0]
+    d, _, _, fwr, _ = B._geometry(cfg, pre, post)
+    late = pre[1][O.I_STEP] >= cfg.task.max_episode_steps
+    wanted = [late & ~avoid, (d < 0.1) & ~fwr & ~late & ~avoid] + ([] if B.is_v1(cfg) else [fwr & (d < 0.1) & ~late & ~avoid])
+    must = [int(np.nonzero(w)[0][-1]) for w in wanted]
+    f, _, masks = B.poison(cfg, fs, np.zeros((n, 4 + cfg.vehicle.n_joints), np.float32), np.random.RandomState(POISON_SEED), must=must, avoid=avoid)
+    f.setflags(write=False)
+    return cfg, f, is_, masks
+
+
+def flag_actions(cfg, pre, rng, t, masks):
+    """Step t's actions of a flag-sweep case: B.actions, with the action poison on ACTION_POISON_STEPS when the blob is the poisoned one."""
+    a = B.actions(cfg, pre[0], rng)
+    return B.poison_actions(a, masks) if masks is not None and t in ACTION_POISON_STEPS else a
+
+
+@functools.lru_cache(maxsize=None)
+def flag_run(vehicle, n, dtype, task, flags):
+    """STEPS steps of the oracle alone as the flag sweep runs them: with the guard from the poisoned blob, else from the clean one; beside
+    it the clean twin (guard off, clean blob, same auto-reset).  Per step (pre, actions, o, post, clean_distance, twin's o)."""
+    guard = (flags & O.FLAG_NAN_GUARD) != 0
+    cfg, fs, is_, masks = poisoned_start(vehicle, n, dtype, task) if guard else start_state(vehicle, n, dtype, task) + (None,)
+    cfg = B._cfg_for(cfg, n, flags)
+    tcfg = B._cfg_for(cfg, n, flags & ~O.FLAG_NAN_GUARD)
+    rngs = [(np.random.RandomState(ACTION_SEED), np.random.RandomState(RESEAT_SEED)) for _ in range(2)]
+    pre, tpre, run = (fs, is_), start_state(vehicle, n, dtype, task)[1:], []
+    for t in range(STEPS):
+        a, ta = flag_actions(cfg, pre, rngs[0][0], t, masks), flag_actions(tcfg, tpre, rngs[1][0], t, None)
+        (o, post), (to, tpost) = B.oracle_step(cfg, pre, a), B.oracle_step(tcfg, tpre, ta)
+        run.append((pre, a, o, post, B._geometry(tcfg, tpre, tpost)[0], to))
+        nxt = []
+        for c, oo, (_, rl) in ((cfg, o, rngs[0]), (tcfg, to, rngs[1])):
+            with np.errstate(invalid="ignore"):
+                f = B.reseat_last_distance(c, oo["fstate"], rl, oo["istate"])
+            nxt.append((B.to_f32(f) if dtype == "f32" else f, oo["istate"]))
+        pre, tpre = nxt
+    return cfg, masks, run
+
+
+@pytest.mark.parametrize("word", list(FLAG_WORDS))
+@pytest.mark.parametrize("vehicle,n,dtype,task", FLAG_STATES)
+def test_flag_runs_reach_every_class_on_the_oracle(vehicle, n, dtype, task, word):
+    """What tests/test_gpu_flag_sweep.py relies on: the poison stays below a quarter of the batch and leaves every branch class reached on
+    the clean envs; every class of the guard is reached; the clean envs are, bit for bit, those of the clean twin; the flip cap is still a
+    condition; `compare` accepts each step against itself."""
+    flags = FLAG_WORDS[word]
+    cfg, masks, run = flag_run(vehicle, n, dtype, task, flags)
+    guard, auto = (flags & O.FLAG_NAN_GUARD) != 0, (flags & O.FLAG_AUTO_RESET) != 0
+    clean = masks["clean"] if guard else np.ones(n, bool)
+    names = [k for k in B.class_names(cfg) if auto or not k.startswith("reset_drew")]       # (what a reset drew: there is none without auto-reset)
+    seen, seen_nf = {k: 0 for k in names}, {k: 0 for k in B.nonfinite_class_names(cfg)}
+    if guard:
+        n_s, n_a = 3 * len(B.guarded_rows(cfg)), 3 * (4 + cfg.vehicle.n_joints)
+        assert int(masks["state"].sum()) == n_s and int(masks["action"].sum()) == n_a and n_s + n_a <= 0.25 * n
+        assert all(masks["state"][e] for e in (0, 15, 16, 63, 64, n - 1))
+    for t, (pre, a, o, post, clean_d, to) in enumerate(run):
+        with np.errstate(invalid="ignore"):
+            m = B.margins(cfg, pre, post)
+            cl = B.classes(cfg, pre, post, o)
+        n_el = int(B.eligible(m).sum())
+        assert n_el <= B.flip_cap(n), f"step {t}: {n_el} envs within {B.FLIP_MARGIN} of a threshold, the cap is {B.flip_cap(n)}"
+        for k in names:
+            seen[k] += int((cl[k] & clean).sum())
+        nf = (o["info"] & O.INFO_NONFINITE) != 0
+        assert not nf[clean].any()
+        for k in ("obs", "reward", "done", "info"):                      # isolation, on the oracle: a clean env does not see the poison
+            assert np.array_equal(np.asarray(o[k])[clean], np.asarray(to[k])[clean]), (t, k)
+        assert np.array_equal(o["fstate"][:, clean], to["fstate"][:, clean]) and np.array_equal(o["istate"][:, clean], to["istate"][:, clean]), t
+        if guard:
+            for k, v in B.nonfinite_classes(cfg, pre, a, o["info"], clean_d).items():
+                seen_nf[k] += int(v.sum())
+            if t == 0 or not auto:
+                assert nf[masks["state"]].all(), (t, "state poison not flagged", np.nonzero(masks["state"] & ~nf)[0])
+            # action poison: flagged on its steps; between them only an env whose state it reached (a NaN joint command, never reset)
+            stale = ~np.isfinite(pre[0][B.guarded_rows(cfg)]).all(axis=0)
+            assert not (auto and stale[masks["action"]].any())
+            assert np.array_equal(nf[masks["action"]], np.ones(int(masks["action"].sum()), bool) if t in ACTION_POISON_STEPS else stale[masks["action"]]), t
+            assert (o["reward"][nf] == -100.0).all() and ((o["info"][nf] & O.INFO_TERMINATED) != 0).all() and (o["done"][nf] == 1).all()
+        with np.errstate(invalid="ignore"):
+            r = B.compare(copy.deepcopy(o), o, m, dtype, flags)
+        assert r["flips"] == 0 and r["nonfinite"] == int(nf.sum())
+    print(vehicle, task, n, dtype, word, seen, seen_nf)
+    assert all(v >= 1 for v in seen.values()), seen
+    assert not guard or all(v >= 1 for v in seen_nf.values()), seen_nf
+
+
+@pytest.mark.parametrize("vehicle,n,dtype,task", [s for s in FLAG_STATES if s[2] == "f32" and s[1] < 4096])
+def test_guard_on_is_bit_equal_to_guard_off_on_the_clean_blob(vehicle, n, dtype, task):
+    cfg, fs, is_ = start_state(vehicle, n, dtype, task)
+    a = B.actions(cfg, fs, np.random.RandomState(ACTION_SEED))
+    for auto in (O.FLAG_AUTO_RESET, 0):
+        on, _ = B.oracle_step(B._cfg_for(cfg, n, auto | O.FLAG_NAN_GUARD), (fs, is_), a)
+        off, _ = B.oracle_step(B._cfg_for(cfg, n, auto), (fs, is_), a)
+        for k in on:
+            assert np.array_equal(np.asarray(on[k]), np.asarray(off[k]), equal_nan=True), k
+
+
+def _guard_step():
+    cfg, masks, run = flag_run("quad", 300, "f32", "v2", GUARD_AUTO)
+    pre, a, o, post, _, _ = run[0]
+    with np.errstate(invalid="ignore"):
+        return o, B.margins(cfg, pre, post), masks
+
+
+@pytest.mark.parametrize("field", ["flag bits", "reward", "int field", "ep_len", "ep_return", "reset state", "post-reset row", "missed", "invented"])
+def test_compare_rejects_one_changed_field_of_a_nonfinite_env(field):
+    """A NONFINITE env is never an excusable flip, whatever the margins say, and is gated on everything but its terminal row."""
+    o, m, masks = _guard_step()
+    g = copy.deepcopy(o)
+    k = int(masks["state_env"][0])
+    assert o["info"][k] & O.INFO_NONFINITE
+    m = {q: np.full_like(v, 1e-9) for q, v in m.items()}              # every env "on a threshold"
+    if field == "flag bits":
+        g["info"][k] |= O.INFO_TRUNCATED
+    elif field == "reward":
+        g["reward"][k] = np.nextafter(-100.0, 0.0)
+    elif field == "int field":
+        g["istate"][O.I_EPISODE, k] += 1
+    elif field == "ep_len":
+        g["ep_len"][k] += 1
+    elif field == "ep_return":
+        g["ep_return"][k] += 1e-3 * max(1.0, abs(g["ep_return"][k]))
+    elif field == "reset state":
+        g["fstate"][0, k] += 1e-7
+    elif field == "post-reset row":
+        g["obs"][k, 2] += 1e-4
+    elif field == "missed":
+        g["info"][k] &= ~np.uint32(O.INFO_NONFINITE)
+    else:
+        j = _pick(masks["clean"] & (o["done"] == 0))
+        g["info"][j] |= O.INFO_NONFINITE | O.INFO_TERMINATED
+    with pytest.raises(AssertionError), np.errstate(invalid="ignore"):
+        B.compare(g, o, m, "f32", GUARD_AUTO)
+    g = copy.deepcopy(o)
+    g["terminal_obs"][k] = 7.0                                         # unspecified: not compared
+    with np.errstate(invalid="ignore"):
+        B.compare(g, o, m, "f32", GUARD_AUTO)
+
+
+def test_compare_gates_an_ended_env_that_is_not_reset_like_one_that_goes_on():
+    cfg, _, run = flag_run("quad", 300, "f32", "v2", PLAIN)
+    pre, a, o, post, _, _ = run[0]
+    m = B.margins(cfg, pre, post)
+    k = _pick((o["done"] != 0) & (m["reward"] > 1e-2))
+    assert not (o["info"][k] & O.INFO_WAS_RESET) and np.array_equal(o["fstate"][:13, k], post[0][:13, k])
+    B.compare(copy.deepcopy(o), o, m, "f32", PLAIN)
+    g = copy.deepcopy(o)
+    g["fstate"][3, k] += 1e-4 * max(1.0, abs(g["fstate"][3, k]))
+    with pytest.raises(AssertionError):
+        B.compare(g, o, m, "f32", PLAIN)
+    with pytest.raises(AssertionError):                                # ... and the flag word is part of the comparison
+        B.compare(copy.deepcopy(o), o, m, "f32", O.FLAG_AUTO_RESET)
