@@ -55,6 +55,10 @@ def main():
     ap.add_argument("--action-history", type=int, default=None, metavar="H",
                     help="append the last H (1 or 2) action rows each env was given to its observation rows: the commands still in flight under "
                          "--action-delay / --rotor-lag (fp32 rigid vehicles; not with --normalize-obs --fused-rollout; DESIGN 4n)")
+    ap.add_argument("--target-kl", type=float, default=None, metavar="X",
+                    help="SB3's target_kl: leave an update once a minibatch's approx_kl exceeds 1.5 X (decided on the GPU, no extra synchronisation; one rank only)")
+    ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear"],
+                    help="linear: learning_rate = 2e-4 * progress_remaining (SB3's linear schedule), evaluated once per iteration")
     ap.add_argument("--log-json", default=None, help="write the learning curve (one record per iteration) and the final evaluation to this file")
     ap.add_argument("--warm-start-pid", type=int, default=None, metavar="DAGGER_ROUNDS",
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
@@ -86,7 +90,8 @@ def main():
         env.set_action_history(amd.ActionHistory(a.action_history))
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
-    model = amd.PPO(env, learning_rate=2e-4, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
+    lr = 2e-4 if a.lr_schedule == "constant" else (lambda progress_remaining: 2e-4 * progress_remaining)
+    model = amd.PPO(env, learning_rate=lr, target_kl=a.target_kl, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
                     gae_lambda=0.9, clip_range=0.2, ent_coef=0.01 if v1 else (1e-4 if a.resume else 5e-4), dist=dist, fused_rollout=a.fused_rollout,
                     seed=a.seed, obs_normalizer=norm, reward_normalizer=amd.RewardNormalizer(env.num_envs, device=local) if a.norm_reward else None)
     if a.resume:
@@ -101,7 +106,7 @@ def main():
     curve = []
 
     def show(r):
-        curve.append({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()})
+        curve.append({k: (round(v, 8 if k in ("approx_kl", "learning_rate") else 4) if isinstance(v, float) else v) for k, v in r.items()})
         print(curve[-1], flush=True)
 
     import time
@@ -126,6 +131,7 @@ def main():
             with open(a.log_json, "w") as f:
                 json.dump({"command": " ".join(sys.argv), "learn_seconds": seconds, "timesteps": a.timesteps, "timesteps_to_90pct_success": first90,
                            "final_success_rate_mean_of_last_10_iterations": sum(c["success_rate"] for c in curve[-10:]) / max(1, len(curve[-10:])),
+                           "n_updates": model.n_updates, "iterations_stopped_early_by_target_kl": sum(c["kl_early_stop"] for c in curve),
                            "evaluate_policy_mean_reward": mean_reward, "evaluate_policy_std_reward": std_reward, "curve_every_20th_iteration": curve[::20]}, f, indent=1)
     if dist is not None:
         dist.destroy_process_group()

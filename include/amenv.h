@@ -620,6 +620,52 @@ int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_di
 int amenv_ppo_adam_step(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6,
                         float* grad_norm_out, uint32_t* ticket, void* stream);
 
+/* ---- PPO training controls: approx_kl and the on-device target_kl gate -----------------------------------------------
+ * SB3 2.6.0 PPO.train computes approx_kl = mean((r - 1) - log r), r = exp(logp - old_logp), per minibatch and, with target_kl set, leaves
+ * the update when approx_kl > 1.5 target_kl -- AFTER the loss of that minibatch, BEFORE its optimiser step.  A host-side check would cost
+ * one device-to-host synchronisation per minibatch; here the decision is taken and obeyed on the device.
+ *
+ * amenv_ppo_ctl lives in DEVICE memory, allocated by the caller (amenv_ppo_ctl_bytes() bytes, 4-byte aligned), written by the kernels
+ * only, read back by the caller once per update.  amenv_ppo_ctl_arm (one tiny launch, asynchronous on `stream`) sets struct_size and
+ * kl_limit and zeroes everything else; call it once per update, before the first minibatch.
+ *   - the kernel that finalises a minibatch's scalars (the last launch of amenv_ppo_loss_grad_ctl / amenv_ppo_mlp_step_ctl) adds 1 to
+ *     `evaluated`, the minibatch's approx_kl to `kl_sum`, its four scalars to sum[0..3], sets `kl_last`, and sets stop = 1 when
+ *     kl_limit > 0 and kl_last > kl_limit (callers pass kl_limit = 1.5 target_kl; <= 0: never stops);
+ *   - amenv_ppo_adam_step_ctl with `stop` set changes NOTHING (parameters, both moments, the step counter, grad_norm_out); otherwise the
+ *     workgroup that finishes last adds 1 to `applied` and the gradient norm to sum[4];
+ *   - every kernel of a later amenv_ppo_loss_grad_ctl / amenv_ppo_mlp_step_ctl call returns at entry while `stop` is set: gradients,
+ *     stats and this block keep the values of the minibatch that tripped the limit.
+ * With ctl = NULL the three _ctl entry points are the plain ones.  `stats` stays the four floats of the plain entry points with or
+ * without ctl: approx_kl of the minibatch is the block's kl_last (read it on the device, or copy the block back).
+ * Gradients, parameters and the first four scalars are bit-identical with and without ctl while the gate is open.  Deterministic: every
+ * field has one writing thread per launch, sums in fixed order.  One update at a time per block (launches ordered on one stream). */
+typedef struct amenv_ppo_ctl {
+  uint32_t struct_size; /* = sizeof(amenv_ppo_ctl) = amenv_ppo_ctl_bytes(): guard, written by amenv_ppo_ctl_arm */
+  float kl_limit;       /* <= 0: no limit */
+  uint32_t stop;        /* 1 once a minibatch's approx_kl exceeded kl_limit */
+  uint32_t stop_seen;   /* internal: `stop` as the fused kernel of the current minibatch step read it (what its reduction launch obeys) */
+  uint32_t evaluated;   /* minibatches whose loss was computed since the last arm */
+  uint32_t applied;     /* Adam steps applied since the last arm */
+  float kl_sum;         /* sum of approx_kl over the evaluated minibatches */
+  float kl_last;        /* approx_kl of the last evaluated minibatch */
+  float sum[5];         /* running sums: policy loss, value loss, entropy loss, clip fraction (evaluated minibatches), grad norm (applied steps) */
+  uint32_t reserved[3];
+} amenv_ppo_ctl;
+size_t amenv_ppo_ctl_bytes(void);
+/* AMENV_ERR_INVALID for ctl = NULL or a kl_limit that is NaN */
+int amenv_ppo_ctl_arm(amenv_ppo_ctl* ctl, float kl_limit, void* stream);
+/* amenv_ppo_loss_grad / amenv_ppo_mlp_step / amenv_ppo_adam_step with the control block as last argument before the stream (NULL: none) */
+int amenv_ppo_loss_grad_ctl(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
+                            const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
+                            float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats,
+                            void* workspace, amenv_ppo_ctl* ctl, void* stream);
+int amenv_ppo_mlp_step_ctl(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
+                           const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef,
+                           float vf_coef, int32_t normalize_advantage, float* flat_grad, float* stats, void* workspace, amenv_ppo_ctl* ctl,
+                           void* stream);
+int amenv_ppo_adam_step_ctl(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6,
+                            float* grad_norm_out, uint32_t* ticket, amenv_ppo_ctl* ctl, void* stream);
+
 /* Parity gate of the arm vehicle's arithmetic (no reference dynamics exist for it; DESIGN.md "arm"): the 19 state derivatives of n states
  * [n, 19] = (p, v, q, w, th, thd) under post-mixer wrenches [n, 4] = (F, Mx, My, Mz) and joint commands [n, 3], deriv [n, 19], all of `dtype`
  * (AMENV_F32 | AMENV_F64), on the current device.  form 0: the per-link Newton-Euler sums the lane and two-wave kernels run; form 1: the staged

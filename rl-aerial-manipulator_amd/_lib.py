@@ -85,6 +85,12 @@ class ActionDelayC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_steps", C.c_int32), ("max_steps", C.c_int32)]
 
 
+class PpoCtl(C.Structure):
+    """amenv_ppo_ctl: the device control block of a PPO update (include/amenv.h); this is the layout of the bytes read back from it."""
+    _fields_ = [("struct_size", C.c_uint32), ("kl_limit", C.c_float), ("stop", C.c_uint32), ("stop_seen", C.c_uint32), ("evaluated", C.c_uint32),
+                ("applied", C.c_uint32), ("kl_sum", C.c_float), ("kl_last", C.c_float), ("sum", C.c_float * 5), ("reserved", C.c_uint32 * 3)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -146,6 +152,11 @@ SYMBOLS = {
     "amenv_ppo_mlp_workspace_bytes": (C.c_size_t, []),
     "amenv_ppo_mlp_step": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P]),
     "amenv_ppo_adam_step": (C.c_int, [_P] * 5 + [C.c_int64, _P, _P, _P, _P]),
+    "amenv_ppo_ctl_bytes": (C.c_size_t, []),
+    "amenv_ppo_ctl_arm": (C.c_int, [_P, C.c_float, _P]),
+    "amenv_ppo_loss_grad_ctl": (C.c_int, [_P] * 7 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "amenv_ppo_mlp_step_ctl": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P]),
+    "amenv_ppo_adam_step_ctl": (C.c_int, [_P] * 5 + [C.c_int64, _P, _P, _P, _P, _P]),
     "amenv_arm_rhs": (C.c_int, [C.POINTER(Config), C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     "amenv_pid_default_params": (C.c_int, [C.POINTER(PidParams)]),
     "amenv_pid_run": (C.c_int, [C.POINTER(PidParams), C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),

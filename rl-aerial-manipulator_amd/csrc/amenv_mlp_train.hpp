@@ -166,6 +166,13 @@ __device__ __forceinline__ void mlp_pack_element(const float* __restrict__ Pm, i
 }
 // Everything the fused kernel needs beforehand in ONE launch (each launch in this chain costs ~4.7 us whatever it does): workgroups
 // [0, adv_blocks) sum the minibatch's advantages (ppo_adv_partials), the rest write the split-weight streams.  256 threads.
+__global__ __launch_bounds__(kPpoBlock) void ppo_mlp_prologue_kernel_ctl(const amenv_ppo_ctl* ctl, const float* __restrict__ adv, int64_t n, double* __restrict__ adv_part,
+                                                                         const int64_t* __restrict__ index, int adv_blocks, const float* __restrict__ Pm, int D, int A,
+                                                                         uint16_t* __restrict__ WS) {
+  if (ppo_ctl_stopped<true>(ctl)) return;                           // the gate is shut: this minibatch step does nothing (amenv_train.hpp)
+  if (int(blockIdx.x) < adv_blocks) ppo_adv_partials_block(adv, n, adv_part, index, int(blockIdx.x), adv_blocks);   // uniform per workgroup
+  else mlp_pack_element(Pm, D, A, WS, (int(blockIdx.x) - adv_blocks) * kPpoBlock + int(threadIdx.x));
+}
 __global__ __launch_bounds__(kPpoBlock) void ppo_mlp_prologue_kernel(const float* __restrict__ adv, int64_t n, double* __restrict__ adv_part,
                                                                      const int64_t* __restrict__ index, int adv_blocks, const float* __restrict__ Pm, int D, int A,
                                                                      uint16_t* __restrict__ WS) {
@@ -348,7 +355,7 @@ __device__ __forceinline__ void mlp_tile_out(float* slab, int stride, int row0, 
 
 struct MlpLoss { float clip, vf_coef, inv_n, mu, inv_sd; };
 
-#ifdef AMENV_MLP_STAMPS   // diagnostic build: clocks per phase (forward, loss, weight gradients, data gradients, LDS publish incl. barriers), summed into stats slots 11..15
+#ifdef AMENV_MLP_STAMPS   // diagnostic build: clocks per phase (forward, loss, weight gradients, data gradients, LDS publish incl. barriers), summed into stats slots 11..15 of the CRITIC's slabs (slot 11 of the actor's is approx_kl)
 #define MLP_T0() unsigned long long t_ = __builtin_readcyclecounter()
 #define MLP_TK(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_readcyclecounter(); tph[k] += float(n_ - t_); t_ = n_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -357,12 +364,17 @@ struct MlpLoss { float clip, vf_coef, inv_n, mu, inv_sd; };
 #endif
 
 // One PPO minibatch: forward + loss + backward + weight gradients of both nets.  grid = (blocks, 2), 256 threads.
-template <int D, int A>
-__global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
-                                                            const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
-                                                            const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
-                                                            float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
-                                                            float* __restrict__ part) {
+template <bool kCtl, int D, int A>
+__device__ __forceinline__ void ppo_mlp_fused_body(amenv_ppo_ctl* ctl, const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
+                                                   const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                   const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
+                                                   float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
+                                                   float* __restrict__ part) {
+  if constexpr (kCtl) {   // the gate: read once, by every thread, before the first barrier; one thread hands what was read to the reduction launch
+    const uint32_t st = ctl->stop;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ctl->stop_seen = st;
+    if (st != 0u) return;
+  }
   extern __shared__ __attribute__((aligned(16))) float mlp_lds[];   // transposes [kXposeRows][kXs] | stats [4 wavefronts][16]
   float* xz = mlp_lds;
   float* lstats = mlp_lds + kXposeRows * kXs;
@@ -392,7 +404,7 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restr
   float els[4], isd[4];                                   // log_std / 1 / std of this lane's four head rows (actor)
 #pragma unroll
   for (int r = 0; r < 4; r++) { const int k = r + 4 * h; els[r] = k < A ? Pm[k] : 0.0f; isd[r] = __expf(-els[r]); }
-  float s_dls[4] = {0, 0, 0, 0}, s_pol = 0.0f, s_val = 0.0f, s_clipn = 0.0f;
+  float s_dls[4] = {0, 0, 0, 0}, s_pol = 0.0f, s_val = 0.0f, s_clipn = 0.0f, s_kl = 0.0f;
 #ifdef AMENV_MLP_STAMPS
   float tph[5] = {0, 0, 0, 0, 0};
 #endif
@@ -453,7 +465,8 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restr
         lp += k < A ? fma_(-0.5f * z[r], z[r], -els[r]) - 0.918938533204672742f : 0.0f;
       }
       lp += __shfl_xor(lp, 32);
-      const float ratio = __expf(lp - olp_s);
+      const float lr = lp - olp_s;
+      const float ratio = __expf(lr);
       const float a = (adv_s - Lp.mu) * Lp.inv_sd;
       const float s1 = a * ratio, s2 = a * fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
       const bool inside = ratio >= 1.0f - clip && ratio <= 1.0f + clip;
@@ -463,7 +476,7 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restr
         dY[0][r] = g_lp * z[r] * isd[r];
         s_dls[r] += (r + 4 * h < A) ? g_lp * fma_(z[r], z[r], -1.0f) : 0.0f;
       }
-      if (sv && h == 0) { s_pol += -fminf(s1, s2); s_clipn += fabsf(ratio - 1.0f) > clip ? 1.0f : 0.0f; }
+      if (sv && h == 0) { s_pol += -fminf(s1, s2); s_clipn += fabsf(ratio - 1.0f) > clip ? 1.0f : 0.0f; if (kCtl) s_kl += (ratio - 1.0f) - lr; }   // (SB3's approx_kl estimator)
     } else if (h == 0) {
       const float dv = adv_s - Y[0][0];
       dY[0][0] = sv ? -2.0f * vf_coef * dv * Lp.inv_n : 0.0f;
@@ -550,12 +563,12 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restr
     if ((wave & 1) == 0) { slab[kAccW2 + (32 * (wave >> 1) + nn) * 129 + 128] = gb2; slab[kAccW3 + (32 * (wave >> 1) + nn) * 65 + 64] = gb3; }
     if (wave == 0) slab[kAccW4 + nn * 65 + 64] = gb4;
   }
-  // per-lane loss sums -> the stats slots (d log_std[0..A), policy, value, clip count): a butterfly over the 32 lanes of each half, one
+  // per-lane loss sums -> the stats slots (d log_std[0..A), policy, value, clip count, approx-kl sum): a butterfly over the 32 lanes of each half, one
   // LDS slot per wavefront, then a fixed-order sum over the wavefronts -- deterministic like the rest
   {
-    float vals[7] = {s_dls[0], s_dls[1], s_dls[2], s_dls[3], s_pol, s_val, s_clipn};
+    float vals[8] = {s_dls[0], s_dls[1], s_dls[2], s_dls[3], s_pol, s_val, s_clipn, s_kl};
 #pragma unroll
-    for (int k = 0; k < 7; k++)
+    for (int k = 0; k < (kCtl ? 8 : 7); k++)
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) vals[k] += __shfl_xor(vals[k], o);
     if (nn == 0) {
@@ -563,15 +576,31 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restr
       if (net == 0) {
 #pragma unroll
         for (int r = 0; r < 4; r++) ws_[r + 4 * h] = vals[r];
-        if (h == 0) { ws_[8] = vals[4]; ws_[10] = vals[6]; }
+        if (h == 0) { ws_[8] = vals[4]; ws_[10] = vals[6]; if (kCtl) ws_[11] = vals[7]; }
       } else if (h == 0) ws_[9] = vals[5];
 #ifdef AMENV_MLP_STAMPS
-      if (h == 0) for (int k = 0; k < 5; k++) ws_[11 + k] = tph[k];
+      if (h == 0 && net == 1) for (int k = 0; k < 5; k++) ws_[11 + k] = tph[k];
 #endif
     }
   }
   __syncthreads();
   if (threadIdx.x < 16) slab[kAccStats + threadIdx.x] = ((lstats[threadIdx.x] + lstats[16 + threadIdx.x]) + lstats[32 + threadIdx.x]) + lstats[48 + threadIdx.x];
+}
+template <int D, int A>
+__global__ __launch_bounds__(256) void ppo_mlp_fused_kernel(const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
+                                                            const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                            const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
+                                                            float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
+                                                            float* __restrict__ part) {
+  ppo_mlp_fused_body<false, D, A>(nullptr, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf_coef, normalize, adv_part, adv_blocks, part);
+}
+template <int D, int A>
+__global__ __launch_bounds__(256) void ppo_mlp_fused_kernel_ctl(amenv_ppo_ctl* ctl, const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
+                                                                const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                                const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
+                                                                float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
+                                                                float* __restrict__ part) {
+  ppo_mlp_fused_body<true, D, A>(ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf_coef, normalize, adv_part, adv_blocks, part);
 }
 
 // The forward passes alone: mean [n, A] = action_net(pi trunk(obs)), value [n] = value_net(vf trunk(obs)) for large batches (the rollout
@@ -625,17 +654,24 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const float* __rest
   }
 }
 
-// Fixed-order sum of the per-workgroup slabs into the flat gradient (SB3 parameter order) + d log_std + the four reported scalars.
+// Fixed-order sum of the per-workgroup slabs into the flat gradient (SB3 parameter order) + d log_std + the reported scalars.
+// Plain form: grid = ceil((total + 4) / 64), the four scalars follow the gradient entries.  _ctl form: grid = ceil(total / 64) + 1, the LAST
+// workgroup holds the scalars alone (policy loss, value loss, entropy loss, clip fraction, approx_kl in lanes 0..4 of its first wavefront),
+// so that one lane has them all: it adds them to the block's sums and takes the gate's decision.  That launch obeys `stop_seen`, never
+// `stop`, which it may set itself (amenv_train.hpp).  Every output is the same sum in the same order in both forms.
 // 512 threads = 64 outputs x 8 slab groups: a wavefront reads 64 consecutive slots of one slab (coalesced), the (up to 16) loads of its
 // group in flight together; the group sums meet in LDS and are added in group order.
 constexpr int kRedGroups = 8;
-__global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel(const float* __restrict__ part, int blocks, int D, int A, int64_t n, const float* __restrict__ Pm,
-                                                              float ent_coef, float* __restrict__ grad, float* __restrict__ stats) {
+template <bool kCtl>
+__device__ __forceinline__ void mlp_grad_reduce_body(amenv_ppo_ctl* ctl, const float* __restrict__ part, int blocks, int D, int A, int64_t n, const float* __restrict__ Pm,
+                                                     float ent_coef, float* __restrict__ grad, float* __restrict__ stats) {
   __shared__ float sh[kRedGroups][64];
+  if constexpr (kCtl) { if (ctl->stop_seen != 0u) return; }
   const int trunk = kH1 * D + kH1 + kH2 * kH1 + kH2 + kH3 * kH2 + kH3;
   const int total = A + 2 * trunk + A * kH3 + A + kH3 + 1;
   const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int tid = blockIdx.x * 64 + lane;
+  const bool scalars = kCtl && int(blockIdx.x) * 64 >= total; // _ctl form: the last workgroup, the one behind the gradient entries
+  const int tid = scalars ? total + lane : int(blockIdx.x) * 64 + lane;
   int net = 0, slot = -1;                                    // slot < 0: nothing to sum (entropy, out of range)
   if (tid < A) slot = kAccStats + tid;
   else if (tid < total) {
@@ -655,11 +691,12 @@ __global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel(const 
       else if ((e -= A) < kH3) { net = 1; slot = kAccW4 + e; }
       else { net = 1; slot = kAccW4 + 64; }
     }
-  } else if (tid < total + 4) {
-    const int k = tid - total;                               // policy loss, value loss, entropy loss, clip fraction
+  } else if (tid < total + (kCtl ? 5 : 4) && (!kCtl || scalars)) {
+    const int k = tid - total;                               // policy loss, value loss, entropy loss, clip fraction, approx_kl
     if (k == 0) slot = kAccStats + 8;
     else if (k == 1) { net = 1; slot = kAccStats + 9; }
     else if (k == 3) slot = kAccStats + 10;
+    else if (kCtl && k == 4) slot = kAccStats + 11;
   }
   float t = 0.0f;
   if (slot >= 0) {
@@ -677,15 +714,36 @@ __global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel(const 
   }
   sh[grp][lane] = t;
   __syncthreads();
-  if (grp != 0 || tid >= total + 4) return;
+  if (grp != 0 || (!kCtl && tid >= total + 4)) return;
   t = 0.0f;
 #pragma unroll
   for (int g = 0; g < kRedGroups; g++) t += sh[g][lane];
-  if (tid >= total) {
-    const int k = tid - total;
-    if (k == 2) { float e = 0.0f; for (int j = 0; j < A; j++) e += 1.418938533204672742f + Pm[j]; stats[2] = -e; }
-    else stats[k] = t / float(n);
-  } else grad[tid] = tid < A ? t - ent_coef : t;
+  if constexpr (!kCtl) {
+    if (tid >= total) {
+      const int k = tid - total;
+      if (k == 2) { float e = 0.0f; for (int j = 0; j < A; j++) e += 1.418938533204672742f + Pm[j]; stats[2] = -e; }
+      else stats[k] = t / float(n);
+    } else grad[tid] = tid < A ? t - ent_coef : t;
+    return;
+  }
+  if (!scalars) {                                            // (uniform per workgroup)
+    if (tid < total) grad[tid] = tid < A ? t - ent_coef : t;
+    return;
+  }
+  const int k = lane;
+  float sk = t / float(n);
+  if (k == 2) { float e = 0.0f; for (int j = 0; j < A; j++) e += 1.418938533204672742f + Pm[j]; sk = -e; }
+  if (k < 4) stats[k] = sk;
+  const float pl = __shfl(sk, 0), vl = __shfl(sk, 1), el = __shfl(sk, 2), cf = __shfl(sk, 3), kl = __shfl(sk, 4);
+  if (k == 0) ppo_ctl_evaluated(ctl, pl, vl, el, cf, kl);
+}
+__global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel(const float* __restrict__ part, int blocks, int D, int A, int64_t n, const float* __restrict__ Pm,
+                                                              float ent_coef, float* __restrict__ grad, float* __restrict__ stats) {
+  mlp_grad_reduce_body<false>(nullptr, part, blocks, D, A, n, Pm, ent_coef, grad, stats);
+}
+__global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel_ctl(amenv_ppo_ctl* ctl, const float* __restrict__ part, int blocks, int D, int A, int64_t n,
+                                                                  const float* __restrict__ Pm, float ent_coef, float* __restrict__ grad, float* __restrict__ stats) {
+  mlp_grad_reduce_body<true>(ctl, part, blocks, D, A, n, Pm, ent_coef, grad, stats);
 }
 
 // Gradient-norm clip + Adam on the flat parameter buffer in one launch (torch.nn.utils.clip_grad_norm_ + torch.optim.Adam, the step SB3's
@@ -698,10 +756,12 @@ __global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel(const 
 // entry, incremented by the last one to finish (ticket), after every workgroup has read it.
 // hyper: [0] lr  [1] beta1  [2] beta2  [3] eps  [4] max_grad_norm (<= 0: no clipping)  [5] grad_scale (1 / world size after a sum all-reduce)
 constexpr int kAdamBlock = 1024, kAdamMaxBlocks = 64;
-__global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
-                                                               float* __restrict__ step, int64_t n, const float* __restrict__ hyper, float* __restrict__ grad_norm,
-                                                               unsigned int* __restrict__ ticket) {
+template <bool kCtl>
+__device__ __forceinline__ void adam_clip_body(amenv_ppo_ctl* ctl, float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
+                                               float* __restrict__ step, int64_t n, const float* __restrict__ hyper, float* __restrict__ grad_norm,
+                                               unsigned int* __restrict__ ticket) {
   __shared__ float sh[kAdamBlock / 64];
+  if (ppo_ctl_stopped<kCtl>(ctl)) return;   // the gate (amenv_train.hpp): nothing is touched, the ticket included; `stop` is not written by this kernel
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], max_norm = hyper[4], scale = hyper[5];
   const float t = step[0] + 1.0f;
   float ss = 0.0f;
@@ -748,8 +808,21 @@ __global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel(float* __restrict
   __syncthreads();
   if (threadIdx.x == 0) {
     __threadfence();
-    if (atomicAdd(ticket, 1u) == gridDim.x - 1) { step[0] = t; *ticket = 0u; }
+    if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+      step[0] = t; *ticket = 0u;
+      if constexpr (kCtl) { ctl->applied += 1u; ctl->sum[4] += gn; }
+    }
   }
+}
+__global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
+                                                               float* __restrict__ step, int64_t n, const float* __restrict__ hyper, float* __restrict__ grad_norm,
+                                                               unsigned int* __restrict__ ticket) {
+  adam_clip_body<false>(nullptr, param, grad, m, v, step, n, hyper, grad_norm, ticket);
+}
+__global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel_ctl(amenv_ppo_ctl* ctl, float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
+                                                                   float* __restrict__ v, float* __restrict__ step, int64_t n, const float* __restrict__ hyper,
+                                                                   float* __restrict__ grad_norm, unsigned int* __restrict__ ticket) {
+  adam_clip_body<true>(ctl, param, grad, m, v, step, n, hyper, grad_norm, ticket);
 }
 
 }  // namespace amenv_dev

@@ -101,12 +101,46 @@ __global__ __launch_bounds__(256) void gaussian_act_kernel(const float* __restri
 // unclipped term is the smaller one, else 0.
 constexpr int kPpoBlock = 256;
 constexpr int kPpoMaxBlocks = 1024;
-constexpr int kPpoPartial = AMENV_MAX_JOINTS + kActDim + 4;   // d log_std[<=7] + policy / value / clip-fraction sums (+1 spare)
+constexpr int kPpoPartial = AMENV_MAX_JOINTS + kActDim + 4;   // d log_std[<=7] + policy / value / clip-fraction / approx-kl sums
+static_assert(kPpoPartial >= AMENV_MAX_JOINTS + 4 + 4, "ppo_loss_grad's partials: A + 4 slots for A <= 7");
+
+// ---- the device control block of an update (include/amenv.h) ----------------------------------------------------------------
+// `stop` is read ONCE at kernel entry, by every thread the same way and before the first barrier, so a launch either runs whole or not
+// at all.  No launch reads `stop` at entry and also writes it from one of several workgroups: the single-workgroup ppo_finalize does
+// both in program order; the many-workgroup mlp_grad_reduce_kernel writes it and obeys `stop_seen` instead, the copy the fused kernel in
+// front of it made of what IT read (a late workgroup of the reduction would otherwise see the stop its own launch just set and leave
+// its slice of the gradient unwritten).
+//
+// Every kernel that can take the block is built in TWO forms from one body, `<kCtl>`: `name` (kCtl = false) has the signature and the code
+// it had before the block existed -- no `ctl` parameter, no test at entry, no approx_kl sum -- and is what the plain entry points launch;
+// `name_ctl` (kCtl = true, ctl never NULL) is what the _ctl entry points launch when they are given a block.  (One form with a run-time
+// test of `ctl` measured 0.85 us slower through the plain entry points on a 40 us minibatch step of 1,024 samples: profiles/r18.)
+template <bool kCtl>
+__device__ __forceinline__ bool ppo_ctl_stopped(const amenv_ppo_ctl* ctl) {
+  if constexpr (kCtl) return ctl->stop != 0u;
+  else return false;
+}
+
+// one thread, after the minibatch's scalars are final: s4 = {policy loss, value loss, entropy loss, clip fraction}
+__device__ __forceinline__ void ppo_ctl_evaluated(amenv_ppo_ctl* ctl, float pl, float vl, float el, float cf, float kl) {
+  ctl->evaluated += 1u;
+  ctl->kl_sum += kl;
+  ctl->kl_last = kl;
+  ctl->sum[0] += pl; ctl->sum[1] += vl; ctl->sum[2] += el; ctl->sum[3] += cf;
+  if (ctl->kl_limit > 0.0f && kl > ctl->kl_limit) ctl->stop = 1u;
+}
+__global__ void ppo_ctl_arm_kernel(amenv_ppo_ctl* ctl, float kl_limit) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  amenv_ppo_ctl z{};
+  z.struct_size = uint32_t(sizeof(amenv_ppo_ctl));
+  z.kl_limit = kl_limit;
+  *ctl = z;
+}
 
 // body of ppo_adv_partials for block `blk` of `nblk` (also called from the fused minibatch step's prologue kernel, amenv_mlp_train.hpp)
 __device__ __forceinline__ void ppo_adv_partials_block(const float* __restrict__ adv, int64_t n, double* __restrict__ part, const int64_t* __restrict__ index,
                                                        int blk, int nblk) {
-  __shared__ double sh[2][kPpoBlock / 64];
+  __shared__ double sh[2][kPpoBlock / 64];   // (callers test the control block's stop flag before they come here: barrier below)
   double s = 0.0, q = 0.0;
   for (int64_t i = int64_t(blk) * kPpoBlock + threadIdx.x; i < n; i += int64_t(nblk) * kPpoBlock) {
     const double a = adv[index ? index[i] : i];
@@ -126,16 +160,23 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_adv_partials(const float* __res
                                                               const int64_t* __restrict__ index = nullptr) {
   ppo_adv_partials_block(adv, n, part, index, int(blockIdx.x), int(gridDim.x));
 }
+__global__ __launch_bounds__(kPpoBlock) void ppo_adv_partials_ctl(const amenv_ppo_ctl* ctl, const float* __restrict__ adv, int64_t n, double* __restrict__ part,
+                                                                  const int64_t* __restrict__ index) {
+  if (ppo_ctl_stopped<true>(ctl)) return;
+  ppo_adv_partials_block(adv, n, part, index, int(blockIdx.x), int(gridDim.x));
+}
 
-template <int A>
-__global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad(const float* __restrict__ mean, const float* __restrict__ value,
-                                                           const float* __restrict__ log_std, const float* __restrict__ actions,
-                                                           const float* __restrict__ old_logp, const float* __restrict__ adv,
-                                                           const float* __restrict__ ret, int64_t n, float clip, float vf_coef,
-                                                           int normalize, const double* __restrict__ adv_part, int adv_blocks,
-                                                           float* __restrict__ d_mean, float* __restrict__ d_value,
-                                                           float* __restrict__ part) {
+template <bool kCtl, int A>
+__device__ __forceinline__ void ppo_loss_grad_body(const amenv_ppo_ctl* ctl, const float* __restrict__ mean, const float* __restrict__ value,
+                                                   const float* __restrict__ log_std, const float* __restrict__ actions,
+                                                   const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                   const float* __restrict__ ret, int64_t n, float clip, float vf_coef,
+                                                   int normalize, const double* __restrict__ adv_part, int adv_blocks,
+                                                   float* __restrict__ d_mean, float* __restrict__ d_value,
+                                                   float* __restrict__ part) {
   __shared__ float sh[kPpoBlock / 64][kPpoPartial];
+  if (ppo_ctl_stopped<kCtl>(ctl)) return;
+  constexpr int NP = kCtl ? A + 4 : A + 3;                                   // partial slots in use: approx_kl only with a control block
   // advantage statistics: every block sums the (few hundred) partials in the same fixed order
   float mu = 0.0f, inv_sd = 1.0f;
   if (normalize && n > 1) {
@@ -160,7 +201,8 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad(const float* __restri
       z[k] = (actions[i * A + k] - mean[i * A + k]) * isd[k];
       lp += fma_(-0.5f * z[k], z[k], -els[k]) - 0.918938533204672742f;
     }
-    const float r = expf(lp - old_logp[i]);
+    const float lr = lp - old_logp[i];
+    const float r = expf(lr);
     const float a = (adv[i] - mu) * inv_sd;
     const float s1 = a * r, s2 = a * fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
     const bool inside = r >= 1.0f - clip && r <= 1.0f + clip;
@@ -175,39 +217,72 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad(const float* __restri
     acc[A] += -fminf(s1, s2);
     acc[A + 1] += dv * dv;
     acc[A + 2] += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+    if (kCtl) acc[A + 3] += (r - 1.0f) - lr;                                 // SB3's approx_kl estimator
   }
 #pragma unroll
-  for (int k = 0; k < A + 3; k++)
+  for (int k = 0; k < NP; k++)
     for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
-    for (int k = 0; k < A + 3; k++) sh[w][k] = acc[k];
+    for (int k = 0; k < NP; k++) sh[w][k] = acc[k];
   __syncthreads();
-  if (threadIdx.x < A + 3) {
+  if (threadIdx.x < NP) {
     float t = 0.0f;
     for (int k = 0; k < kPpoBlock / 64; k++) t += sh[k][threadIdx.x];
     part[blockIdx.x * kPpoPartial + threadIdx.x] = t;
   }
 }
 
+template <int A>
+__global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad(const float* __restrict__ mean, const float* __restrict__ value, const float* __restrict__ log_std,
+                                                           const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                           const float* __restrict__ ret, int64_t n, float clip, float vf_coef, int normalize,
+                                                           const double* __restrict__ adv_part, int adv_blocks, float* __restrict__ d_mean,
+                                                           float* __restrict__ d_value, float* __restrict__ part) {
+  ppo_loss_grad_body<false, A>(nullptr, mean, value, log_std, actions, old_logp, adv, ret, n, clip, vf_coef, normalize, adv_part, adv_blocks, d_mean, d_value, part);
+}
+template <int A>
+__global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad_ctl(const amenv_ppo_ctl* ctl, const float* __restrict__ mean, const float* __restrict__ value,
+                                                               const float* __restrict__ log_std, const float* __restrict__ actions,
+                                                               const float* __restrict__ old_logp, const float* __restrict__ adv, const float* __restrict__ ret,
+                                                               int64_t n, float clip, float vf_coef, int normalize, const double* __restrict__ adv_part,
+                                                               int adv_blocks, float* __restrict__ d_mean, float* __restrict__ d_value, float* __restrict__ part) {
+  ppo_loss_grad_body<true, A>(ctl, mean, value, log_std, actions, old_logp, adv, ret, n, clip, vf_coef, normalize, adv_part, adv_blocks, d_mean, d_value, part);
+}
+
 // d_log_std[k] = sum of partials + ent_coef * d(-mean entropy)/d log_std = ... - ent_coef ; stats = {policy loss, value loss,
-// entropy loss, clip fraction}
-__global__ void ppo_finalize(const float* __restrict__ part, int blocks, int A, int64_t n, const float* __restrict__ log_std, float ent_coef,
-                             float* __restrict__ d_log_std, float* __restrict__ stats) {
+// entropy loss, clip fraction} and nothing behind them; with a control block approx_kl goes to its kl_last, with the block's sums and the gate.
+// ONE wavefront (64 threads).
+template <bool kCtl>
+__device__ __forceinline__ void ppo_finalize_body(amenv_ppo_ctl* ctl, const float* __restrict__ part, int blocks, int A, int64_t n, const float* __restrict__ log_std,
+                                                  float ent_coef, float* __restrict__ d_log_std, float* __restrict__ stats) {
+  if (ppo_ctl_stopped<kCtl>(ctl)) return;
   const int k = threadIdx.x;
-  if (k >= A + 3) return;
-  float t = 0.0f;
-  for (int b = 0; b < blocks; b++) t += part[b * kPpoPartial + k];
+  float t = 0.0f, e = 0.0f;
+  if (k < (kCtl ? A + 4 : A + 3))
+    for (int b = 0; b < blocks; b++) t += part[b * kPpoPartial + k];
   if (k < A) d_log_std[k] = t - ent_coef;
   else if (k == A) stats[0] = t / float(n);
   else if (k == A + 1) stats[1] = t / float(n);
-  else {
+  else if (k == A + 2) {
     stats[3] = t / float(n);
-    float e = 0.0f;
     for (int j = 0; j < A; j++) e += 1.418938533204672742f + log_std[j];
     stats[2] = -e;
   }
+  if constexpr (kCtl) {
+    const float mean_k = t / float(n);
+    const float pl = __shfl(mean_k, A), vl = __shfl(mean_k, A + 1), cf = __shfl(mean_k, A + 2), kl = __shfl(mean_k, A + 3), el = -__shfl(e, A + 2);
+    if (k == 0) ppo_ctl_evaluated(ctl, pl, vl, el, cf, kl);
+  }
+}
+__global__ void ppo_finalize(const float* __restrict__ part, int blocks, int A, int64_t n, const float* __restrict__ log_std, float ent_coef,
+                             float* __restrict__ d_log_std, float* __restrict__ stats) {
+  ppo_finalize_body<false>(nullptr, part, blocks, A, n, log_std, ent_coef, d_log_std, stats);
+}
+__global__ void ppo_finalize_ctl(amenv_ppo_ctl* ctl, const float* __restrict__ part, int blocks, int A, int64_t n, const float* __restrict__ log_std, float ent_coef,
+                                 float* __restrict__ d_log_std, float* __restrict__ stats) {
+  ppo_finalize_body<true>(ctl, part, blocks, A, n, log_std, ent_coef, d_log_std, stats);
 }
 
 }  // namespace amenv_dev

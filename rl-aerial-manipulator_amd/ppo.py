@@ -248,6 +248,15 @@ class RolloutBuffer:
         return sum(t.numel() * t.element_size() for t in vars(self).values() if torch.is_tensor(t))
 
 
+def explained_variance(values, returns):
+    """SB3 `explained_variance(y_pred = values, y_true = returns)`: 1 - Var[returns - values] / Var[returns] (population variances) as a
+    0-dim tensor on the inputs' device; 0.0 where SB3 gives NaN (constant returns), so that a log record stays finite."""
+    y, v = returns.reshape(-1).to(torch.float64), values.reshape(-1).to(torch.float64)
+    var_y = y.var(unbiased=False)
+    ev = 1.0 - (y - v).var(unbiased=False) / torch.where(var_y > 0, var_y, torch.ones_like(var_y))
+    return torch.where(var_y > 0, ev, torch.zeros_like(ev)).to(torch.float32)
+
+
 def compute_gae(buffer, gamma, gae_lambda):
     """advantages / returns of a rollout buffer through the HIP kernel (`amenv_gae`); device tensors only."""
     b = buffer
@@ -284,14 +293,41 @@ class MinibatchStep:
     On the GPU the step is launch-bound in eager mode (~200 small kernels per minibatch; rocprof: 245 ms of kernels in a
     359 ms update), so after three eager calls it is captured into HIP graphs on static minibatch buffers and replayed:
     one graph for a single GPU; for several GPUs two graphs (forward/backward | clip + Adam) around the ONE eager RCCL
-    all-reduce of the flat gradient buffer.  A ragged last minibatch (n % batch_size) always runs eagerly."""
+    all-reduce of the flat gradient buffer.  A ragged last minibatch (n % batch_size) always runs eagerly.
+
+    `stats` (device, 5 floats): policy loss, value loss, entropy loss, clip fraction, gradient norm of the last minibatch; `kl` (device,
+    1 float): its approx_kl -- on the HIP paths a view of the control block's `kl_last`, which is where the kernels put it.
+
+    `target_kl` (SB3's: leave the update once a minibatch's approx_kl exceeds 1.5 target_kl, after its loss and before its optimiser
+    step).  Where the whole step is HIP (fused MLP + fused Adam) the decision is taken and obeyed ON THE DEVICE through the
+    control block `amenv_ppo_ctl`: no host synchronisation, the caller keeps launching and the kernels of the later minibatches return at
+    entry (`device_gate`).  Every other path checks on the host like SB3, one synchronisation per minibatch, and sets `stopped`.  Captured
+    graphs are not built with it (`use_graph=True` raises), nor are several ranks (they would disagree on the stop).  `arm()` starts an
+    update: it zeroes the counters and re-opens the gate; `ppo_update` calls it.
+
+    `set_hyper(learning_rate, clip_range)`: new values for the next minibatches (the schedules of `PPO`).  The fused Adam step re-uploads
+    its hyper-parameters when they change and the eager paths read them on every call; CAPTURED GRAPHS have `clip_range` baked in (a launch
+    argument) and, with torch's Adam, the learning rate too: such a change drops them and the next full minibatch captures again (one
+    capture per change, i.e. per iteration under a schedule).  With the fused Adam step the learning rate lives in a device buffer that the
+    replayed launch reads, so a change of the learning rate alone is one small upload and the graphs stay."""
 
     def __init__(self, policy, optimizer, *, clip_range=0.2, ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5,
-                 normalize_advantage=True, dist=None, use_graph=None, split_graphs=None, fused_loss=None, fused_mlp=None):
+                 normalize_advantage=True, dist=None, use_graph=None, split_graphs=None, fused_loss=None, fused_mlp=None, target_kl=None):
         if policy.flat_grad is None:
             policy.flatten_()
         self.policy, self.optimizer, self.dist = policy, optimizer, dist
         self.world = dist.get_world_size() if dist is not None else 1
+        self.target_kl = None if target_kl is None else float(target_kl)
+        if self.target_kl is not None:
+            if not self.target_kl > 0.0:
+                raise L.AmenvError(f"target_kl must be positive (got {target_kl!r}); None switches the early stop off")
+            if self.world > 1:
+                raise L.AmenvError("target_kl with several ranks is not built: every rank would take the stop decision from its own shard's approx_kl and "
+                                   "the ranks would disagree on it (no multi-GPU machine was available to test an agreed stop); train with target_kl=None")
+            if use_graph:
+                raise L.AmenvError("target_kl with use_graph=True is not built: the early stop sits between the loss and the optimiser step, inside "
+                                   "what a captured graph replays as one piece; leave use_graph unset (target_kl runs the eager paths)")
+            use_graph = False
         # two graphs around an eager all-reduce whenever there is a process group to talk to (tests force it with 1 rank)
         self.split = (self.world > 1) if split_graphs is None else bool(split_graphs)
         self.clip_range, self.ent_coef, self.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
@@ -320,6 +356,53 @@ class MinibatchStep:
         self._static = None
         self._graphs = None
         self._eager_calls = 0
+        # the device control block (amenv_ppo_ctl) of the HIP paths: the gate where the whole step is HIP, approx_kl and the running sums everywhere
+        self.device_gate = self.target_kl is not None and self.fused_mlp and self.fused_adam
+        self._ctl = None
+        if dev.type == "cuda" and (self.fused_loss or self.fused_mlp):
+            if L.load().amenv_ppo_ctl_bytes() != C.sizeof(L.PpoCtl):
+                raise L.AmenvError("amenv_ppo_ctl: the library's layout differs from this package's (rebuild libamenv.so)")
+            self._ctl = torch.zeros(C.sizeof(L.PpoCtl) // 4, dtype=torch.int32, device=dev)
+        k = L.PpoCtl.kl_last.offset // 4
+        self.kl = torch.zeros(1, device=dev) if self._ctl is None else self._ctl.view(torch.float32)[k:k + 1]   # approx_kl of the last minibatch
+        # host side of the gate (every path but the device gate): sums over the evaluated minibatches, counters, the stop
+        self._acc = torch.zeros(6, device=dev)
+        self.evaluated = self.applied = 0
+        self.stopped = False
+        self.arm()
+
+    # -- training controls -------------------------------------------------------------------------
+    def _ctl_ptr(self):
+        return None if self._ctl is None else C.c_void_p(self._ctl.data_ptr())
+
+    def arm(self):
+        """Start an update: counters and sums to zero, the gate open (asynchronous: one tiny launch on the current stream)."""
+        if self._ctl is not None:
+            limit = 1.5 * self.target_kl if self.device_gate else 0.0
+            rc = L.load().amenv_ppo_ctl_arm(self._ctl_ptr(), limit, C.c_void_p(torch.cuda.current_stream(self._ctl.device).cuda_stream))
+            if rc != 0:
+                raise L.AmenvError(f"amenv_ppo_ctl_arm failed ({rc})")
+        self._acc.zero_()
+        self.evaluated = self.applied = 0
+        self.stopped = False
+
+    def set_hyper(self, learning_rate=None, clip_range=None):
+        changed = False
+        if clip_range is not None and float(clip_range) != self.clip_range:
+            self.clip_range, changed = float(clip_range), True
+        if learning_rate is not None:
+            for g in self.optimizer.param_groups:
+                if isinstance(g["lr"], torch.Tensor):
+                    g["lr"].fill_(float(learning_rate))
+                elif g["lr"] != float(learning_rate):
+                    g["lr"] = float(learning_rate)
+                    if self.fused_adam:                  # the fused Adam step reads lr from `hyper6` on the device, inside a replayed graph too
+                        if self._adam_hyper is not None:
+                            self._adam_upload_hyper()
+                    else:
+                        changed = True                   # torch's Adam took the Python float into the capture
+        if changed and self._graphs is not None:         # baked into a capture: capture again at the next full minibatch
+            self._graphs = self._static = None
 
     # -- the arithmetic (shared by the eager and the captured path) --------------------------------
     def _forward_backward(self, obs, actions, old_logp, adv, ret):
@@ -330,7 +413,8 @@ class MinibatchStep:
         if self.normalize_advantage and adv.numel() > 1:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         values, logp, entropy = self.policy.evaluate_actions(obs, actions)
-        ratio = torch.exp(logp - old_logp)
+        log_ratio = logp - old_logp
+        ratio = torch.exp(log_ratio)
         c = self.clip_range
         pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1.0 - c, 1.0 + c)).mean()
         vl = torch.nn.functional.mse_loss(ret, values)
@@ -342,6 +426,7 @@ class MinibatchStep:
         with torch.no_grad():
             self.stats[0], self.stats[1], self.stats[2] = pl.detach(), vl.detach(), el.detach()
             self.stats[3] = ((ratio.detach() - 1.0).abs() > c).float().mean()
+            self.kl[0] = ((ratio.detach() - 1.0) - log_ratio.detach()).mean()         # SB3's approx_kl
 
     def _forward_backward_fused(self, obs, actions, old_logp, adv, ret):
         """Same loss, with everything between the network outputs and the backward pass in the HIP kernels of
@@ -356,9 +441,9 @@ class MinibatchStep:
         d_mean, d_value, d_log_std, ws = self._fused_buf
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         m, v = mean.detach().contiguous(), values.detach().contiguous()
-        rc = L.load().amenv_ppo_loss_grad(p(m), p(v), p(pol.log_std.detach()), p(actions), p(old_logp), p(adv), p(ret), n, a, self.clip_range,
-                                          self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(d_mean), p(d_value), p(d_log_std),
-                                          p(self.stats), p(ws), C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
+        rc = L.load().amenv_ppo_loss_grad_ctl(p(m), p(v), p(pol.log_std.detach()), p(actions), p(old_logp), p(adv), p(ret), n, a, self.clip_range,
+                                              self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(d_mean), p(d_value), p(d_log_std),
+                                              p(self.stats), p(ws), self._ctl_ptr(), C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
         if rc != 0:
             raise L.AmenvError(f"amenv_ppo_loss_grad failed ({rc})")
         grads = torch.autograd.grad([mean, values], self._net_params, grad_outputs=[d_mean, d_value])
@@ -384,9 +469,9 @@ class MinibatchStep:
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         obs, actions = obs.contiguous(), actions.contiguous()
         n = obs.shape[0] if index is None else index.shape[0]
-        rc = L.load().amenv_ppo_mlp_step(p(pol.flat_param.detach()), pol.obs_dim, pol.act_dim, p(obs), p(actions), p(old_logp), p(adv), p(ret),
-                                         None if index is None else p(index), n, self.clip_range, self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(pol.flat_grad), p(self.stats),
-                                         p(self._mlp_ws), C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
+        rc = L.load().amenv_ppo_mlp_step_ctl(p(pol.flat_param.detach()), pol.obs_dim, pol.act_dim, p(obs), p(actions), p(old_logp), p(adv), p(ret),
+                                             None if index is None else p(index), n, self.clip_range, self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(pol.flat_grad), p(self.stats),
+                                             p(self._mlp_ws), self._ctl_ptr(), C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
         if rc != 0:
             raise L.AmenvError(f"amenv_ppo_mlp_step failed ({rc})")
 
@@ -406,20 +491,27 @@ class MinibatchStep:
             st["step"] = torch.zeros((), dtype=torch.float32, device=leaf.device)
             st["exp_avg"] = torch.zeros_like(pol.flat_param)
             st["exp_avg_sq"] = torch.zeros_like(pol.flat_param)
+        self._adam_upload_hyper()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        rc = L.load().amenv_ppo_adam_step_ctl(p(pol.flat_param.detach()), p(pol.flat_grad), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"]), pol.flat_param.numel(),
+                                              p(self._adam_hyper), C.c_void_p(self.stats.data_ptr() + 16), p(self._adam_ticket), self._ctl_ptr(),
+                                              C.c_void_p(torch.cuda.current_stream(leaf.device).cuda_stream))
+        if rc != 0:
+            raise L.AmenvError(f"amenv_ppo_adam_step failed ({rc})")
+
+    def _adam_upload_hyper(self):
+        """hyper6 of the fused Adam step on the device, re-uploaded when a value changed (a host-to-device copy: `_capture` calls this
+        BEFORE it starts capturing, a copy from pageable memory is not allowed inside a capture)."""
+        g = self.optimizer.param_groups[0]
         key = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, 1.0 / self.world)
         if key != self._adam_key:
+            dev = g["params"][0].device
             if self._adam_hyper is None:
-                self._adam_hyper = torch.empty(6, dtype=torch.float32, device=leaf.device)
-                self._adam_ticket = torch.zeros(1, dtype=torch.int32, device=leaf.device)
+                self._adam_hyper = torch.empty(6, dtype=torch.float32, device=dev)
+                self._adam_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             self._adam_hyper.copy_(torch.tensor(key, dtype=torch.float32))
             self._adam_key = key
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        rc = L.load().amenv_ppo_adam_step(p(pol.flat_param.detach()), p(pol.flat_grad), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"]), pol.flat_param.numel(),
-                                          p(self._adam_hyper), C.c_void_p(self.stats.data_ptr() + 16), p(self._adam_ticket),
-                                          C.c_void_p(torch.cuda.current_stream(leaf.device).cuda_stream))
-        if rc != 0:
-            raise L.AmenvError(f"amenv_ppo_adam_step failed ({rc})")
 
     def _apply(self):
         if self.fused_adam:
@@ -431,22 +523,83 @@ class MinibatchStep:
         self.optimizer.step()
         self.stats[4] = gn
 
+    def _host_gate(self):
+        """SB3's check where the step is not all HIP: between the loss and the optimiser step, one host synchronisation.  True: stop."""
+        if self.target_kl is None or self.device_gate:
+            return False
+        self._acc[:4] += self.stats[:4]
+        self._acc[5:] += self.kl
+        self.evaluated += 1
+        if float(self.kl) > 1.5 * self.target_kl:
+            self.stopped = True
+        return self.stopped
+
+    def _applied(self):
+        if self.target_kl is not None and not self.device_gate:
+            self._acc[4] += self.stats[4]
+            self.applied += 1
+
     def _eager(self, *mb):
+        if self.stopped:
+            return
         self._forward_backward(*mb)
+        if self._host_gate():
+            return
         self._exchange()
         self._apply()
+        self._applied()
 
     def indexed(self, obs, actions, old_logp, adv, ret, index):
         """One minibatch step on rows `index` of the whole-rollout tensors (fused path only): no gathered copies, no graph."""
+        if self.stopped:
+            return
         self._forward_backward_mlp(obs, actions, old_logp, adv, ret, index)
+        if self._host_gate():
+            return
         self._exchange()
         self._apply()
+        self._applied()
+
+    def readout(self, total, n_batches, extra=None):
+        """The record of an update from ONE device-to-host transfer: `total` (the last epoch's sums of `stats` and `kl` over `n_batches`
+        minibatches), the control block and `extra` (name -> 0-dim device tensor).  Without target_kl: last-epoch means, the meaning the
+        five loss keys always had.  With it: means over every minibatch that was EVALUATED in the whole update (the gradient norm: over
+        the steps applied), as SB3 logs them -- the last epoch may not have run."""
+        extra = extra or {}
+        parts = [total.to(torch.float32).view(torch.int32), self._acc.view(torch.int32)]   # (as raw words: the block's counters are integers)
+        if self._ctl is not None:
+            parts.append(self._ctl)
+        parts += [v.detach().reshape(1).to(torch.float32).view(torch.int32) for v in extra.values()]
+        host = torch.cat(parts).cpu().numpy().view(np.float32)
+        tot, acc = host[:6].astype(np.float64), host[6:12].astype(np.float64)
+        k = 12
+        evaluated, applied, stopped = self.evaluated, self.applied, self.stopped
+        if self._ctl is not None:
+            c = L.PpoCtl.from_buffer_copy(host[k:k + self._ctl.numel()].tobytes())
+            k += self._ctl.numel()
+            if self.device_gate:
+                acc = np.array([c.sum[0], c.sum[1], c.sum[2], c.sum[3], c.sum[4], c.kl_sum], dtype=np.float64)
+                evaluated, applied, stopped = int(c.evaluated), int(c.applied), bool(c.stop)
+        if self.target_kl is None:
+            s = tot / max(n_batches, 1)
+            n_updates, stopped = None, False
+        else:
+            s = acc / max(evaluated, 1)
+            s[4] = acc[4] / max(applied, 1)
+            n_updates = applied
+        rec = dict(policy_loss=float(s[0]), value_loss=float(s[1]), entropy_loss=float(s[2]), clip_fraction=float(s[3]), grad_norm=float(s[4]),
+                   approx_kl=float(s[5]), kl_early_stop=int(stopped))
+        for name, v in zip(extra, host[k:]):
+            rec[name] = float(v)
+        return rec, n_updates
 
     # -- graph capture --------------------------------------------------------------------------
     def _capture(self, mb):
         self._static = tuple(torch.empty_like(t) for t in mb)
         for s, t in zip(self._static, mb):
             s.copy_(t)
+        if self.fused_adam:
+            self._adam_upload_hyper()
         torch.cuda.synchronize()
         g1 = torch.cuda.CUDAGraph()
         if not self.split:
@@ -489,18 +642,30 @@ class MinibatchStep:
 
 
 def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *, batch_size, n_epochs, clip_range=0.2,
-               ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None, dist=None, step=None):
+               ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None, dist=None, step=None, target_kl=None,
+               extra=None):
     """SB3 `PPO.train()` on flattened rollout tensors (obs [n, D], actions [n, A], the rest [n]).  Device-agnostic torch;
     with `dist` (an initialised torch.distributed, RCCL on GPUs) every minibatch gradient is averaged over ranks with ONE
     all-reduce of the policy's flat gradient buffer.  `step`: a persistent `MinibatchStep` (keeps its captured graphs
-    between calls).  Returns the mean losses of the last epoch (one host sync)."""
+    between calls; its own `target_kl` holds).  Returns policy_loss, value_loss, entropy_loss, clip_fraction, grad_norm and approx_kl as
+    means of the last epoch (one host sync), `n_updates` (optimiser steps applied by this call) and `kl_early_stop` (0 / 1).
+
+    `target_kl`: SB3's early stop (see `MinibatchStep`).  On the all-HIP path the loop below keeps launching and the device gate makes
+    the remaining launches no-ops: still one host sync per update.  On the other paths the host checks every minibatch and breaks.  With
+    it the six scalars are means over every evaluated minibatch of the update.  `extra`: name -> 0-dim device tensor, or a callable
+    returning one that is evaluated after the last minibatch; fetched with the same transfer and returned under its name."""
     n = obs.shape[0]
     if step is None:
         step = MinibatchStep(policy, optimizer, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
-                             normalize_advantage=normalize_advantage, dist=dist, use_graph=False)
-    total = torch.zeros(5, device=obs.device)
+                             normalize_advantage=normalize_advantage, dist=dist, use_graph=False, target_kl=target_kl)
+    elif target_kl is not None and step.target_kl != float(target_kl):
+        raise L.AmenvError(f"ppo_update: target_kl={target_kl!r} but the MinibatchStep given was built with target_kl={step.target_kl!r}")
+    step.arm()
+    total = torch.zeros(6, device=obs.device)
     n_batches = 0
     for epoch in range(n_epochs):
+        if step.stopped:                                 # (host gate only: the device gate never tells the host before the end)
+            break
         # one shuffle of the whole buffer per epoch (5 gathers), then every minibatch is a contiguous slice
         perm = torch.randperm(n, device=obs.device, generator=generator)
         indexed = step.fused_mlp and not step.use_graph
@@ -512,11 +677,16 @@ def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *
                 step.indexed(obs, actions, old_logp, advantages, returns, perm[sl])
             else:
                 step(obs_s[sl], act_s[sl], olp_s[sl], adv_s[sl], ret_s[sl])
+            if step.stopped:
+                break
             if epoch == n_epochs - 1:   # losses are reported for the last epoch only (no host sync inside the loop)
-                total += step.stats
+                total[:5] += step.stats
+                total[5:] += step.kl
                 n_batches += 1
-    s = (total / max(n_batches, 1)).tolist()
-    return dict(policy_loss=s[0], value_loss=s[1], entropy_loss=s[2], clip_fraction=s[3], grad_norm=s[4])
+    extra = {k: (v() if callable(v) else v) for k, v in (extra or {}).items()}
+    rec, n_updates = step.readout(total, n_batches, extra)
+    rec["n_updates"] = n_epochs * ((n + batch_size - 1) // batch_size) if n_updates is None else n_updates
+    return rec
 
 
 class PPO:
@@ -535,11 +705,23 @@ class PPO:
     def __init__(self, env, policy=None, learning_rate=2e-4, n_steps=2048, batch_size=128, n_epochs=12, gamma=0.995,
                  gae_lambda=0.9, clip_range=0.2, ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True,
                  net_arch=(128, 64, 64), seed=0, obs_normalizer=None, bootstrap_truncated=True, dist=None, use_graph=None, fused_rollout=False, fused_mlp=None, fused_rollout_fp32_stats=True,
-                 reward_normalizer=None):
+                 reward_normalizer=None, target_kl=None):
         if env.state_dtype != torch.float32:
             raise L.AmenvError("PPO needs the fp32 environment")
         self.env, self.dist = env, dist
         self.world = dist.get_world_size() if dist is not None else 1
+        self.target_kl = None if target_kl is None else float(target_kl)
+        if self.target_kl is not None and self.world > 1:
+            raise L.AmenvError("target_kl with several ranks is not built: every rank would take the stop decision from its own shard's approx_kl and "
+                               "the ranks would disagree on it (no multi-GPU machine was available to test an agreed stop); train with target_kl=None")
+        # SB3's Schedule: a float, or a callable of progress_remaining (1 at the start of `learn`, towards 0 at its end)
+        self._lr_fn = learning_rate if callable(learning_rate) else None
+        self._clip_fn = clip_range if callable(clip_range) else None
+        self._progress = 1.0
+        if self._lr_fn is not None:
+            learning_rate = float(self._lr_fn(1.0))
+        if self._clip_fn is not None:
+            clip_range = float(self._clip_fn(1.0))
         self.device = env.device
         self.n_steps, self.batch_size, self.n_epochs = int(n_steps), int(batch_size), int(n_epochs)
         self.gamma, self.gae_lambda, self.clip_range = float(gamma), float(gae_lambda), float(clip_range)
@@ -559,7 +741,8 @@ class PPO:
         self.optimizer = torch.optim.Adam([self._leaf], lr=learning_rate, eps=1e-5, capturable=self.device.type == "cuda")
         self._step = MinibatchStep(self.policy, self.optimizer, clip_range=self.clip_range, ent_coef=self.ent_coef, vf_coef=self.vf_coef,
                                    max_grad_norm=self.max_grad_norm, normalize_advantage=self.normalize_advantage,
-                                   dist=dist if self.world > 1 else None, use_graph=use_graph, fused_mlp=fused_mlp)
+                                   dist=dist if self.world > 1 else None, use_graph=use_graph, fused_mlp=fused_mlp, target_kl=self.target_kl)
+        self.n_updates = 0   # optimiser steps applied so far (SB3's `_n_updates` counts epochs; with an early stop inside an epoch steps are the honest unit)
         self.obs_normalizer = obs_normalizer
         self.reward_normalizer = reward_normalizer
         if reward_normalizer is not None and int(reward_normalizer.num_envs) != int(env.num_envs):
@@ -689,13 +872,32 @@ class PPO:
         return b
 
     # ---- update ---------------------------------------------------------------------------------
+    @property
+    def learning_rate(self):
+        return float(self.optimizer.param_groups[0]["lr"])
+
     def train(self):
-        """SB3 `PPO.train`: n_epochs passes over the buffer in shuffled minibatches."""
+        """SB3 `PPO.train`: n_epochs passes over the buffer in shuffled minibatches, left early once approx_kl > 1.5 target_kl.
+
+        Schedules (`learning_rate` / `clip_range` given as callables of progress_remaining) are evaluated here, once per call, at the
+        progress `learn` set (1 outside `learn`), and take effect on every update path: the fused Adam step re-uploads its
+        hyper-parameters, the torch optimiser reads its `param_groups`, and captured graphs -- which bake both values in -- are dropped
+        and captured again when either changed (`MinibatchStep.set_hyper`).  Plain floats are left alone (a resumed checkpoint's
+        learning rate stays).  The record adds to the losses: approx_kl, explained_variance (SB3's, over the buffer as stored before the
+        update; 0.0 where the returns are constant), std (mean of exp(log_std) after the update), n_updates (cumulative optimiser steps),
+        learning_rate, clip_range, kl_early_stop.  All of it comes with the update's one device-to-host transfer."""
         b, T = self.buffer, self.n_steps
         n = T * b.n_envs
-        return ppo_update(self.policy, self.optimizer, b.obs[:T].reshape(n, -1), b.actions.reshape(n, -1), b.logp.reshape(n),
-                          b.advantages.reshape(n), b.returns.reshape(n), batch_size=self.batch_size, n_epochs=self.n_epochs,
-                          generator=self._gen, step=self._step)
+        self._step.set_hyper(None if self._lr_fn is None else float(self._lr_fn(self._progress)),
+                             None if self._clip_fn is None else float(self._clip_fn(self._progress)))
+        self.clip_range = self._step.clip_range
+        rec = ppo_update(self.policy, self.optimizer, b.obs[:T].reshape(n, -1), b.actions.reshape(n, -1), b.logp.reshape(n),
+                         b.advantages.reshape(n), b.returns.reshape(n), batch_size=self.batch_size, n_epochs=self.n_epochs,
+                         generator=self._gen, step=self._step,
+                         extra=dict(explained_variance=explained_variance(b.values, b.returns), std=lambda: self.policy.log_std.detach().exp().mean()))
+        self.n_updates += int(rec["n_updates"])
+        rec.update(n_updates=self.n_updates, learning_rate=self.learning_rate, clip_range=self.clip_range)
+        return rec
 
     def learn(self, total_timesteps, log_fn=None, save_freq=None, save_path=None, name_prefix="ppo_model"):
         """`model.learn(total_timesteps, callback=CheckpointCallback(save_freq, save_path, name_prefix))` (v2/rl_train.py:14-18,56):
@@ -709,7 +911,13 @@ class PPO:
             self.env.stats(reset=True)
             self.collect_rollouts()
             ep = self.env.stats(reset=True)
-            rec = self.train()
+            # SB3 (reset_num_timesteps=False): progress_remaining = 1 - num_timesteps / target, set after the rollout, before train()
+            # (held at 0 where the last rollout overshoots the target, so that a linear schedule never turns negative)
+            self._progress = max(1.0 - self.num_timesteps / float(target), 0.0)
+            try:
+                rec = self.train()
+            finally:
+                self._progress = 1.0
             n_ep = max(int(ep["episodes"]), 1)
             rec.update(timesteps=self.num_timesteps, episodes=int(ep["episodes"]), ep_rew_mean=ep["return_sum"] / n_ep,
                        ep_len_mean=ep["length_sum"] / n_ep, success_rate=ep["success"] / n_ep)
@@ -731,12 +939,13 @@ class PPO:
     # ---- checkpoints ----------------------------------------------------------------------------
     def save(self, path):
         """A zip with SB3's member names: `policy.pth` (SB3 keys: loadable into an SB3 `ActorCriticPolicy`),
-        `policy.optimizer.pth` (this class's Adam state) and `data` (hyper-parameters as plain JSON); with a reward normaliser one more
+        `policy.optimizer.pth` (this class's Adam state) and `data` (hyper-parameters as plain JSON: under a schedule the CURRENT numeric
+        learning_rate / clip_range -- schedules are not serialised, whoever resumes passes them again -- plus target_kl and n_updates); with a reward normaliser one more
         member, `reward_normalizer.npz` (its `state_dict`), which `load` restores into this model's normaliser.  It is NOT a complete
         SB3 archive (SB3's `data` holds cloudpickled objects); use `policy.pth` to move weights either way."""
         path = path if str(path).endswith(".zip") else str(path) + ".zip"
         data = {k: getattr(self, k) for k in ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef",
-                                              "vf_coef", "max_grad_norm", "normalize_advantage", "num_timesteps", "seed")}
+                                              "vf_coef", "max_grad_norm", "normalize_advantage", "num_timesteps", "seed", "target_kl", "n_updates")}
         data.update(format="amenv-ppo", draw=int(self._draw), learning_rate=self.optimizer.param_groups[0]["lr"], net_arch=list(self.policy.net_arch),
                     obs_dim=self.policy.obs_dim, act_dim=self.policy.act_dim)
         with zipfile.ZipFile(path, "w") as z:
@@ -791,6 +1000,7 @@ class PPO:
                 for g, gs in zip(self.optimizer.param_groups, osd["param_groups"]):
                     g["lr"] = gs["lr"]
             self.num_timesteps = int(data.get("num_timesteps", self.num_timesteps))
+            self.n_updates = int(data.get("n_updates", self.n_updates))
             self._draw = int(data.get("draw", self._draw))   # action-noise counter: resumed rollouts draw fresh noise
             if "reward_normalizer.npz" in names and self.reward_normalizer is not None:
                 with np.load(io.BytesIO(z.read("reward_normalizer.npz")), allow_pickle=False) as sd:

@@ -1,0 +1,306 @@
+"""PPO training controls on the GPU: approx_kl from both fused loss paths against fp64, the on-device target_kl gate of the
+fused MLP + Adam step (exact: which minibatch trips it, what every buffer holds afterwards), the gate switched off, the fused path
+against the torch path under the gate, schedules on the captured-graph path, and `PPO.learn` end to end."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import rl_aerial_manipulator_amd as amd
+from rl_aerial_manipulator_amd import _lib as L
+from rl_aerial_manipulator_amd.ppo import ActorCritic, MinibatchStep, PPO, ppo_update
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+SHAPES = [(20, 4, 1000), (29, 7, 4096)]          # a ragged tile (1000 is no multiple of 32) and a full one, the two policy shapes
+ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+
+
+def _ctl():
+    t = torch.zeros(C.sizeof(L.PpoCtl) // 4, dtype=torch.int32, device="cuda")
+    assert L.load().amenv_ppo_ctl_arm(ptr(t), 0.0, None) == 0
+    return t
+
+
+def _read(ctl):
+    return L.PpoCtl.from_buffer_copy(ctl.cpu().numpy().tobytes())
+
+
+def _kl64(pol, obs, actions, old_logp):
+    pol64 = ActorCritic(pol.obs_dim, pol.act_dim).cuda().double()
+    pol64.load_state_dict({k: v.double() for k, v in pol.state_dict().items()})
+    with torch.no_grad():
+        _, logp, _ = pol64.evaluate_actions(obs.double(), actions.double())
+        lr = logp - old_logp.double()
+        return float(((lr.exp() - 1.0) - lr).mean())
+
+
+def test_control_block_layout_and_arm():
+    lib = L.load()
+    assert lib.amenv_ppo_ctl_bytes() == C.sizeof(L.PpoCtl) == 64
+    t = torch.full((16,), 0x55555555, dtype=torch.int32, device="cuda")
+    assert lib.amenv_ppo_ctl_arm(ptr(t), 0.03, None) == 0
+    c = _read(t)
+    assert c.struct_size == 64 and c.kl_limit == np.float32(0.03) and (c.stop, c.stop_seen, c.evaluated, c.applied) == (0, 0, 0, 0)
+    assert c.kl_sum == 0.0 and c.kl_last == 0.0 and list(c.sum) == [0.0] * 5 and list(c.reserved) == [0, 0, 0]
+    assert lib.amenv_ppo_ctl_arm(None, 0.03, None) == -1 and lib.amenv_ppo_ctl_arm(ptr(t), float("nan"), None) == -1
+
+
+@pytest.mark.parametrize("D,A,n", SHAPES)
+def test_loss_kernel_approx_kl_matches_fp64_and_the_plain_entry_point_bit_for_bit(D, A, n):
+    """amenv_ppo_loss_grad_ctl on the data of test_fused_ppo_loss_kernel_matches_autograd (old log-probs off by 0.3 sigma)."""
+    torch.manual_seed(A)
+    pol = ActorCritic(D, A).cuda().flatten_()
+    with torch.no_grad():
+        pol.log_std.data.copy_(torch.linspace(-0.7, 0.2, A))
+    obs = torch.randn(n, D, device="cuda")
+    with torch.no_grad():
+        mean, value = pol.actor(obs).contiguous(), pol.critic(obs).contiguous()
+    actions = (mean + torch.randn(n, A, device="cuda") * pol.log_std.detach().exp() * 1.5).contiguous()
+    with torch.no_grad():
+        old_logp = (pol.evaluate_actions(obs, actions)[1] + 0.3 * torch.randn(n, device="cuda")).contiguous()
+    adv, ret = (torch.randn(n, device="cuda") * 3 + 0.5).contiguous(), (torch.randn(n, device="cuda") * 10).contiguous()
+    lib = L.load()
+    ws = torch.empty(lib.amenv_ppo_workspace_bytes() // 8, dtype=torch.float64, device="cuda")
+    outs = []
+    for ctl in (None, _ctl()):
+        dm, dv, dl = torch.zeros(n, A, device="cuda"), torch.zeros(n, device="cuda"), torch.zeros(A, device="cuda")
+        stats = torch.full((6,), 777.0, device="cuda")
+        args = (ptr(mean), ptr(value), ptr(pol.log_std.detach()), ptr(actions), ptr(old_logp), ptr(adv), ptr(ret), n, A, 0.2, 5e-4, 0.5, 1, ptr(dm), ptr(dv), ptr(dl), ptr(stats), ptr(ws))
+        rc = lib.amenv_ppo_loss_grad(*args, None) if ctl is None else lib.amenv_ppo_loss_grad_ctl(*args, ptr(ctl), None)
+        assert rc == 0
+        outs.append((dm, dv, dl, stats, ctl))
+    (dm0, dv0, dl0, s0, _), (dm1, dv1, dl1, s1, ctl) = outs
+    assert torch.equal(dm0, dm1) and torch.equal(dv0, dv1) and torch.equal(dl0, dl1) and torch.equal(s0[:4], s1[:4])
+    assert s0[4:].tolist() == [777.0, 777.0] == s1[4:].tolist()            # four floats from either entry point: approx_kl goes to the block
+    ref = _kl64(pol, obs, actions, old_logp)
+    c = _read(ctl)
+    kl = c.kl_last
+    print(f"loss kernel approx_kl {kl:.9g} fp64 {ref:.9g} rel {abs(kl - ref) / max(abs(ref), 1e-3):.3g}")
+    assert 5e-3 < ref < 0.2
+    assert abs(kl - ref) / max(abs(ref), 1e-3) < 1e-4
+    assert (c.evaluated, c.applied, c.stop) == (1, 0, 0) and c.kl_last == c.kl_sum and list(c.sum)[:4] == s1[:4].tolist()
+
+
+def _autograd_problem(D, A, n):
+    """The data of test_fused_mlp_step_matches_autograd (old log-probs off by 0.15 sigma)."""
+    torch.manual_seed(3)
+    pol = ActorCritic(D, A).cuda().flatten_()
+    with torch.no_grad():
+        pol.log_std.data.copy_(torch.linspace(-0.7, 0.2, A))
+        pol.action_net.weight.mul_(20.0)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    obs = torch.randn(n, D, device="cuda", generator=g) * 0.7
+    with torch.no_grad():
+        mean = pol.action_net(pol.mlp_extractor.policy_net(obs))
+    actions = mean + torch.exp(pol.log_std.detach()) * torch.randn(n, A, device="cuda", generator=g)
+    with torch.no_grad():
+        _, logp, _ = pol.evaluate_actions(obs, actions)
+    old_logp = logp + 0.15 * torch.randn(n, device="cuda", generator=g)
+    adv = torch.randn(n, device="cuda", generator=g) * 3.0 + 0.5
+    ret = torch.randn(n, device="cuda", generator=g) * 2.0
+    return pol, (obs.contiguous(), actions.contiguous(), old_logp.contiguous(), adv, ret)
+
+
+@pytest.mark.parametrize("D,A,n", SHAPES)
+def test_mlp_step_approx_kl_matches_fp64_and_the_plain_entry_point_bit_for_bit(D, A, n):
+    pol, (obs, actions, old_logp, adv, ret) = _autograd_problem(D, A, n)
+    lib = L.load()
+    ws = torch.empty(lib.amenv_ppo_mlp_workspace_bytes() // 8 + 2, dtype=torch.float64, device="cuda")
+    outs = []
+    for ctl in (None, _ctl()):
+        grad, stats = torch.zeros_like(pol.flat_param), torch.full((6,), 777.0, device="cuda")
+        args = (ptr(pol.flat_param.detach()), D, A, ptr(obs), ptr(actions), ptr(old_logp), ptr(adv), ptr(ret), None, n, 0.2, 5e-4, 0.5, 1, ptr(grad), ptr(stats), ptr(ws))
+        rc = lib.amenv_ppo_mlp_step(*args, None) if ctl is None else lib.amenv_ppo_mlp_step_ctl(*args, ptr(ctl), None)
+        assert rc == 0
+        outs.append((grad, stats, ctl))
+    (g0, s0, _), (g1, s1, ctl) = outs
+    assert torch.equal(g0, g1) and torch.equal(s0[:4], s1[:4]) and float(g0.abs().max()) > 0
+    assert s0[4:].tolist() == [777.0, 777.0] == s1[4:].tolist()
+    ref = _kl64(pol, obs, actions, old_logp)
+    c = _read(ctl)
+    kl = c.kl_last
+    print(f"mlp step approx_kl {kl:.9g} fp64 {ref:.9g} rel {abs(kl - ref) / abs(ref):.3g}")
+    assert 5e-3 < ref < 0.1
+    assert abs(kl - ref) <= 2e-4 * abs(ref) + 1e-6
+    assert (c.evaluated, c.applied, c.stop, c.stop_seen) == (1, 0, 0, 0) and c.kl_last == c.kl_sum and list(c.sum)[:4] == s1[:4].tolist()
+
+
+# ---- the gate ------------------------------------------------------------------------------------------------------------------------
+LR_GATE = 3e-3      # large enough that approx_kl grows from minibatch to minibatch
+
+
+def _rollout_problem(D, A, n, seed=1):
+    """Rollout-shaped data: the old log-probs are the policy's own, so approx_kl starts at 0 and grows with the update."""
+    torch.manual_seed(3)
+    pol = ActorCritic(D, A).cuda().flatten_()
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    obs = torch.randn(n, D, device="cuda", generator=g) * 0.7
+    with torch.no_grad():
+        actions = (pol.actor(obs) + torch.randn(n, A, device="cuda", generator=g)).contiguous()
+        _, old_logp, _ = pol.evaluate_actions(obs, actions)
+    adv = torch.randn(n, device="cuda", generator=g) * 3.0 + 0.5
+    ret = torch.randn(n, device="cuda", generator=g) * 2.0
+    opt = torch.optim.Adam([pol.flat_param.requires_grad_(True)], lr=LR_GATE, eps=1e-5, capturable=True)
+    pol.flat_param.grad = pol.flat_grad
+    return pol, opt, (obs, actions, old_logp.contiguous(), adv, ret)
+
+
+def _perms(n, mb, epochs, seed=11):
+    gen = torch.Generator(device="cuda").manual_seed(seed)     # ppo_update draws its permutations the same way
+    return [p[s:s + mb] for p in (torch.randperm(n, device="cuda", generator=gen) for _ in range(epochs)) for s in range(0, n, mb)]
+
+
+def _adam_state(opt):
+    st = opt.state[opt.param_groups[0]["params"][0]]
+    return st["exp_avg"].clone(), st["exp_avg_sq"].clone(), st["step"].clone()
+
+
+def _trip_point(kls):
+    """Minibatch j of the second epoch whose approx_kl tops every earlier one by >= 1.2x; the limit is the geometric mean of the two."""
+    for j in range(4, 8):
+        top = max(kls[:j])
+        if top > 0 and kls[j] >= 1.2 * top:
+            return j, math.sqrt(kls[j] * top)
+    raise AssertionError(f"test data: no minibatch of the second epoch tops the earlier ones by 1.2x: {kls}")
+
+
+def _ungated_run(D, A, mb, fused=True):
+    """12 minibatch steps with the gate open; per step: (grad, stats) after the loss, (param, moments, step) BEFORE its Adam step."""
+    pol, opt, data = _rollout_problem(D, A, 4 * mb)
+    step = MinibatchStep(pol, opt, use_graph=False, fused_mlp=fused)
+    assert step.fused_mlp == fused and step.fused_adam == fused and not step.device_gate
+    trace = []
+    for idx in _perms(4 * mb, mb, 3):
+        before = (pol.flat_param.detach().clone(),) + (_adam_state(opt) if opt.state else (None, None, None))
+        if fused:
+            step._forward_backward_mlp(*data, idx)
+        else:
+            step._forward_backward(*[t[idx].contiguous() for t in data])
+        trace.append((pol.flat_grad.clone(), torch.cat([step.stats, step.kl]), before))
+        step._apply()
+    kls = [float(t[1][5]) for t in trace]
+    return trace, kls
+
+
+@pytest.mark.parametrize("D,A,mb", SHAPES)
+def test_device_gate_stops_exactly_where_the_limit_is_crossed(D, A, mb):
+    trace, kls = _ungated_run(D, A, mb)
+    j, limit = _trip_point(kls)
+    print(f"approx_kl per minibatch {['%.4g' % k for k in kls]} -> j = {j}, 1.5 target_kl = {limit:.5g}")
+    g_j, s_j, (p_j, m_j, v_j, t_j) = trace[j]
+    runs = []
+    for _ in range(2):
+        pol, opt, data = _rollout_problem(D, A, 4 * mb)
+        step = MinibatchStep(pol, opt, use_graph=False, target_kl=limit / 1.5)
+        assert step.device_gate
+        step.arm()
+        for idx in _perms(4 * mb, mb, 3):
+            step.indexed(*data, idx)                       # the host keeps launching: no synchronisation, no look at the block
+        c = _read(step._ctl)
+        assert (c.evaluated, c.applied, c.stop) == (j + 1, j, 1) and c.kl_last == np.float32(kls[j]) and c.kl_limit == np.float32(limit)
+        assert c.kl_sum == pytest.approx(sum(kls[:j + 1]), rel=1e-5)
+        m, v, t = _adam_state(opt)
+        assert torch.equal(pol.flat_param.detach(), p_j) and torch.equal(m, m_j) and torch.equal(v, v_j) and float(t) == float(t_j) == j
+        # gradient and scalars are minibatch j's ([4], the gradient norm, is still that of Adam step j - 1: step j never ran)
+        assert torch.equal(pol.flat_grad, g_j) and torch.equal(torch.cat([step.stats, step.kl]), s_j)
+        assert int(step._adam_ticket) == 0
+        runs.append((pol.flat_param.detach().clone(), step._ctl.clone()))
+    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+
+
+def test_gate_off_is_todays_update_bit_for_bit():
+    D, A, mb = 29, 7, 1000
+    res = []
+    for mode in ("today", "none", "huge"):
+        pol, opt, data = _rollout_problem(D, A, 4 * mb)
+        step = None if mode == "today" else MinibatchStep(pol, opt, use_graph=False, target_kl=None if mode == "none" else 1e9)
+        rec = ppo_update(pol, opt, *data, batch_size=mb, n_epochs=3, generator=torch.Generator(device="cuda").manual_seed(11), step=step)
+        res.append((pol.flat_param.detach().clone(), rec))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][0], res[2][0])
+    assert res[0][1] == res[1][1] and res[2][1]["n_updates"] == 12 and res[2][1]["kl_early_stop"] == 0 and res[0][1]["n_updates"] == 12
+    # the same 12 minibatch steps through amenv_ppo_mlp_step / amenv_ppo_adam_step themselves: the plain entry points, which launch the
+    # kernels' plain forms (what an update launched before the control block existed)
+    pol, opt, data = _rollout_problem(D, A, 4 * mb)
+    lib, prm = L.load(), pol.flat_param.detach()
+    k = prm.numel()
+    grad, m, v, stp = torch.zeros(k, device="cuda"), torch.zeros(k, device="cuda"), torch.zeros(k, device="cuda"), torch.zeros((), device="cuda")
+    stats, ticket = torch.zeros(5, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    hyper = torch.tensor([LR_GATE, 0.9, 0.999, 1e-5, 0.5, 1.0], device="cuda")          # MinibatchStep's defaults and the optimiser's
+    ws = torch.empty(lib.amenv_ppo_mlp_workspace_bytes() // 8 + 2, dtype=torch.float64, device="cuda")
+    for idx in _perms(4 * mb, mb, 3):
+        assert lib.amenv_ppo_mlp_step(ptr(prm), D, A, *[ptr(t) for t in data], ptr(idx), mb, 0.2, 5e-4, 0.5, 1, ptr(grad), ptr(stats), ptr(ws), None) == 0
+        assert lib.amenv_ppo_adam_step(ptr(prm), ptr(grad), ptr(m), ptr(v), ptr(stp), k, ptr(hyper), C.c_void_p(stats.data_ptr() + 16), ptr(ticket), None) == 0
+    assert float(stp) == 12.0 and torch.equal(prm, res[0][0])
+
+
+def test_fused_and_torch_paths_stop_at_the_same_minibatch():
+    D, A, mb = 20, 4, 1000
+    _, kls_f = _ungated_run(D, A, mb, fused=True)
+    _, kls_t = _ungated_run(D, A, mb, fused=False)
+    j, limit = _trip_point(kls_f)
+    assert _trip_point(kls_t)[0] == j and max(kls_t[:j]) * 1.1 < limit < kls_t[j] / 1.1     # the same margin holds on the torch path
+    res = []
+    for fused in (False, True):
+        pol, opt, data = _rollout_problem(D, A, 4 * mb)
+        step = MinibatchStep(pol, opt, use_graph=False, fused_mlp=fused, target_kl=limit / 1.5)
+        assert step.device_gate == fused
+        rec = ppo_update(pol, opt, *data, batch_size=mb, n_epochs=3, generator=torch.Generator(device="cuda").manual_seed(11), step=step)
+        res.append((pol.flat_param.detach().clone(), rec, float(_adam_state(opt)[2])))
+    (p0, r0, t0), (p1, r1, t1) = res
+    assert r0["n_updates"] == r1["n_updates"] == j == t0 == t1 and r0["kl_early_stop"] == r1["kl_early_stop"] == 1
+    assert float((p0 - p1).abs().max()) < 0.05 * j * LR_GATE, float((p0 - p1).abs().max())
+    for k in r0:
+        assert abs(r0[k] - r1[k]) <= 2e-3 * max(abs(r0[k]), 1e-3), (k, r0[k], r1[k])
+    assert r1["approx_kl"] == pytest.approx(np.mean(kls_f[:j + 1]), rel=1e-4)                # the mean over the evaluated minibatches
+
+
+# ---- schedules and the whole loop -----------------------------------------------------------------------------------------------------
+def _fixture_policy(device):
+    z = np.load(os.path.join(GOLD, "policy_2300000.npz"))
+    return ActorCritic.from_sb3({k: torch.from_numpy(z[k]) for k in z.files if not k.startswith("_")}, device=device)
+
+
+def test_schedule_takes_effect_on_the_captured_graph_path():
+    """Two updates on one rollout with learning_rate and clip_range halved between them, captured graphs against eager: a capture bakes
+    clip_range in (the learning rate of the fused Adam step is re-uploaded to its device buffer), so the change drops the graphs and the
+    next full minibatch captures again.  Tolerances: those of
+    test_graph_captured_update_equals_eager_update (a stale graph would be off by ~16 steps x 1e-4)."""
+    out = []
+    for use_graph in (False, True):
+        env = amd.GpuWaypointEnv(1024, seed=8)
+        algo = PPO(env, policy=_fixture_policy(env.device), n_steps=64, batch_size=8192, n_epochs=2, seed=4, use_graph=use_graph,
+                   learning_rate=lambda p: 2e-4 * p, clip_range=lambda p: 0.2 * p)
+        captures = []
+        capture = algo._step._capture
+        algo._step._capture = lambda mb: (captures.append(1), capture(mb))[1]
+        algo.collect_rollouts()
+        r1 = algo.train()
+        algo._progress = 0.5
+        r2 = algo.train()
+        assert (r1["learning_rate"], r1["clip_range"], r2["learning_rate"], r2["clip_range"]) == (2e-4, 0.2, 1e-4, 0.1)
+        out.append((algo.policy.flat_param.detach().clone(), r2, len(captures), algo._step._graphs is not None))
+        env.close()
+    (p0, r0, c0, g0), (p1, r1, c1, g1) = out
+    assert (c0, g0) == (0, False) and (c1, g1) == (2, True)
+    assert float((p0 - p1).abs().max()) < 1e-5
+    assert abs(r0["value_loss"] - r1["value_loss"]) <= 1e-4 * abs(r0["value_loss"]) and abs(r0["grad_norm"] - r1["grad_norm"]) <= 1e-3 * r0["grad_norm"]
+    assert abs(r0["approx_kl"] - r1["approx_kl"]) <= 2e-3 * max(abs(r0["approx_kl"]), 1e-3)
+
+
+def test_learn_with_target_kl_and_a_linear_learning_rate():
+    env = amd.GpuWaypointEnv(256, seed=2)
+    algo = PPO(env, n_steps=64, batch_size=4096, n_epochs=4, seed=1, target_kl=0.01, learning_rate=lambda p: 1e-3 * p, fused_rollout=True)
+    assert algo._step.device_gate and not algo._step.use_graph
+    algo.learn(3 * 64 * 256)
+    assert len(algo.log) == 3
+    for rec in algo.log:
+        assert all(isinstance(v, (int, float)) and math.isfinite(v) for v in rec.values()), rec
+        assert rec["kl_early_stop"] in (0, 1) and rec["approx_kl"] >= 0.0 and rec["std"] > 0 and rec["explained_variance"] <= 1.0
+    ups, lrs = [r["n_updates"] for r in algo.log], [r["learning_rate"] for r in algo.log]
+    assert ups[0] >= 1 and ups[0] <= ups[1] <= ups[2] <= 3 * 16 and lrs[0] > lrs[1] > lrs[2] >= 0.0
+    assert lrs == pytest.approx([1e-3 * 2 / 3, 1e-3 / 3, 0.0], abs=1e-12)
+    env.close()
