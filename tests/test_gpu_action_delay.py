@@ -5,7 +5,6 @@ one-launch rollouts and closed loops replay bit for bit through amenv_step, dela
 reference checkpoint at 10 and 40 ms, PPO."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
@@ -14,13 +13,13 @@ import torch
 import rl_aerial_manipulator_amd as amd
 from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
-from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
-from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic, evaluate_policy
+from rl_aerial_manipulator_amd.ppo import PPO, evaluate_policy
 from tests import delay_ref
+from tests import switch_harness as H
 
 pytestmark = pytest.mark.gpu
+SW = H.ACTION_DELAY
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 N, GID0 = 200, 1000                      # three full tiles + 8 ragged lanes; a non-zero env_id_offset
 FULL = amd.ActionDelay(0, 8)
 DR = amd.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.7, 1.3), thrust=(0.9, 1.1))
@@ -31,63 +30,12 @@ HOVER = torch.tensor([1.0, 0.0, 0.0, 0.0])
 
 
 def _env(vehicle="quad", task="v2", nwp=1, n=N, seed=4, **kw):
-    kw.setdefault("max_episode_steps", 25)
     kw.setdefault("env_id_offset", GID0)
-    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
+    return H.make_env(vehicle, task, nwp, n, seed, **kw)
 
 
-def _actions(T, n, seed, dev, wide=False):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    if wide:   # near +-1 (and 0 / 2 on the collective): consecutive rows differ strongly
-        a = torch.rand(T, n, 4, generator=g)
-        a = torch.where(a < 0.5, -1.0 + 0.2 * a, 0.8 + 0.4 * a)
-        a[..., 0] = torch.where(a[..., 0] < 0, 1.5 + a[..., 0], a[..., 0] + 0.7)
-    else:
-        a = torch.rand(T, n, 4, generator=g) * torch.tensor([0.6, 0.4, 0.4, 0.4]) + torch.tensor([0.7, -0.2, -0.2, -0.2])
-    return a.to(dev).contiguous()
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
-
-
-def _buffers(T, n, od, dev):
-    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
-                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
-
-
-def _step_all(env, a):
-    o, r, d, i = env.step(a)
-    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
-
-
-def _same_step(ra, da, rb, db, t):
-    for x, y in zip(ra[:4], rb[:4]):
-        assert torch.equal(x, y), t
-    for x, y in zip(ra[4:], rb[4:]):
-        assert torch.equal(x[da], y[db]), t
-
-
-def _same_state(a, b):
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    return torch.equal(fa, fb) and torch.equal(ia, ib)
-
-
-def _history(env, z):
-    """The test's own history of a handle whose delay was just turned on or that was just reset."""
-    ep = env.get_state()[1][L.I_EPISODE].cpu().numpy()
-    return delay_ref.History(env.cfg.seed, env.cfg.env_id_offset, ep, z.min_steps, z.max_steps)
-
-
-def _push(hist, env, given, info):
-    reset = (info.cpu().numpy().view(np.uint32) & delay_ref.WAS_RESET) != 0
-    hist.push(given.cpu().numpy(), reset, env.get_state()[1][L.I_EPISODE].cpu().numpy())
-    return reset
+_actions, _step_all, _same_step, _same_state = H.actions, H.step_all, H.same_step, H.same_state
+_history, _push = H.delay_history, H.push_history
 
 
 def _published(env):
@@ -101,20 +49,7 @@ def test_delay_set_and_cleared_is_bit_invisible_step_and_rollout(vehicle, task, 
     T = 40
     a = _env(vehicle, task, nwp, kernel=kernel)
     b = _env(vehicle, task, nwp, kernel=kernel)
-    name = b.kernel_name
-    b.set_action_delay(FULL)
-    assert b.kernel_name == name + " +delay" and b.action_delay is FULL
-    b.set_action_delay(None)
-    assert b.kernel_name == name == a.kernel_name and b.action_delay is None
-    assert torch.equal(a.reset(), b.reset())
-    acts = _actions(T, N, 1, a.device)
-    for t in range(T):
-        ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
-        _same_step(ra, da, rb, db, t)
-    ra, rb = a.rollout(acts), b.rollout(acts)
-    for k in ra:
-        assert torch.equal(ra[k], rb[k]), k
-    assert _same_state(a, b) and a.stats() == b.stats()
+    H.check_set_and_cleared_step_and_rollout(SW, FULL, a, b, _actions(T, N, 1, a.device))
     a.close(); b.close()
 
 
@@ -123,19 +58,7 @@ def test_delay_set_and_cleared_is_bit_invisible_closed_loop():
     n, T = 4096, 48
     a = _env(n=n)
     b = _env(n=n, action_delay=FULL)
-    b.set_action_delay(None)
-    assert a.kernel_name == b.kernel_name
-    a.reset(); b.reset()
-    od, dev = a.obs_dim, a.device
-    pol = _policy(od)
-    ba, bb = _buffers(T, n, od, dev), _buffers(T, n, od, dev)
-    ia, ib = (torch.zeros(T, n, dtype=torch.int32, device=dev) for _ in range(2))
-    a.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ia, **ba)
-    b.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ib, **bb)
-    torch.cuda.synchronize()
-    for k in ba:
-        assert torch.equal(ba[k], bb[k]), k
-    assert torch.equal(ia, ib) and int(ba["dones"].sum()) > 0 and _same_state(a, b)
+    H.check_set_and_cleared_closed_loop(SW, a, b, T)
     a.close(); b.close()
 
 
@@ -163,7 +86,7 @@ def test_delayed_handle_equals_a_plain_twin_given_the_applied_rows(vehicle, task
         differed += int((applied != acts[t]).any(dim=1).sum())
         ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, applied)
         _same_step(ra, da, rb, db, t)
-        assert _same_state(a, b), t
+        _same_state(a, b, t)
         ended += int(_push(hist, a, acts[t], ra[3]).sum())
     assert a.stats() == b.stats() and ended > N
     assert differed == 0 if z.max_steps == 0 else differed > T * N // 2
@@ -266,15 +189,9 @@ def test_delayed_rollout_equals_steps(vehicle, task, nwp, extra):
     T = 64
     a = _env(vehicle, task, nwp, action_delay=FULL, **extra)
     b = _env(vehicle, task, nwp, action_delay=FULL, **extra)
-    a.reset(); b.reset()
-    acts = _actions(T, N, 2, a.device, wide=True)
-    ro = a.rollout(acts)
-    for t in range(T):
-        o, r, d, i = b.step(acts[t])
-        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
-    assert int(ro["done"].sum()) > N and _same_state(a, b) and a.stats() == b.stats()
-    (da, ra), (db, rb) = a.action_delay_state(), b.action_delay_state()
-    assert torch.equal(da, db) and torch.equal(ra, rb) and not torch.equal(ra, HOVER.to(ra.device).expand_as(ra))
+    H.check_rollout_equals_steps(a, b, _actions(T, N, 2, a.device, wide=True), min_ended=N, side=(SW,))
+    ra = a.action_delay_state()[1]
+    assert not torch.equal(ra, HOVER.to(ra.device).expand_as(ra))
     a.close(); b.close()
 
 
@@ -290,57 +207,37 @@ def test_delayed_closed_loop_replays_bit_for_bit(vehicle, task, nwp, n, norm, ex
     env = _env(vehicle, task, nwp, n=n, action_delay=FULL, **extra)
     ref = _env(vehicle, task, nwp, n=n, kernel="lane", action_delay=amd.ActionDelay(1), **extra)
     assert env.kernel_name.endswith(" +delay")
-    od, dev = env.obs_dim, env.device
-    pol = _policy(od)
-    env.reset(); ref.reset()
-    warm = _actions(3, n, 8, dev, wide=True)
-    for t in range(3):                                   # a start state with rows in the history
-        env.step(warm[t])
-    ref.set_action_delay(FULL)                           # (on -> on: keeps ref's own d and rows until the restore below)
-    ref.set_state(*env.get_state())
-    ref.set_action_delay_state(*env.action_delay_state())
-    if "rotor_lag" in extra:
-        ref.set_rotor_state(env.rotor_state())
+    dev = env.device
     plain = hist = None
-    if twin:
-        plain = _env(vehicle, task, nwp, n=n, kernel="lane", **extra)
-        plain.reset(); plain.set_state(*env.get_state())
-        hist = _history(env, FULL)
-        hist.d, hist.recent = (x.copy() for x in _published(env))
-    kw = {}
-    if norm:
-        nrm = ObsNormalizer(od)
-        nrm.update(env.observe())
-        entry = ObsNormalizer(od); entry.set(*nrm.get())
-        kw = dict(obs_normalizer=nrm)
-    b = _buffers(T, n, od, dev)
-    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
-    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b, **kw)
-    torch.cuda.synchronize()
-    tr = (lambda x: entry.normalize(x)) if norm else (lambda x: x)
-    lo, hi = pol.action_low, pol.action_high
-    for t in range(T):
-        given = torch.max(torch.min(b["actions"][t], hi), lo)
-        o, r, d, i = ref.step(given)
-        assert torch.equal(tr(o), b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
-        dn = d.bool()
-        if bool(dn.any()):
-            assert torch.equal(tr(ref.terminal_obs[dn]), tobs[t][dn]), t
+
+    def start(env, ref):
+        nonlocal plain, hist
+        warm = _actions(3, n, 8, dev, wide=True)
+        for t in range(3):                               # a start state with rows in the history
+            env.step(warm[t])
+        ref.set_action_delay(FULL)                       # (on -> on: keeps ref's own d and rows until the restore below)
+        ref.set_state(*env.get_state())
+        ref.set_action_delay_state(*env.action_delay_state())
+        if "rotor_lag" in extra:
+            ref.set_rotor_state(env.rotor_state())
         if twin:
-            _, rp, dp, _ = plain.step(torch.from_numpy(hist.applied(given.cpu().numpy())).to(dev))
-            assert torch.equal(rp, b["rewards"][t]) and torch.equal(dp, b["dones"][t]), t
-            _push(hist, ref, given, i)
-    assert _same_state(env, ref) and env.stats()["episodes"] > 0
-    (da, ra), (db, rb) = env.action_delay_state(), ref.action_delay_state()
-    assert torch.equal(da, db) and torch.equal(ra, rb)
+            plain = _env(vehicle, task, nwp, n=n, kernel="lane", **extra)
+            plain.reset(); plain.set_state(*env.get_state())
+            hist = _history(env, FULL)
+            hist.d, hist.recent = (x.copy() for x in _published(env))
+
+    def plain_twin(t, given, o, r, d, i):
+        _, rp, dp, _ = plain.step(torch.from_numpy(hist.applied(given.cpu().numpy())).to(dev))
+        assert torch.equal(rp, r) and torch.equal(dp, d), t
+        _push(hist, ref, given, i)
+
+    run = H.check_closed_loop_replays(env, ref, T, norm=norm, side=(SW,), prepare=start, each_step=plain_twin if twin else None, totals=False)
+    assert env.stats()["episodes"] > 0
     if twin:
-        assert np.array_equal(da.cpu().numpy(), hist.d) and np.array_equal(ra.cpu().numpy(), hist.recent)
-    assert int(b["dones"].sum()) > 0
-    env.close(); ref.close()
-    if twin:
+        da, ra = _published(env)
+        assert np.array_equal(da, hist.d) and np.array_equal(ra, hist.recent)
         plain.close()
-    if norm:
-        nrm.close(); entry.close()
+    run.close()
 
 
 # ---- 7. without auto-reset ----------------------------------------------------------------------------------------------------------
@@ -380,9 +277,8 @@ def test_restore_into_a_fresh_handle_and_set_state_alone():
     for t in range(30, 50):
         ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
         _same_step(ra, da, rb, db, t)
-    assert _same_state(a, b)
-    (da_, ra_), (db_, rb_) = a.action_delay_state(), b.action_delay_state()
-    assert torch.equal(da_, db_) and torch.equal(ra_, rb_)
+    _same_state(a, b)
+    SW.same_side_state(a, b)
     # the setter clamps d to 0..8
     b.set_action_delay_state(torch.full((N,), 99, dtype=torch.int32), recent)
     assert bool((b.action_delay_state()[0] == 8).all())
@@ -396,17 +292,7 @@ def test_two_shards_equal_one_handle():
     whole = _env("hexa", "v2", 1, n=n, seed=13, max_episode_steps=20, action_delay=FULL)
     h0 = _env("hexa", "v2", 1, n=cut, seed=13, max_episode_steps=20, action_delay=FULL)
     h1 = _env("hexa", "v2", 1, n=n - cut, seed=13, max_episode_steps=20, action_delay=FULL, env_id_offset=GID0 + cut)
-    ow = whole.reset().clone(); o0 = h0.reset().clone(); o1 = h1.reset().clone()
-    assert torch.equal(ow, torch.cat([o0, o1]))
-    acts = _actions(T, n, 4, whole.device, wide=True)
-    for t in range(T):
-        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
-        p0 = [x.clone() for x in h0.step(acts[t, :cut])]
-        p1 = [x.clone() for x in h1.step(acts[t, cut:])]
-        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
-            assert torch.equal(x, torch.cat([y, z])), t
-    for x, y, z in zip(whole.action_delay_state(), h0.action_delay_state(), h1.action_delay_state()):
-        assert torch.equal(x, torch.cat([y, z]))
+    H.check_two_shards(whole, h0, h1, cut, _actions(T, n, 4, whole.device, wide=True), side=(SW,))
     for e in (whole, h0, h1):
         e.close()
 
@@ -418,8 +304,7 @@ def test_reference_checkpoint_under_delay(d):
     92 of 95, 96.8 %; a sample of 95 has about 2 points of spread, the bar sits 9 points under).  40 ms: success < 10 %, crashes the
     majority of endings (the delayed oracle: 1 of 512, 511 crashed)."""
     env = amd.GpuWaypointEnv(1024, seed=99, action_delay=amd.ActionDelay(d))
-    z = np.load(os.path.join(GOLD, "policy_2300000.npz"))
-    pol = ActorCritic.from_sb3({k: torch.from_numpy(z[k]) for k in z.files if not k.startswith("_")}, device=env.device)
+    pol = H.fixture_policy(env.device)
     env.reset()
     env.stats(reset=True)
     evaluate_policy(pol, env, n_eval_episodes=1024)
@@ -434,64 +319,28 @@ def test_reference_checkpoint_under_delay(d):
 
 
 # ---- 10. refusals -----------------------------------------------------------------------------------------------------------------
-def _octo_config(n):
-    """A synthetic 8-rotor vehicle (the runtime-rotor-count kernels): rotors on a 0.3 m circle, alternating spin, pseudo-inverse allocation."""
-    cfg = L.default_config("hexa", n)
-    v = cfg.vehicle
-    v.n_rotors, v.mass = 8, 3.0
-    ang = np.arange(8) * np.pi / 4
-    mix = np.stack([np.ones(8), 0.3 * np.sin(ang), -0.3 * np.cos(ang), 0.02 * (-1.0) ** np.arange(8)])
-    alloc = np.linalg.pinv(mix)
-    for r in range(8):
-        for j in range(4):
-            v.alloc[r * 4 + j] = alloc[r, j]
-            v.mix[j * 8 + r] = mix[j, r]
-        v.t_min[r], v.t_max[r] = 0.0, 2.0 * v.mass * v.g / 8
-    cfg.env_id_offset = GID0
-    return cfg
-
-
 def test_delay_refusals_leave_everything_untouched():
-    def refused(env, twin, call):
-        env.reset(); twin.reset()
-        with pytest.raises(L.AmenvError):
-            call(env)
-        assert "+delay" not in env.kernel_name and env.action_delay is None and env.kernel_name == env.lib.amenv_kernel_name(env._h).decode()
-        a = _actions(1, env.num_envs, 3, env.device)[0]
-        if env.act_dim != 4:
-            a = torch.cat([a, torch.zeros(env.num_envs, env.act_dim - 4, device=env.device)], dim=1).contiguous()
-        for x, y in zip(env.step(a), twin.step(a)):
-            assert torch.equal(x, y)
-        assert _same_state(env, twin)
-        env.close(); twin.close()
-
-    on = lambda e: e.set_action_delay(FULL)   # noqa: E731
-    refused(_env("hexa_arm", n=64), _env("hexa_arm", n=64), on)
+    H.check_refused(SW, lambda: _env("hexa_arm", n=64), FULL)
     with pytest.raises(L.AmenvError):
         _env("hexa_arm", n=64, n_joints=2, action_delay=FULL)
-    refused(_env(n=64, dtype="f64"), _env(n=64, dtype="f64"), on)
-    refused(_env(n=64, kernel="team"), _env(n=64, kernel="team"), on)
-    refused(amd.GpuWaypointEnv(64, config=_octo_config(64)), amd.GpuWaypointEnv(64, config=_octo_config(64)), on)
-    # bad struct_size / ranges through ctypes; the delay state while off
-    env, twin = _env(n=64), _env(n=64)
-    env.reset(); twin.reset()
-    bad = FULL._as_c()
-    bad.struct_size = 8
-    assert env.lib.amenv_set_action_delay(env._h, C.byref(bad)) == -1 and b"struct_size" in env.lib.amenv_last_error(env._h)
-    for lo, hi in [(3, 2), (0, 9), (-1, 4)]:
-        c = FULL._as_c()
-        c.min_steps, c.max_steps = lo, hi
-        assert env.lib.amenv_set_action_delay(env._h, C.byref(c)) == -1, (lo, hi)
-    with pytest.raises(L.AmenvError, match="off"):
-        env.action_delay_state()
-    with pytest.raises(L.AmenvError, match="off"):
-        env.set_action_delay_state(torch.zeros(64, dtype=torch.int32), torch.zeros(64, 8, 4))
-    assert "+delay" not in env.kernel_name and env.kernel_name == env.lib.amenv_kernel_name(env._h).decode()
-    a = _actions(1, 64, 3, env.device)[0]
-    for x, y in zip(env.step(a), twin.step(a)):
-        assert torch.equal(x, y)
-    assert _same_state(env, twin)
-    env.close(); twin.close()
+    H.check_refused(SW, lambda: _env(n=64, dtype="f64"), FULL)
+    H.check_refused(SW, lambda: _env(n=64, kernel="team"), FULL)
+    H.check_refused(SW, lambda: amd.GpuWaypointEnv(64, config=H.octo_config(64, GID0)), FULL)
+
+    def bad_struct_and_off(env):     # bad struct_size / ranges through ctypes; the delay state while off
+        bad = FULL._as_c()
+        bad.struct_size = 8
+        assert env.lib.amenv_set_action_delay(env._h, C.byref(bad)) == -1 and b"struct_size" in env.lib.amenv_last_error(env._h)
+        for lo, hi in [(3, 2), (0, 9), (-1, 4)]:
+            c = FULL._as_c()
+            c.min_steps, c.max_steps = lo, hi
+            assert env.lib.amenv_set_action_delay(env._h, C.byref(c)) == -1, (lo, hi)
+        with pytest.raises(L.AmenvError, match="off"):
+            env.action_delay_state()
+        with pytest.raises(L.AmenvError, match="off"):
+            env.set_action_delay_state(torch.zeros(64, dtype=torch.int32), torch.zeros(64, 8, 4))
+
+    H.check_refused(SW, lambda: _env(n=64), bad_struct_and_off)
 
 
 # ---- 11. PPO ----------------------------------------------------------------------------------------------------------------------

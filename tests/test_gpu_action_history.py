@@ -4,6 +4,7 @@ history the test keeps itself with tests/delay_ref.py and tests/history_ref.py (
 amenv_step; toggling, refusals, sharding, restore; the MLP kernels at the four new shapes under the project's own gates; one fp32 case
 against the fp64 oracle."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -15,10 +16,12 @@ from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
 from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic, MinibatchStep
-from tests import delay_ref, history_ref
+from tests import history_ref
+from tests import switch_harness as SH     # (H is the number of history rows in this file)
 from tests.policy_ref import VALUE_BIAS, forward_bf16_model, forward_fp64, nondegenerate_policy, philox_normals_fp64
 
 pytestmark = pytest.mark.gpu
+SW = SH.ACTION_HISTORY
 
 N, GID0 = 200, 1000                      # three full tiles + 8 ragged lanes; a non-zero env_id_offset
 FULL = amd.ActionDelay(0, 8)
@@ -31,71 +34,14 @@ HOVER = np.array([1.0, 0.0, 0.0, 0.0], np.float32)
 
 
 def _env(vehicle="quad", task="v2", nwp=1, n=N, seed=4, **kw):
-    kw.setdefault("max_episode_steps", 25)
     kw.setdefault("env_id_offset", GID0)
-    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
+    return SH.make_env(vehicle, task, nwp, n, seed, **kw)
 
 
-def _actions(T, n, seed, dev):
-    """The delay test's `wide` generator: near +-1 (and 0 / 2 on the collective), so consecutive rows differ strongly."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    a = torch.rand(T, n, 4, generator=g)
-    a = torch.where(a < 0.5, -1.0 + 0.2 * a, 0.8 + 0.4 * a)
-    a[..., 0] = torch.where(a[..., 0] < 0, 1.5 + a[..., 0], a[..., 0] + 0.7)
-    return a.to(dev).contiguous()
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
-
-
-def _nan_buffers(T, n, od, dev):
-    """Every output filled with NaN (dones with 0xFF) first: a row the kernel does not write stays visible."""
-    nan = float("nan")
-    return dict(obs=torch.full((T + 1, n, od), nan, device=dev), actions=torch.full((T, n, 4), nan, device=dev), logp=torch.full((T, n), nan, device=dev),
-                values=torch.full((T, n), nan, device=dev), rewards=torch.full((T, n), nan, device=dev),
-                dones=torch.full((T, n), 0xFF, dtype=torch.uint8, device=dev))
-
-
-def _all_written(b):
-    for k, v in b.items():
-        if k == "dones":
-            assert bool(((v == 0) | (v == 1)).all()), "a dones entry was not written"
-        else:
-            assert not bool(torch.isnan(v).any()), f"a row of {k} was not written"
-
-
-def _step_all(env, a):
-    o, r, d, i = env.step(a)
-    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
-
-
-def _same_state(a, b):
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    return torch.equal(fa, fb) and torch.equal(ia, ib)
-
-
-def _same_delay_state(a, b):
-    (da, ra), (db, rb) = a.action_delay_state(), b.action_delay_state()
-    return torch.equal(da, db) and torch.equal(ra, rb)
-
-
-def _history(env, z):
-    """The test's own history of a handle that was just reset (z None: the history alone, range (0, 0))."""
-    ep = env.get_state()[1][L.I_EPISODE].cpu().numpy()
-    lo, hi = (0, 0) if z is None else (z.min_steps, z.max_steps)
-    return delay_ref.History(env.cfg.seed, env.cfg.env_id_offset, ep, lo, hi)
-
-
-def _push(hist, env, given, info):
-    reset = (info.cpu().numpy().view(np.uint32) & delay_ref.WAS_RESET) != 0
-    hist.push(given.cpu().numpy(), reset, env.get_state()[1][L.I_EPISODE].cpu().numpy())
-    return reset
+_actions = functools.partial(SH.actions, wide=True)      # near +-1 (and 0 / 2 on the collective), so consecutive rows differ strongly
+_nan_buffers = functools.partial(SH.buffers, fill=float("nan"))
+_step_all, _same_step, _same_state, _same_delay_state = SH.step_all, SH.same_step, SH.same_state, SW.same_side_state
+_history, _push = SH.delay_history, SH.push_history
 
 
 def _t(x, dev):
@@ -126,7 +72,7 @@ def test_history_handle_equals_its_twin_and_the_reference_history(vehicle, task,
         for x, y in zip(ra[1:4], rb[1:4]):
             assert torch.equal(x, y), t
         assert torch.equal(ra[4][da][:, :base], rb[4][db]) and torch.equal(ra[5][da], rb[5][db]) and torch.equal(ra[6][da], rb[6][db]), t
-        assert _same_state(a, b), t
+        _same_state(a, b, t)
         term = history_ref.pushed(ref, acts[t].cpu().numpy(), H)
         reset = _push(ref, a, acts[t], ra[3])
         assert torch.equal(ra[0][:, base:], _t(history_ref.rows(ref, H), dev)), t           # step rows; hover where a new episode started
@@ -136,7 +82,7 @@ def test_history_handle_equals_its_twin_and_the_reference_history(vehicle, task,
         d, recent = a.action_delay_state()
         assert np.array_equal(d.cpu().numpy(), ref.d) and np.array_equal(recent.cpu().numpy().view(np.uint32), ref.recent.view(np.uint32)), t
         if z is not None:
-            assert _same_delay_state(a, b), t
+            _same_delay_state(a, b, t)
         ended += int(reset.sum())
     assert ended > N and a.stats() == b.stats()
     if z is None:
@@ -152,7 +98,8 @@ def test_history_handle_equals_its_twin_and_the_reference_history(vehicle, task,
     assert torch.equal(oa[:, base:][m], _t(np.tile(HOVER, (int(m.sum()), H)), dev)) and torch.equal(oa[:, base:][~m], _t(cur[~m], dev))
     assert not np.array_equal(cur[~m], np.tile(HOVER, (int((~m).sum()), H)))
     ra, da = _step_all(a, acts[T]); rb, db = _step_all(b, acts[T])                            # and both go on alike
-    assert torch.equal(ra[0][:, :base], rb[0]) and torch.equal(ra[1], rb[1]) and _same_state(a, b)
+    assert torch.equal(ra[0][:, :base], rb[0]) and torch.equal(ra[1], rb[1])
+    _same_state(a, b)
     if "rotor_lag" in extra:
         assert torch.equal(a.rotor_state(), b.rotor_state())
     a.close(); b.close()
@@ -164,14 +111,8 @@ def test_history_rollout_equals_steps(vehicle, task, nwp, hist, z):
     T = 30
     a = _env(vehicle, task, nwp, action_delay=z, action_history=hist)
     b = _env(vehicle, task, nwp, action_delay=z, action_history=hist)
-    a.reset(); b.reset()
-    acts = _actions(T, N, 2, a.device)
-    ro = a.rollout(acts)
+    ro = SH.check_rollout_equals_steps(a, b, _actions(T, N, 2, a.device), min_ended=N // 2, side=(SW,))
     assert ro["obs"].shape == (T, N, a.obs_dim)
-    for t in range(T):
-        o, r, d, i = b.step(acts[t])
-        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
-    assert int(ro["done"].sum()) > N // 2 and _same_state(a, b) and a.stats() == b.stats() and _same_delay_state(a, b)
     a.close(); b.close()
 
 
@@ -180,35 +121,26 @@ def _closed_loop_replay(vehicle, task, nwp, n, T, hist, z, steps_max):
     env = _env(vehicle, task, nwp, n=n, action_delay=z, action_history=hist, max_episode_steps=steps_max)
     ref = _env(vehicle, task, nwp, n=n, kernel="lane", action_delay=z, action_history=hist, max_episode_steps=steps_max)
     assert env.kernel_name.endswith(f" +history {hist.rows}")
-    od, dev = env.obs_dim, env.device
-    base = od - 4 * hist.rows
-    pol = _policy(od)
-    env.reset(); ref.reset()
-    warm = _actions(3, n, 8, dev)
-    for t in range(3):                                   # a start state with rows in the history
-        env.step(warm[t])
-    ref.set_state(*env.get_state())
-    ref.set_action_delay_state(*env.action_delay_state())
-    row0 = env.observe()
-    assert torch.equal(row0[:, base:base + 4], warm[2]) or bool(env.done.any())
-    b = _nan_buffers(T, n, od, dev)
-    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
-    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b)
-    torch.cuda.synchronize()
-    _all_written(b)
-    assert torch.equal(b["obs"][0], row0)                # row 0: the current history
-    lo, hi = pol.action_low, pol.action_high
-    for t in range(T):
-        given = torch.max(torch.min(b["actions"][t], hi), lo)
-        o, r, d, i = ref.step(given)
-        assert torch.equal(o, b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
-        dn = d.bool()
-        keep = ~dn
+    base = env.obs_dim - 4 * hist.rows
+    row0 = None
+
+    def start(env, ref):
+        nonlocal row0
+        warm = _actions(3, n, 8, env.device)
+        for t in range(3):                               # a start state with rows in the history
+            env.step(warm[t])
+        ref.set_state(*env.get_state())
+        ref.set_action_delay_state(*env.action_delay_state())
+        row0 = env.observe()
+        assert torch.equal(row0[:, base:base + 4], warm[2]) or bool(env.done.any())
+
+    def given_row(t, given, o, r, d, i):
+        keep = ~d.bool()
         assert torch.equal(o[keep][:, base:base + 4], given[keep]), t          # the clipped sample is the given row
-        if bool(dn.any()):
-            assert torch.equal(ref.terminal_obs[dn], tobs[t][dn]), t
-    assert _same_state(env, ref) and _same_delay_state(env, ref) and int(b["dones"].sum()) > 0
-    env.close(); ref.close()
+
+    run = SH.check_closed_loop_replays(env, ref, T, fill=float("nan"), side=(SW,), prepare=start, each_step=given_row, totals=False)
+    assert torch.equal(run.b["obs"][0], row0)            # row 0: the current history
+    run.close()
 
 
 @pytest.mark.parametrize("z", [None, amd.ActionDelay(0, 2)])
@@ -240,7 +172,7 @@ def test_history_rollout_mlp_vs_bf16_model(task, od):
     b = _nan_buffers(T, n, od, env.device)
     env.rollout_policy(pol.flat_param, T, seed, draw0, **b)
     torch.cuda.synchronize()
-    _all_written(b)
+    SH.all_written(b)
     hist_cols = b["obs"][:T, :, od - 8:]
     assert float(hist_cols.std()) > 0.3                    # the history columns carry the (order-one) actions
     zr = torch.from_numpy(philox_normals_fp64(seed, GID0 + np.arange(n)[None, :], (draw0 + np.arange(T))[:, None], 4)).to(env.device)
@@ -361,68 +293,36 @@ def test_history_set_and_cleared_is_bit_invisible(z):
     assert a.obs_dim == base == int(a.lib.amenv_obs_dim(a._h)) and a.kernel_name == name and a.action_history is None and a.obs.shape == (N, base)
     for t in range(8, 18):
         ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
-        for x, y in zip(ra[:4], rb[:4]):
-            assert torch.equal(x, y), t
-        for x, y in zip(ra[4:], rb[4:]):
-            assert torch.equal(x[da], y[db]), t
-        assert _same_state(a, b), t
+        _same_step(ra, da, rb, db, t)
+        _same_state(a, b, t)
         if z is not None:
-            assert _same_delay_state(a, b), t
+            _same_delay_state(a, b, t)
     assert a.stats() == b.stats()
     a.close(); b.close()
 
 
 # ---- 8. refusals -------------------------------------------------------------------------------------------------------------------
-def _octo_config(n):
-    """A synthetic 8-rotor vehicle (the runtime-rotor-count kernels): rotors on a 0.3 m circle, alternating spin, pseudo-inverse allocation."""
-    cfg = L.default_config("hexa", n)
-    v = cfg.vehicle
-    v.n_rotors, v.mass = 8, 3.0
-    ang = np.arange(8) * np.pi / 4
-    mix = np.stack([np.ones(8), 0.3 * np.sin(ang), -0.3 * np.cos(ang), 0.02 * (-1.0) ** np.arange(8)])
-    alloc = np.linalg.pinv(mix)
-    for r in range(8):
-        for j in range(4):
-            v.alloc[r * 4 + j] = alloc[r, j]
-            v.mix[j * 8 + r] = mix[j, r]
-        v.t_min[r], v.t_max[r] = 0.0, 2.0 * v.mass * v.g / 8
-    cfg.env_id_offset = GID0
-    return cfg
-
-
-def _next_step_alike(env, twin):
-    a = _actions(1, env.num_envs, 3, env.device)[0]
-    if env.act_dim != 4:
-        a = torch.cat([a, torch.zeros(env.num_envs, env.act_dim - 4, device=env.device)], dim=1).contiguous()
-    for x, y in zip(env.step(a), twin.step(a)):
-        assert torch.equal(x, y)
-    assert _same_state(env, twin)
+_wide_row = functools.partial(SH.one_action, rows=_actions)
 
 
 def test_history_refusals_leave_everything_untouched():
-    def refused(env, twin, call):
-        env.reset(); twin.reset()
+    def on(env):
         od = env.obs_dim
         with pytest.raises(L.AmenvError):
-            call(env)
-        assert "+history" not in env.kernel_name and env.action_history is None and env.kernel_name == env.lib.amenv_kernel_name(env._h).decode()
+            env.set_action_history(H2)
         assert env.obs_dim == od == int(env.lib.amenv_obs_dim(env._h))
-        _next_step_alike(env, twin)
-        env.close(); twin.close()
 
-    on = lambda e: e.set_action_history(H2)   # noqa: E731
-    refused(_env("hexa_arm", n=64), _env("hexa_arm", n=64), on)
-    refused(_env(n=64, dtype="f64"), _env(n=64, dtype="f64"), on)
-    refused(_env(n=64, kernel="team"), _env(n=64, kernel="team"), on)
-    refused(amd.GpuWaypointEnv(64, config=_octo_config(64)), amd.GpuWaypointEnv(64, config=_octo_config(64)), on)
-    # rows outside 0..2, past the Python class
-    env, twin = _env(n=64), _env(n=64)
-    env.reset(); twin.reset()
-    for rows in (3, -1):
-        assert env.lib.amenv_set_action_history(env._h, rows) == -1 and b"rows" in env.lib.amenv_last_error(env._h), rows
-    assert int(env.lib.amenv_obs_dim(env._h)) == 20 and "+history" not in env.lib.amenv_kernel_name(env._h).decode()
-    _next_step_alike(env, twin)
-    env.close(); twin.close()
+    def bad_rows(env):     # rows outside 0..2, past the Python class
+        for rows in (3, -1):
+            assert env.lib.amenv_set_action_history(env._h, rows) == -1 and b"rows" in env.lib.amenv_last_error(env._h), rows
+        assert int(env.lib.amenv_obs_dim(env._h)) == 20 and "+history" not in env.lib.amenv_kernel_name(env._h).decode()
+
+    refused = functools.partial(SH.check_refused, SW, action=_wide_row)
+    refused(lambda: _env("hexa_arm", n=64), on)
+    refused(lambda: _env(n=64, dtype="f64"), on)
+    refused(lambda: _env(n=64, kernel="team"), on)
+    refused(lambda: amd.GpuWaypointEnv(64, config=SH.octo_config(64, GID0)), on)
+    refused(lambda: _env(n=64), bad_rows)
     # the normaliser inside the launch, while the history is on
     env, twin = _env(n=64, action_history=H2), _env(n=64, action_history=H2)
     env.reset(); twin.reset()
@@ -432,13 +332,13 @@ def test_history_refusals_leave_everything_untouched():
     before = nrm.get()
     b = _nan_buffers(4, 64, od, dev)
     with pytest.raises(L.AmenvError, match="history"):
-        env.rollout_policy(_policy(od).flat_param, 4, seed=1, draw0=0, obs_normalizer=nrm, **b)
+        env.rollout_policy(SH.policy(od).flat_param, 4, seed=1, draw0=0, obs_normalizer=nrm, **b)
     torch.cuda.synchronize()
     assert bool(torch.isnan(b["obs"]).all())
     for x, y in zip(before, nrm.get()):
         assert np.array_equal(x, y)
-    _next_step_alike(env, twin)
-    assert _same_delay_state(env, twin)
+    SH.next_step_alike(env, twin, _wide_row)
+    _same_delay_state(env, twin)
     nrm.close(); env.close(); twin.close()
 
 
@@ -449,16 +349,8 @@ def test_history_two_shards_equal_one_handle_and_restore():
     whole = _env("hexa", "v2", 1, n=n, **kw)
     h0 = _env("hexa", "v2", 1, n=cut, **kw)
     h1 = _env("hexa", "v2", 1, n=n - cut, env_id_offset=GID0 + cut, **kw)
-    assert torch.equal(whole.reset(), torch.cat([h0.reset(), h1.reset()]))
     acts = _actions(T + 10, n, 4, whole.device)
-    for t in range(T):
-        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
-        p0 = [x.clone() for x in h0.step(acts[t, :cut])]
-        p1 = [x.clone() for x in h1.step(acts[t, cut:])]
-        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
-            assert torch.equal(x, torch.cat([y, z])), t
-    for x, y, z in zip(whole.action_delay_state(), h0.action_delay_state(), h1.action_delay_state()):
-        assert torch.equal(x, torch.cat([y, z]))
+    SH.check_two_shards(whole, h0, h1, cut, acts[:T], side=(SW,))
     # restore into a fresh handle: get_state + action_delay_state are the whole state
     fresh = _env("hexa", "v2", 1, n=n, **kw)
     fresh.reset()
@@ -467,11 +359,9 @@ def test_history_two_shards_equal_one_handle_and_restore():
     assert torch.equal(fresh.observe(), whole.obs)
     for t in range(T, T + 10):
         ra, da = _step_all(whole, acts[t]); rb, db = _step_all(fresh, acts[t])
-        for x, y in zip(ra[:4], rb[:4]):
-            assert torch.equal(x, y), t
-        for x, y in zip(ra[4:], rb[4:]):
-            assert torch.equal(x[da], y[db]), t
-    assert _same_state(whole, fresh) and _same_delay_state(whole, fresh)
+        _same_step(ra, da, rb, db, t)
+    _same_state(whole, fresh)
+    _same_delay_state(whole, fresh)
     for e in (whole, h0, h1, fresh):
         e.close()
 

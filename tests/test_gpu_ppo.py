@@ -11,6 +11,7 @@ import torch
 import rl_aerial_manipulator_amd as amd
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.ppo import ActorCritic, PPO, RolloutBuffer, compute_gae, gaussian_act
+from tests.switch_harness import fixture_policy
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,11 +28,6 @@ def gae_magnitude(r, v, d, lv, gamma=0.995, lam=0.9):
         m[t] = last
         nv = v[t]
     return m
-
-
-def fixture_policy(device):
-    z = np.load(os.path.join(GOLD, "policy_2300000.npz"))
-    return ActorCritic.from_sb3({k: torch.from_numpy(z[k]) for k in z.files if not k.startswith("_")}, device=device)
 
 
 @pytest.mark.parametrize("T,N", [(1, 1), (37, 1000), (128, 4096), (5, 70001)])

@@ -3,7 +3,6 @@ fused MLP + Adam step (exact: which minibatch trips it, what every buffer holds 
 against the torch path under the gate, schedules on the captured-graph path, and `PPO.learn` end to end."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
@@ -12,9 +11,9 @@ import torch
 import rl_aerial_manipulator_amd as amd
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.ppo import ActorCritic, MinibatchStep, PPO, ppo_update
+from tests.switch_harness import fixture_policy as _fixture_policy
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 SHAPES = [(20, 4, 1000), (29, 7, 4096)]          # a ragged tile (1000 is no multiple of 32) and a full one, the two policy shapes
 ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
 
@@ -259,11 +258,6 @@ def test_fused_and_torch_paths_stop_at_the_same_minibatch():
 
 
 # ---- schedules and the whole loop -----------------------------------------------------------------------------------------------------
-def _fixture_policy(device):
-    z = np.load(os.path.join(GOLD, "policy_2300000.npz"))
-    return ActorCritic.from_sb3({k: torch.from_numpy(z[k]) for k in z.files if not k.startswith("_")}, device=device)
-
-
 def test_schedule_takes_effect_on_the_captured_graph_path():
     """Two updates on one rollout with learning_rate and clip_range halved between them, captured graphs against eager: a capture bakes
     clip_range in (the learning rate of the fused Adam step is re-uploaded to its device buffer), so the change drops the graphs and the

@@ -13,50 +13,18 @@ import rl_aerial_manipulator_amd as amd
 from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
-from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic
+from rl_aerial_manipulator_amd.ppo import PPO
 from tests import dr_ref
+from tests import switch_harness as H
 
 pytestmark = pytest.mark.gpu
+SW = H.RANDOMIZATION
 
 DR = amd.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.7, 1.3), thrust=(0.9, 1.1))
 ONE = amd.DynamicsRandomization()
 # (vehicle, task, waypoints): the lane / helper-wave instantiations (KW = 1 v2, KW = 4 v2, KW = 2 v1)
 CONFIGS = [("quad", "v2", 1), ("hexa", "v2", 1), ("hexa", "v2", 3), ("quad", "v1_raw", 1)]
-
-
-def _env(vehicle, task, nwp, n, seed=4, **kw):
-    kw.setdefault("max_episode_steps", 25)
-    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
-
-
-def _actions(T, n, seed, dev, wide=False):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    if wide:   # near +-1 (and 0 / 2 on the collective): rotors saturate at both limits
-        a = torch.rand(T, n, 4, generator=g)
-        a = torch.where(a < 0.5, -1.0 + 0.2 * a, 0.8 + 0.4 * a)
-        a[..., 0] = torch.where(a[..., 0] < 0, 1.5 + a[..., 0], a[..., 0] + 0.7)
-    else:
-        a = torch.rand(T, n, 4, generator=g) * torch.tensor([0.6, 0.4, 0.4, 0.4]) + torch.tensor([0.7, -0.2, -0.2, -0.2])
-    return a.to(dev).contiguous()
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
-
-
-def _buffers(T, n, od, dev):
-    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
-                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
-
-
-def _step_all(env, a):
-    o, r, d, i = env.step(a)
-    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
+_env, _actions = H.make_env, H.actions
 
 
 # ---- 1. {1, 1} ranges are the identity ------------------------------------------------------------------------------------------
@@ -70,18 +38,7 @@ def test_unit_ranges_are_bit_identical_step_and_rollout(vehicle, task, nwp, dtyp
     assert "+dr" in b.kernel_name and "+dr" not in a.kernel_name
     assert torch.equal(a.reset(), b.reset())
     assert torch.equal(b.dynamics_factors(), torch.ones(n, 2 + b.n_rotors, device=b.device))
-    acts = _actions(T, n, 1, a.device)
-    for t in range(T):
-        ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
-        for x, y in zip(ra[:4], rb[:4]):
-            assert torch.equal(x, y), t
-        for x, y in zip(ra[4:], rb[4:]):
-            assert torch.equal(x[da], y[db]), t
-    ra, rb = a.rollout(acts), b.rollout(acts)
-    for k in ra:
-        assert torch.equal(ra[k], rb[k]), k
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
+    H.check_same_steps_and_rollout(a, b, _actions(T, n, 1, a.device))
     a.close(); b.close()
 
 
@@ -94,29 +51,12 @@ def test_unit_ranges_are_bit_identical_closed_loop(vehicle, task, nwp, n):
     a = _env(vehicle, task, nwp, n, block_size=64)
     b = _env(vehicle, task, nwp, n, randomization=ONE)
     a.reset(); b.reset()
-    od, dev = a.obs_dim, a.device
-    pol = _policy(od)
-    for norm in (False, True):
-        ba, bb = _buffers(T, n, od, dev), _buffers(T, n, od, dev)
-        ia, ib = (torch.zeros(T, n, dtype=torch.int32, device=dev) for _ in range(2))
-        kw_a, kw_b = {}, {}
-        if norm:   # the same entry statistics in both (the normaliser's fp64 sums are atomics: their rounding is not reproducible bit for bit)
-            na, nb = ObsNormalizer(od), ObsNormalizer(od)
-            na.update(a.observe()); nb.set(*na.get())
-            kw_a, kw_b = dict(obs_normalizer=na), dict(obs_normalizer=nb)
-        a.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ia, **ba, **kw_a)
-        b.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ib, **bb, **kw_b)
-        torch.cuda.synchronize()
-        for k in ba:
-            assert torch.equal(ba[k], bb[k]), (norm, k)
-        assert torch.equal(ia, ib) and int(ba["dones"].sum()) > 0
-        if norm:
-            (ma, va, ca), (mb, vb, cb) = na.get(), nb.get()
-            assert ca == cb
-            np.testing.assert_allclose(ma, mb, rtol=1e-10, atol=1e-12); np.testing.assert_allclose(va, vb, rtol=1e-10, atol=1e-12)
-            na.close(); nb.close()
-    fa, sa = a.get_state(); fb, sb = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(sa, sb)
+    pol = H.policy(a.obs_dim)
+    H.check_same_closed_loop(a, b, pol, T)
+    (ma, va, ca), (mb, vb, cb) = H.check_same_closed_loop(a, b, pol, T, norm=True)
+    assert ca == cb
+    np.testing.assert_allclose(ma, mb, rtol=1e-10, atol=1e-12); np.testing.assert_allclose(va, vb, rtol=1e-10, atol=1e-12)
+    H.same_state(a, b)
     a.close(); b.close()
 
 
@@ -165,7 +105,7 @@ def test_kernels_match_the_oracle_with_per_env_vehicles(vehicle, task, nwp, dtyp
     wide = amd.DynamicsRandomization(mass=(0.6, 1.6), inertia=(0.5, 2.0), thrust=(0.8, 1.2))
     env = _env(vehicle, task, nwp, n, seed=8, dtype=dtype, kernel=kernel, max_episode_steps=12, randomization=wide)
     env.reset()
-    base = O.Config.from_buffer_copy(env.cfg)
+    base = H.oracle_cfg(env)
     acts = _actions(T, n, 6, env.device, wide=True)
     tol = 1e-12 if dtype == "f64" else 1e-5
     worst, ended = 0.0, 0
@@ -202,16 +142,7 @@ def test_rollout_equals_steps(vehicle, task, nwp, dtype):
     n, T = 1000, 80
     a = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, randomization=DR)
     b = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, randomization=DR)
-    a.reset(); b.reset()
-    acts = _actions(T, n, 2, a.device)
-    ro = a.rollout(acts)
-    for t in range(T):
-        o, r, d, i = b.step(acts[t])
-        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
-    assert int(ro["done"].sum()) > n
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
-    assert torch.equal(a.dynamics_factors(), b.dynamics_factors())
+    H.check_rollout_equals_steps(a, b, _actions(T, n, 2, a.device), min_ended=n, side=(SW,))
     a.close(); b.close()
 
 
@@ -222,33 +153,7 @@ def test_closed_loop_replays_bit_for_bit(vehicle, task, nwp, n, norm):
     T = 64
     env = _env(vehicle, task, nwp, n, randomization=DR)
     ref = _env(vehicle, task, nwp, n, kernel="lane", randomization=DR)
-    od, dev = env.obs_dim, env.device
-    pol = _policy(od)
-    env.reset(); ref.reset()
-    kw = {}
-    if norm:
-        nrm = ObsNormalizer(od)
-        nrm.update(env.observe())
-        entry = ObsNormalizer(od); entry.set(*nrm.get())
-        kw = dict(obs_normalizer=nrm)
-    b = _buffers(T, n, od, dev)
-    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
-    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b, **kw)
-    torch.cuda.synchronize()
-    tr = (lambda x: entry.normalize(x)) if norm else (lambda x: x)
-    lo, hi = pol.action_low, pol.action_high
-    for t in range(T):
-        o, r, d, i = ref.step(torch.max(torch.min(b["actions"][t], hi), lo))
-        assert torch.equal(tr(o), b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
-        dn = d.bool()
-        if bool(dn.any()):
-            assert torch.equal(tr(ref.terminal_obs[dn]), tobs[t][dn]), t
-    f1, i1 = env.get_state(); f2, i2 = ref.get_state()
-    assert torch.equal(f1, f2) and torch.equal(i1, i2) and env.stats() == ref.stats()
-    assert int(b["dones"].sum()) > 0
-    env.close(); ref.close()
-    if norm:
-        nrm.close(); entry.close()
+    H.check_closed_loop_replays(env, ref, T, norm=norm).close()
 
 
 # ---- 6. sharding and re-keying --------------------------------------------------------------------------------------------------
@@ -257,17 +162,7 @@ def test_sharding_and_reseed():
     whole = _env("hexa", "v2", 1, n, seed=13, max_episode_steps=20, randomization=DR)
     h0 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, randomization=DR)
     h1 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, randomization=DR, env_id_offset=n // 2)
-    ow = whole.reset().clone(); o0 = h0.reset().clone(); o1 = h1.reset().clone()
-    assert torch.equal(ow, torch.cat([o0, o1]))
-    assert torch.equal(whole.dynamics_factors(), torch.cat([h0.dynamics_factors(), h1.dynamics_factors()]))
-    acts = _actions(T, n, 4, whole.device)
-    for t in range(T):
-        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
-        p0 = [x.clone() for x in h0.step(acts[t, :n // 2])]
-        p1 = [x.clone() for x in h1.step(acts[t, n // 2:])]
-        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
-            assert torch.equal(x, torch.cat([y, z])), t
-    assert torch.equal(whole.dynamics_factors(), torch.cat([h0.dynamics_factors(), h1.dynamics_factors()]))
+    H.check_two_shards(whole, h0, h1, n // 2, _actions(T, n, 4, whole.device), side=(SW,))
     before = whole.dynamics_factors().clone()
     whole.reseed(14)
     after = whole.dynamics_factors()
@@ -280,26 +175,16 @@ def test_sharding_and_reseed():
 
 # ---- 7. refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_state_untouched():
-    arm = _env("hexa_arm", "v2", 1, 64)
-    arm.reset()
-    f0, i0 = arm.get_state()
-    with pytest.raises(L.AmenvError):
-        arm.set_randomization(DR)
-    with pytest.raises(L.AmenvError):
-        arm.dynamics_factors()
-    f1, i1 = arm.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+dr" not in arm.kernel_name
-    arm.close()
+    def arm_asks(env):
+        with pytest.raises(L.AmenvError):
+            env.set_randomization(DR)
+        with pytest.raises(L.AmenvError):
+            env.dynamics_factors()
+
+    H.check_refused(SW, lambda: _env("hexa_arm", "v2", 1, 64), arm_asks)
     with pytest.raises(L.AmenvError):
         _env("hexa_arm", "v2", 1, 64, n_joints=2, randomization=DR)
-    team = _env("quad", "v2", 1, 64, kernel="team")
-    team.reset()
-    f0, i0 = team.get_state()
-    with pytest.raises(L.AmenvError):
-        team.set_randomization(DR)
-    f1, i1 = team.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+dr" not in team.kernel_name
-    team.close()
+    H.check_refused(SW, lambda: _env("quad", "v2", 1, 64, kernel="team"), DR)
     env = _env("quad", "v2", 1, 64, randomization=DR)
     env.reset()
     f0, i0 = env.get_state(); k0 = env.dynamics_factors().clone()

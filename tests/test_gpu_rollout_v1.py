@@ -13,6 +13,7 @@ from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
 from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic
+from tests.switch_harness import buffers as _buffers, policy as _policy
 from tests.test_gpu_ppo import gae_magnitude
 from tests.test_rollout_v1_cpu import RunningMeanStd
 
@@ -21,20 +22,6 @@ pytestmark = pytest.mark.gpu
 
 def _env(vehicle, task, nwp, n, **kw):
     return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=4, max_episode_steps=60, **kw)
-
-
-def _buffers(T, n, od, dev):
-    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
-                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
 
 
 # sizes: 300 and 4096 run the 16-env workgroups, 12000 the 64-env ones, 40000 the 128-env ones (AMENV_RIGID_WG16_MAX / WG64_MAX)

@@ -5,7 +5,6 @@ state included; the step response is the closed form's; the reference checkpoint
 it; restore and sharding; refusals leave everything untouched; PPO trains with it."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
@@ -15,55 +14,18 @@ import rl_aerial_manipulator_amd as amd
 from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
 from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
-from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic, evaluate_policy
+from rl_aerial_manipulator_amd.ppo import PPO, evaluate_policy
 from tests import dr_ref, lag_ref
+from tests import switch_harness as H
 
 pytestmark = pytest.mark.gpu
+SW = H.ROTOR_LAG
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 LAG = amd.RotorLag(0.015)
 SKEW = amd.RotorLag(0.015, 0.04)
 DR = amd.DynamicsRandomization(mass=(0.8, 1.2), inertia=(0.7, 1.3), thrust=(0.9, 1.1))
 WIDE = amd.DynamicsRandomization(mass=(0.6, 1.6), inertia=(0.5, 2.0), thrust=(0.8, 1.2))
-
-
-def _env(vehicle, task, nwp, n, seed=4, **kw):
-    kw.setdefault("max_episode_steps", 25)
-    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
-
-
-def _actions(T, n, seed, dev, wide=False):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    if wide:   # near +-1 (and 0 / 2 on the collective): rotors saturate at both limits and commands reverse from step to step
-        a = torch.rand(T, n, 4, generator=g)
-        a = torch.where(a < 0.5, -1.0 + 0.2 * a, 0.8 + 0.4 * a)
-        a[..., 0] = torch.where(a[..., 0] < 0, 1.5 + a[..., 0], a[..., 0] + 0.7)
-    else:
-        a = torch.rand(T, n, 4, generator=g) * torch.tensor([0.6, 0.4, 0.4, 0.4]) + torch.tensor([0.7, -0.2, -0.2, -0.2])
-    return a.to(dev).contiguous()
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
-
-
-def _buffers(T, n, od, dev):
-    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
-                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
-
-
-def _step_all(env, a):
-    o, r, d, i = env.step(a)
-    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
-
-
-def _ocfg(env):
-    return O.Config.from_buffer_copy(env.cfg)
+_env, _actions, _ocfg = H.make_env, H.actions, H.oracle_cfg
 
 
 # ---- 1. off is invisible --------------------------------------------------------------------------------------------------------
@@ -73,24 +35,7 @@ def test_lag_set_and_cleared_is_bit_invisible_step_and_rollout(vehicle, task, nw
     n, T = 300, 40
     a = _env(vehicle, task, nwp, n, dtype=dtype, kernel=kernel)
     b = _env(vehicle, task, nwp, n, dtype=dtype, kernel=kernel)
-    name = b.kernel_name
-    b.set_rotor_lag(LAG)
-    assert b.kernel_name == name + " +lag" and b.rotor_lag is LAG
-    b.set_rotor_lag(None)
-    assert b.kernel_name == name == a.kernel_name and b.rotor_lag is None
-    assert torch.equal(a.reset(), b.reset())
-    acts = _actions(T, n, 1, a.device)
-    for t in range(T):
-        ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
-        for x, y in zip(ra[:4], rb[:4]):
-            assert torch.equal(x, y), t
-        for x, y in zip(ra[4:], rb[4:]):
-            assert torch.equal(x[da], y[db]), t
-    ra, rb = a.rollout(acts), b.rollout(acts)
-    for k in ra:
-        assert torch.equal(ra[k], rb[k]), k
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
+    H.check_set_and_cleared_step_and_rollout(SW, LAG, a, b, _actions(T, n, 1, a.device))
     a.close(); b.close()
 
 
@@ -100,21 +45,7 @@ def test_lag_set_and_cleared_is_bit_invisible_closed_loop(vehicle, task, nwp, n)
     T = 48
     a = _env(vehicle, task, nwp, n)
     b = _env(vehicle, task, nwp, n, rotor_lag=LAG)
-    b.set_rotor_lag(None)
-    assert a.kernel_name == b.kernel_name
-    a.reset(); b.reset()
-    od, dev = a.obs_dim, a.device
-    pol = _policy(od)
-    ba, bb = _buffers(T, n, od, dev), _buffers(T, n, od, dev)
-    ia, ib = (torch.zeros(T, n, dtype=torch.int32, device=dev) for _ in range(2))
-    a.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ia, **ba)
-    b.rollout_policy(pol.flat_param, T, seed=9, draw0=3, info_bits=ib, **bb)
-    torch.cuda.synchronize()
-    for k in ba:
-        assert torch.equal(ba[k], bb[k]), k
-    assert torch.equal(ia, ib) and int(ba["dones"].sum()) > 0
-    fa, sa = a.get_state(); fb, sb = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(sa, sb)
+    H.check_set_and_cleared_closed_loop(SW, a, b, T)
     a.close(); b.close()
 
 
@@ -239,17 +170,9 @@ def test_lagged_rollout_equals_steps(vehicle, task, nwp, dtype):
     n, T = 1000, 80
     a = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, rotor_lag=SKEW)
     b = _env(vehicle, task, nwp, n, dtype=dtype, max_episode_steps=25, rotor_lag=SKEW)
-    a.reset(); b.reset()
-    acts = _actions(T, n, 2, a.device)
-    ro = a.rollout(acts)
-    for t in range(T):
-        o, r, d, i = b.step(acts[t])
-        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
-    assert int(ro["done"].sum()) > n
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
-    wa, wb = a.rotor_state(), b.rotor_state()
-    assert torch.equal(wa, wb) and not torch.equal(wa, torch.from_numpy(np.tile(lag_ref.w0(_ocfg(a), dtype), (n, 1))).to(wa.device))
+    H.check_rollout_equals_steps(a, b, _actions(T, n, 2, a.device), min_ended=n, side=(SW,))
+    wa = a.rotor_state()
+    assert not torch.equal(wa, torch.from_numpy(np.tile(lag_ref.w0(_ocfg(a), dtype), (n, 1))).to(wa.device))
     a.close(); b.close()
 
 
@@ -262,34 +185,7 @@ def test_lagged_closed_loop_replays_bit_for_bit(vehicle, task, nwp, n, norm, dr)
     T = 64
     env = _env(vehicle, task, nwp, n, rotor_lag=SKEW, randomization=dr)
     ref = _env(vehicle, task, nwp, n, kernel="lane", rotor_lag=SKEW, randomization=dr)
-    od, dev = env.obs_dim, env.device
-    pol = _policy(od)
-    env.reset(); ref.reset()
-    kw = {}
-    if norm:
-        nrm = ObsNormalizer(od)
-        nrm.update(env.observe())
-        entry = ObsNormalizer(od); entry.set(*nrm.get())
-        kw = dict(obs_normalizer=nrm)
-    b = _buffers(T, n, od, dev)
-    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
-    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b, **kw)
-    torch.cuda.synchronize()
-    tr = (lambda x: entry.normalize(x)) if norm else (lambda x: x)
-    lo, hi = pol.action_low, pol.action_high
-    for t in range(T):
-        o, r, d, i = ref.step(torch.max(torch.min(b["actions"][t], hi), lo))
-        assert torch.equal(tr(o), b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
-        dn = d.bool()
-        if bool(dn.any()):
-            assert torch.equal(tr(ref.terminal_obs[dn]), tobs[t][dn]), t
-    f1, i1 = env.get_state(); f2, i2 = ref.get_state()
-    assert torch.equal(f1, f2) and torch.equal(i1, i2) and env.stats() == ref.stats()
-    assert torch.equal(env.rotor_state(), ref.rotor_state())
-    assert int(b["dones"].sum()) > 0
-    env.close(); ref.close()
-    if norm:
-        nrm.close(); entry.close()
+    H.check_closed_loop_replays(env, ref, T, norm=norm, side=(SW,)).close()
 
 
 # ---- 5. step response on the device ---------------------------------------------------------------------------------------------
@@ -331,17 +227,12 @@ def test_step_response_is_the_closed_form(dtype, kernel):
 
 
 # ---- 6. it changes how a policy flies -------------------------------------------------------------------------------------------
-def _fixture_policy(device):
-    z = np.load(os.path.join(GOLD, "policy_2300000.npz"))
-    return ActorCritic.from_sb3({k: torch.from_numpy(z[k]) for k in z.files if not k.startswith("_")}, device=device)
-
-
 @pytest.mark.parametrize("tau", [0.015, 0.09])
 def test_reference_checkpoint_under_lag(tau):
     """The reference checkpoint on the quadrotor, 1,024 episodes through evaluate_policy: the SDF's 15 ms keeps success >= 95 % (the
     lagged oracle: 148 / 148), 90 ms brings it below 10 % with crashes the majority of endings (the lagged oracle: 6 / 608, 602 crashed)."""
     env = amd.GpuWaypointEnv(1024, seed=99, rotor_lag=amd.RotorLag(tau))
-    pol = _fixture_policy(env.device)
+    pol = H.fixture_policy(env.device)
     env.reset()
     env.stats(reset=True)
     evaluate_policy(pol, env, n_eval_episodes=1024)
@@ -373,12 +264,10 @@ def test_restore_into_a_fresh_handle():
     b.set_rotor_state(w)
     assert torch.equal(b.rotor_state(), w)
     for t in range(30, 50):
-        ra, da = _step_all(a, acts[t]); rb, db = _step_all(b, acts[t])
-        for x, y in zip(ra[:4], rb[:4]):
-            assert torch.equal(x, y), t
-        assert torch.equal(a.rotor_state(), b.rotor_state()), t
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib)
+        ra, da = H.step_all(a, acts[t]); rb, db = H.step_all(b, acts[t])
+        H.same_step(ra, da, rb, db, t)
+        SW.same_side_state(a, b, t)
+    H.same_state(a, b)
     # new time constants on a running handle keep the rotor states
     w = a.rotor_state().clone()
     a.set_rotor_lag(amd.RotorLag(0.05))
@@ -391,101 +280,50 @@ def test_two_shards_equal_one_handle():
     whole = _env("hexa", "v2", 1, n, seed=13, max_episode_steps=20, rotor_lag=SKEW)
     h0 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, rotor_lag=SKEW)
     h1 = _env("hexa", "v2", 1, n // 2, seed=13, max_episode_steps=20, rotor_lag=SKEW, env_id_offset=n // 2)
-    ow = whole.reset().clone(); o0 = h0.reset().clone(); o1 = h1.reset().clone()
-    assert torch.equal(ow, torch.cat([o0, o1]))
-    acts = _actions(T, n, 4, whole.device, wide=True)
-    for t in range(T):
-        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
-        p0 = [x.clone() for x in h0.step(acts[t, :n // 2])]
-        p1 = [x.clone() for x in h1.step(acts[t, n // 2:])]
-        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
-            assert torch.equal(x, torch.cat([y, z])), t
-        assert torch.equal(whole.rotor_state(), torch.cat([h0.rotor_state(), h1.rotor_state()])), t
+    H.check_two_shards(whole, h0, h1, n // 2, _actions(T, n, 4, whole.device, wide=True), side=(SW,), every_step=True)
     for e in (whole, h0, h1):
         e.close()
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------
 def test_lag_refusals_leave_everything_untouched():
-    arm = _env("hexa_arm", "v2", 1, 64)
-    arm.reset()
-    f0, i0 = arm.get_state()
-    with pytest.raises(L.AmenvError):
-        arm.set_rotor_lag(LAG)
-    with pytest.raises(L.AmenvError):
-        arm.rotor_state()
-    f1, i1 = arm.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+lag" not in arm.kernel_name and arm.rotor_lag is None
-    arm.close()
+    def arm_asks(env):
+        with pytest.raises(L.AmenvError):
+            env.set_rotor_lag(LAG)
+        with pytest.raises(L.AmenvError):
+            env.rotor_state()
+
+    H.check_refused(SW, lambda: _env("hexa_arm", "v2", 1, 64), arm_asks)
     with pytest.raises(L.AmenvError):
         _env("hexa_arm", "v2", 1, 64, n_joints=2, rotor_lag=LAG)
-    team = _env("quad", "v2", 1, 64, kernel="team")
-    twin = _env("quad", "v2", 1, 64, kernel="team")
-    team.reset(); twin.reset()
-    f0, i0 = team.get_state()
-    with pytest.raises(L.AmenvError):
-        team.set_rotor_lag(LAG)
-    f1, i1 = team.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+lag" not in team.kernel_name and team.rotor_lag is None
-    a = _actions(1, 64, 3, team.device)[0]
-    for x, y in zip(team.step(a), twin.step(a)):
-        assert torch.equal(x, y)
-    team.close(); twin.close()
+    H.check_refused(SW, lambda: _env("quad", "v2", 1, 64, kernel="team"), LAG)
     # a config with a negative t_min
     cfg = L.default_config("quad", 64)
     cfg.vehicle.t_min[1] = -0.5
-    neg = amd.GpuWaypointEnv(64, config=cfg)
-    neg.reset()
-    f0, i0 = neg.get_state()
-    with pytest.raises(L.AmenvError, match="t_min"):
-        neg.set_rotor_lag(LAG)
-    f1, i1 = neg.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+lag" not in neg.kernel_name
-    neg.close()
-    # bad struct_size / time constants through ctypes; rotor_state() with the lag off
-    env = _env("quad", "v2", 1, 64)
-    twin = _env("quad", "v2", 1, 64)
-    env.reset(); twin.reset()
-    f0, i0 = env.get_state()
-    bad = LAG.to_c()
-    bad.struct_size = 16
-    assert env.lib.amenv_set_rotor_lag(env._h, C.byref(bad)) == -1
-    assert b"struct_size" in env.lib.amenv_last_error(env._h)
-    for tu, td in [(0.0, 0.015), (0.015, -1.0), (float("nan"), 0.015), (0.015, float("inf")), (10.5, 0.015)]:
-        c = LAG.to_c()
-        c.tau_up, c.tau_down = tu, td
-        assert env.lib.amenv_set_rotor_lag(env._h, C.byref(c)) == -1, (tu, td)
-    with pytest.raises(L.AmenvError, match="off"):
-        env.rotor_state()
-    with pytest.raises(L.AmenvError, match="off"):
-        env.set_rotor_state(torch.zeros(64, 4))
-    assert env.lib.amenv_get_rotor_state(env._h, None, None) == -1
-    f1, i1 = env.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1) and "+lag" not in env.kernel_name and env.rotor_lag is None
-    assert env.kernel_name == env.lib.amenv_kernel_name(env._h).decode()
-    for x, y in zip(env.step(a), twin.step(a)):
-        assert torch.equal(x, y)
-    env.close(); twin.close()
+    H.check_refused(SW, lambda: amd.GpuWaypointEnv(64, config=cfg), LAG, "t_min")
+
+    def bad_struct_and_off(env):     # bad struct_size / time constants through ctypes; rotor_state() with the lag off
+        bad = LAG.to_c()
+        bad.struct_size = 16
+        assert env.lib.amenv_set_rotor_lag(env._h, C.byref(bad)) == -1
+        assert b"struct_size" in env.lib.amenv_last_error(env._h)
+        for tu, td in [(0.0, 0.015), (0.015, -1.0), (float("nan"), 0.015), (0.015, float("inf")), (10.5, 0.015)]:
+            c = LAG.to_c()
+            c.tau_up, c.tau_down = tu, td
+            assert env.lib.amenv_set_rotor_lag(env._h, C.byref(c)) == -1, (tu, td)
+        with pytest.raises(L.AmenvError, match="off"):
+            env.rotor_state()
+        with pytest.raises(L.AmenvError, match="off"):
+            env.set_rotor_state(torch.zeros(64, 4))
+        assert env.lib.amenv_get_rotor_state(env._h, None, None) == -1
+
+    H.check_refused(SW, lambda: _env("quad", "v2", 1, 64), bad_struct_and_off)
 
 
 # ---- 9. PPO ---------------------------------------------------------------------------------------------------------------------
 def test_ppo_fused_rollout_with_rotor_lag():
     n, T = 4096, 16
-    env = amd.GpuWaypointEnv(n, seed=2, max_episode_steps=12, rotor_lag=LAG, randomization=DR)
-    ref = amd.GpuWaypointEnv(n, seed=2, max_episode_steps=12, kernel="lane", rotor_lag=LAG, randomization=DR)
-    assert env.kernel_name.endswith("+dr +lag")
-    algo = PPO(env, fused_rollout=True, n_steps=T, n_epochs=2, batch_size=8192, seed=1, bootstrap_truncated=False)
-    ref.reset()
-    algo.learn(T * n)
-    buf = algo.buffer
-    lo, hi = algo.policy.action_low, algo.policy.action_high
-    for t in range(T):   # the first iteration's rollout buffer replays through amenv_step
-        o, r, d, _ = ref.step(torch.max(torch.min(buf.actions[t], hi), lo))
-        assert torch.equal(o, buf.obs[t + 1]) and torch.equal(r, buf.rewards[t]) and torch.equal(d, buf.dones[t]), t
-    algo.learn(T * n)
-    assert len(algo.log) == 2 and all(math.isfinite(x) for rec in algo.log for x in rec.values())
-    assert int(buf.dones.sum()) > 0
-    env.close(); ref.close()
+    H.check_ppo_fused_rollout_replays(SW, n, T, name_ends="+dr +lag", rotor_lag=LAG, randomization=DR)
     norm = ObsNormalizer(17)
     env = amd.GpuWaypointEnv(n, task="v1_raw", seed=3, max_episode_steps=12, rotor_lag=LAG)
     algo = PPO(env, obs_normalizer=norm, fused_rollout=True, n_steps=T, n_epochs=1, batch_size=8192, seed=1)

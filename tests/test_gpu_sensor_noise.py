@@ -3,21 +3,20 @@ are the numpy restatement's, bit for bit; the true dynamics, rewards and Monitor
 terminal, post-reset, reset(), observe() -- is the UNCHANGED fp64 oracle's observation of the perturbed state (tests/noise_ref.py); the
 one-launch rollout and the closed loop replay bit for bit through amenv_step and the policy reads the noisy rows; shards; refusals; PPO."""
 import ctypes as C
-import math
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import rl_aerial_manipulator_amd as amd
-from oracle import oracle as O
 from rl_aerial_manipulator_amd import _lib as L
-from rl_aerial_manipulator_amd.obs_norm import ObsNormalizer
-from rl_aerial_manipulator_amd.ppo import PPO, ActorCritic
 from tests import noise_ref
+from tests import switch_harness as H
 from tests.test_rollout_v1_cpu import RunningMeanStd
 
 pytestmark = pytest.mark.gpu
+SW = H.SENSOR_NOISE
 
 N = 200       # three full 64-env tiles + 8 ragged lanes
 Z = amd.SensorNoise(position=0.03, velocity=0.08, rate=0.05, attitude=0.02)
@@ -29,40 +28,11 @@ OBS_TOL = 1e-5   # the project's fp32 observation gate, relative to max(1, |x|)
 
 
 def _env(vehicle, task, nwp, n=N, seed=4, **kw):
-    kw.setdefault("max_episode_steps", 25)
-    return amd.GpuWaypointEnv(n, vehicle=vehicle, task=task, num_waypoints=nwp, seed=seed, **kw)
+    return H.make_env(vehicle, task, nwp, n, seed, **kw)
 
 
-def _actions(T, n, seed, dev):
-    """Wide commands: a third of the envs is pushed over hard, so that crashes and out-of-bounds ends join the 25-step truncations."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    a = torch.rand(T, n, 4, generator=g) * torch.tensor([0.6, 0.4, 0.4, 0.4]) + torch.tensor([0.7, -0.2, -0.2, -0.2])
-    a[:, ::3, 0] = 0.1
-    a[:, ::3, 1] = 0.9
-    return a.to(dev).contiguous()
-
-
-def _policy(od):
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    return pol
-
-
-def _buffers(T, n, od, dev):
-    return dict(obs=torch.zeros(T + 1, n, od, device=dev), actions=torch.zeros(T, n, 4, device=dev), logp=torch.zeros(T, n, device=dev),
-                values=torch.zeros(T, n, device=dev), rewards=torch.zeros(T, n, device=dev), dones=torch.zeros(T, n, dtype=torch.uint8, device=dev))
-
-
-def _step_all(env, a):
-    o, r, d, i = env.step(a)
-    return [x.clone() for x in (o, r, d, i, env.terminal_obs, env.ep_return, env.ep_len)], d.bool()
-
-
-def _ocfg(env):
-    return O.Config.from_buffer_copy(env.cfg)
+_actions = functools.partial(H.actions, tipped=True)     # a third of the envs is pushed over hard: crashes and out-of-bounds ends join the truncations
+_step_all, _ocfg = H.step_all, H.oracle_cfg
 
 
 def _state(env):
@@ -92,44 +62,21 @@ def test_set_then_cleared_and_zero_sigmas_are_bit_invisible(vehicle, nwp, kernel
     cleared.set_sensor_noise(None)
     zero = _env(vehicle, "v2", nwp, kernel=kernel, sensor_noise=amd.SensorNoise())
     acts = _actions(T, N, 1, twin.device)
-    od, dev = twin.obs_dim, twin.device
-    pol = _policy(od)
+    pol = H.policy(twin.obs_dim)
     for other in (cleared, zero):
         a = _env(vehicle, "v2", nwp, kernel=kernel) if other is zero else twin
         assert other.kernel_name == a.kernel_name and "+noise" not in other.kernel_name
         assert torch.equal(a.reset(), other.reset())
-        for t in range(T):
-            ra, da = _step_all(a, acts[t]); rb, db = _step_all(other, acts[t])
-            for x, y in zip(ra[:4], rb[:4]):
-                assert torch.equal(x, y), t
-            for x, y in zip(ra[4:], rb[4:]):
-                assert torch.equal(x[da], y[db]), t
-        ra, rb = a.rollout(acts), other.rollout(acts)
-        for k in ra:
-            assert torch.equal(ra[k], rb[k]), k
+        H.check_same_steps_and_rollout(a, other, acts)
         assert torch.equal(a.observe(), other.observe())
-        for norm in (False, True):
-            kw_a, kw_b = {}, {}
-            if norm:
-                na, nb = ObsNormalizer(od), ObsNormalizer(od)
-                na.update(a.observe()); nb.set(*na.get())      # the same entry statistics, bit for bit (an update's sums have no fixed order)
-                kw_a, kw_b = dict(obs_normalizer=na), dict(obs_normalizer=nb)
-            ba, bb = _buffers(16, N, od, dev), _buffers(16, N, od, dev)
-            a.rollout_policy(pol.flat_param, 16, seed=9, draw0=3, **ba, **kw_a)
-            other.rollout_policy(pol.flat_param, 16, seed=9, draw0=3, **bb, **kw_b)
-            torch.cuda.synchronize()
-            for k in ba:
-                assert torch.equal(ba[k], bb[k]), (k, norm)
-            if norm:
-                # (the launch adds its per-wavefront fp64 sums with atomics in no fixed order: the merged statistics agree to rounding,
-                # with the tolerances of tests/test_gpu_rollout_v1.py::test_normaliser_inside_the_launch; the rows above used the frozen ones)
-                (ma, va, ca), (mb, vb, cb) = na.get(), nb.get()
-                assert ca == cb
-                np.testing.assert_allclose(mb, ma, rtol=1e-10, atol=1e-12)
-                np.testing.assert_allclose(vb, va, rtol=1e-10, atol=1e-14 * float(np.max(ma ** 2 + va)))
-                na.close(); nb.close()
-        fa, ia = a.get_state(); fb, ib = other.get_state()
-        assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == other.stats()
+        H.check_same_closed_loop(a, other, pol, 16, info_bits=False, ends=False)
+        # (the merged statistics agree to rounding, with the tolerances of tests/test_gpu_rollout_v1.py::test_normaliser_inside_the_launch)
+        (ma, va, ca), (mb, vb, cb) = H.check_same_closed_loop(a, other, pol, 16, norm=True, info_bits=False, ends=False)
+        assert ca == cb
+        np.testing.assert_allclose(mb, ma, rtol=1e-10, atol=1e-12)
+        np.testing.assert_allclose(vb, va, rtol=1e-10, atol=1e-14 * float(np.max(ma ** 2 + va)))
+        H.same_state(a, other)
+        assert a.stats() == other.stats()
         if a is not twin:
             a.close()
     twin.close(); cleared.close(); zero.close()
@@ -243,15 +190,7 @@ def test_noisy_rollout_equals_steps(task):
     T = 64
     a = _env("quad", task, 1, sensor_noise=Z)
     b = _env("quad", task, 1, sensor_noise=Z)
-    assert torch.equal(a.reset(), b.reset())
-    acts = _actions(T, N, 2, a.device)
-    ro = a.rollout(acts)
-    for t in range(T):
-        o, r, d, i = b.step(acts[t])
-        assert torch.equal(ro["obs"][t], o) and torch.equal(ro["reward"][t], r) and torch.equal(ro["done"][t], d) and torch.equal(ro["info_bits"][t], i), t
-    assert int(ro["done"].sum()) > N
-    fa, ia = a.get_state(); fb, ib = b.get_state()
-    assert torch.equal(fa, fb) and torch.equal(ia, ib) and a.stats() == b.stats()
+    ro = H.check_rollout_equals_steps(a, b, _actions(T, N, 2, a.device), min_ended=N)
     assert torch.equal(a.observe(), ro["obs"][T - 1])
     a.close(); b.close()
 
@@ -269,44 +208,22 @@ def test_noisy_closed_loop_replays_and_the_policy_reads_the_noisy_rows(vehicle, 
     ref = _env(vehicle, task, nwp, n=n, kernel="lane", sensor_noise=Z_BIG, **extra)
     clean = _env(vehicle, task, nwp, n=n, kernel="lane", **extra)
     assert "step_kernel<" in ref.kernel_name and ref.kernel_name.endswith("+noise")
-    od, dev = env.obs_dim, env.device
-    pol = _policy(od)
-    o0 = env.reset().clone(); ref.reset()
+    od = env.obs_dim
     c_rows = [clean.reset().clone()]
-    kw = {}
-    if norm:
-        nrm = ObsNormalizer(od)
-        nrm.update(env.observe())
-        entry = ObsNormalizer(od); entry.set(*nrm.get())
-        kw = dict(obs_normalizer=nrm)
-    tr = (lambda x: entry.normalize(x)) if norm else (lambda x: x)
-    b = _buffers(T, n, od, dev)
-    info = torch.zeros(T, n, dtype=torch.int32, device=dev); tobs = torch.full((T, n, od), float("nan"), device=dev)
-    env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, info_bits=info, terminal_obs=tobs, **b, **kw)
-    torch.cuda.synchronize()
-    assert torch.equal(b["obs"][0], tr(o0))
-    lo, hi = pol.action_low, pol.action_high
     raw_rows = []
-    for t in range(T):
-        act = torch.max(torch.min(b["actions"][t], hi), lo)
-        o, r, d, i = ref.step(act)
-        assert torch.equal(tr(o), b["obs"][t + 1]) and torch.equal(r, b["rewards"][t]) and torch.equal(d, b["dones"][t]) and torch.equal(i, info[t]), t
-        dn = d.bool()
-        if bool(dn.any()):
-            assert torch.equal(tr(ref.terminal_obs[dn]), tobs[t][dn]), t
+
+    def clean_twin(t, act, o, r, d, i):
         raw_rows.append(o.clone())
         oc, rc, dc, _ = clean.step(act)
         assert torch.equal(rc, r) and torch.equal(dc, d), t       # the clean twin flies the same true trajectory
         c_rows.append(oc.clone())
-    f1, i1 = env.get_state(); f2, i2 = ref.get_state(); f3, i3 = clean.get_state()
-    assert torch.equal(f1, f2) and torch.equal(i1, i2) and env.stats() == ref.stats()
-    assert torch.equal(f1, f3) and torch.equal(i1, i3)
-    if extra:
-        assert torch.equal(env.rotor_state(), ref.rotor_state())
-    assert int(b["dones"].sum()) > 0
+
+    run = H.check_closed_loop_replays(env, ref, T, norm=norm, side=(H.ROTOR_LAG,) if extra else (), each_step=clean_twin)
+    b, pol, tr = run.b, run.pol, run.tr
+    H.same_state(env, clean)
     if norm:   # the `update` sums counted the noisy raw rows 1..T (tolerances: tests/test_gpu_rollout_v1.py::test_normaliser_inside_the_launch)
-        mean0, var0, count0 = entry.get()
-        mean1, var1, count1 = nrm.get()
+        mean0, var0, count0 = run.entry.get()
+        mean1, var1, count1 = run.nrm.get()
         rms = RunningMeanStd(od)
         rms.mean, rms.var, rms.count = mean0.copy(), var0.copy(), count0
         for row in raw_rows:
@@ -326,9 +243,7 @@ def test_noisy_closed_loop_replays_and_the_policy_reads_the_noisy_rows(vehicle, 
     print(f"values: against the recorded (noisy) rows {d_noisy:.3e}, against the clean twin's rows {d_clean:.3e}, bound {bound:.3e}")
     assert d_noisy < bound
     assert d_clean > bound
-    env.close(); ref.close(); clean.close()
-    if norm:
-        nrm.close(); entry.close()
+    run.close(); clean.close()
 
 
 # ---- 7. shards ------------------------------------------------------------------------------------------------------------------------
@@ -337,62 +252,23 @@ def test_two_shards_equal_one_handle():
     whole = _env("hexa", "v2", 1, seed=13, max_episode_steps=20, sensor_noise=Z)
     h0 = _env("hexa", "v2", 1, n=cut, seed=13, max_episode_steps=20, sensor_noise=Z)
     h1 = _env("hexa", "v2", 1, n=N - cut, seed=13, max_episode_steps=20, sensor_noise=Z, env_id_offset=cut)
-    assert torch.equal(whole.reset(), torch.cat([h0.reset(), h1.reset()]))
-    acts = _actions(T, N, 4, whole.device)
-    for t in range(T):
-        ow, rw, dw, iw = (x.clone() for x in whole.step(acts[t]))
-        p0 = [x.clone() for x in h0.step(acts[t, :cut])]
-        p1 = [x.clone() for x in h1.step(acts[t, cut:])]
-        for x, y, z in zip((ow, rw, dw, iw), p0, p1):
-            assert torch.equal(x, torch.cat([y, z])), t
-        dn = dw.bool()
-        assert torch.equal(whole.terminal_obs[dn], torch.cat([h0.terminal_obs, h1.terminal_obs])[dn]), t
-    assert torch.equal(whole.sensor_noise_samples(), torch.cat([h0.sensor_noise_samples(), h1.sensor_noise_samples()]))
+    H.check_two_shards(whole, h0, h1, cut, _actions(T, N, 4, whole.device), side=(SW,))
     assert whole.stats()["episodes"] >= N        # 40 steps of 20-step episodes: every env ended once
     for e in (whole, h0, h1):
         e.close()
 
 
 # ---- 8. refusals ----------------------------------------------------------------------------------------------------------------------
-def _octo_config(n):
-    """A synthetic 8-rotor vehicle (the runtime-rotor-count kernels): rotors on a 0.3 m circle, alternating spin, pseudo-inverse allocation."""
-    cfg = L.default_config("hexa", n)
-    v = cfg.vehicle
-    v.n_rotors, v.mass = 8, 3.0
-    ang = np.arange(8) * np.pi / 4
-    mix = np.stack([np.ones(8), 0.3 * np.sin(ang), -0.3 * np.cos(ang), 0.02 * (-1.0) ** np.arange(8)])
-    alloc = np.linalg.pinv(mix)
-    for r in range(8):
-        for j in range(4):
-            v.alloc[r * 4 + j] = alloc[r, j]
-            v.mix[j * 8 + r] = mix[j, r]
-        v.t_min[r], v.t_max[r] = 0.0, 2.0 * v.mass * v.g / 8
-    return cfg
+def _unit_row(env):
+    return torch.rand(env.num_envs, env.act_dim, generator=torch.Generator().manual_seed(3)).to(env.device)
 
 
-def _refused(make, what, match=None):
-    """make() twice: one handle is asked for the noise and must refuse and stay as it was; its next step equals the untouched twin's."""
-    env, twin = make(), make()
-    env.reset(); twin.reset()
-    name, (f0, i0) = env.kernel_name, env.get_state()
-    if callable(what):
-        what(env)
-    else:
-        with pytest.raises(L.AmenvError, match=match):
-            env.set_sensor_noise(what)
-    f1, i1 = env.get_state()
-    assert torch.equal(f0, f1) and torch.equal(i0, i1)
-    assert env.kernel_name == name == env.lib.amenv_kernel_name(env._h).decode() and "+noise" not in name and env.sensor_noise is None
-    assert torch.equal(env.observe(), twin.observe())
-    a = torch.rand(env.num_envs, env.act_dim, generator=torch.Generator().manual_seed(3)).to(env.device)
-    for x, y in zip(env.step(a), twin.step(a)):
-        assert torch.equal(x, y)
-    env.close(); twin.close()
+_refused = functools.partial(H.check_refused, SW, action=_unit_row)
 
 
 def test_refusals_leave_the_handle_untouched():
     _refused(lambda: _env("hexa_arm", "v2", 1, n=64), Z, "rigid")
-    _refused(lambda: amd.GpuWaypointEnv(64, config=_octo_config(64)), Z, "4 or 6 rotors")
+    _refused(lambda: amd.GpuWaypointEnv(64, config=H.octo_config(64)), Z, "4 or 6 rotors")
     _refused(lambda: _env("quad", "v2", 1, n=64, dtype="f64"), Z, "fp32")
     _refused(lambda: _env("quad", "v2", 1, n=64, kernel="team"), Z, "lane-quad")
     _refused(lambda: _env("quad", "v2", 1, n=64, max_episode_steps=2 ** 22 - 1), Z, "max_episode_steps")
@@ -424,18 +300,4 @@ def test_refusals_leave_the_handle_untouched():
 # ---- 9. PPO -----------------------------------------------------------------------------------------------------------------------------
 def test_ppo_fused_rollout_with_sensor_noise():
     n, T = 4096, 16
-    env = amd.GpuWaypointEnv(n, seed=2, max_episode_steps=12, sensor_noise=Z)
-    ref = amd.GpuWaypointEnv(n, seed=2, max_episode_steps=12, kernel="lane", sensor_noise=Z)
-    assert env.kernel_name.endswith("+noise")
-    algo = PPO(env, fused_rollout=True, n_steps=T, n_epochs=2, batch_size=8192, seed=1, bootstrap_truncated=False)
-    ref.reset()
-    algo.learn(T * n)
-    buf = algo.buffer
-    lo, hi = algo.policy.action_low, algo.policy.action_high
-    for t in range(T):   # the first iteration's rollout buffer replays through amenv_step: the policy was trained on the noisy rows
-        o, r, d, _ = ref.step(torch.max(torch.min(buf.actions[t], hi), lo))
-        assert torch.equal(o, buf.obs[t + 1]) and torch.equal(r, buf.rewards[t]) and torch.equal(d, buf.dones[t]), t
-    algo.learn(T * n)
-    assert len(algo.log) == 2 and all(math.isfinite(x) for rec in algo.log for x in rec.values())
-    assert int(buf.dones.sum()) > 0
-    env.close(); ref.close()
+    H.check_ppo_fused_rollout_replays(SW, n, T, sensor_noise=Z)      # the policy was trained on the noisy rows

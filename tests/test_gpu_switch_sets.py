@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import rl_aerial_manipulator_amd as amd
-from rl_aerial_manipulator_amd.ppo import ActorCritic
+from tests.switch_harness import buffers, policy
 
 pytestmark = pytest.mark.gpu
 
@@ -124,13 +124,7 @@ def test_closed_loop_runs_its_switch_set(form, c):
     env, ref = _env(form, c), _env(form, c)
     env.reset(); ref.reset()
     od, start = env.obs_dim, _snap(ref, c)
-    torch.manual_seed(7)
-    pol = ActorCritic(od, 4).cuda().flatten_()
-    with torch.no_grad():
-        pol.log_std.data.fill_(-1.2)
-        pol.action_net.weight.mul_(30.0)
-    b = dict(obs=torch.zeros(T + 1, N, od, device=dev), actions=torch.zeros(T, N, 4, device=dev), logp=torch.zeros(T, N, device=dev),
-             values=torch.zeros(T, N, device=dev), rewards=torch.zeros(T, N, device=dev), dones=torch.zeros(T, N, dtype=torch.uint8, device=dev))
+    pol, b = policy(od), buffers(T, N, od, dev)
     env.rollout_policy(pol.flat_param, T, seed=77, draw0=5, **b)
     torch.cuda.synchronize()
     assert all((SUFFIX[s] in env.kernel_name) == bool(c & s) for s in SUFFIX), env.kernel_name
