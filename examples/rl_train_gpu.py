@@ -59,6 +59,10 @@ def main():
                     help="SB3's target_kl: leave an update once a minibatch's approx_kl exceeds 1.5 X (decided on the GPU, no extra synchronisation; one rank only)")
     ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear"],
                     help="linear: learning_rate = 2e-4 * progress_remaining (SB3's linear schedule), evaluated once per iteration")
+    ap.add_argument("--eval-freq", type=int, default=None, metavar="STEPS",
+                    help="evaluate the deterministic policy every STEPS env steps on a separate eval env, in one launch (SB3's EvalCallback; DESIGN 4s): the "
+                         "learning curve gains eval_mean_reward / eval_success_rate, the best model goes to <save>_best/best_model.zip")
+    ap.add_argument("--eval-envs", type=int, default=1024, help="envs of the eval env (one episode each per evaluation); also used by the final evaluation")
     ap.add_argument("--log-json", default=None, help="write the learning curve (one record per iteration) and the final evaluation to this file")
     ap.add_argument("--warm-start-pid", type=int, default=None, metavar="DAGGER_ROUNDS",
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
@@ -76,18 +80,27 @@ def main():
         cfg = amd._lib.default_config(a.vehicle, a.envs, a.task, n_joints=a.n_joints)
         cfg.vehicle.moment_scale = a.moment_scale
         cfg.seed, cfg.env_id_offset = a.seed, sh.env_id_offset
-    env = amd.GpuWaypointEnv(a.envs, device=local, vehicle=a.vehicle, seed=a.seed, env_id_offset=sh.env_id_offset, config=cfg, task=a.task,
-                             n_joints=a.n_joints)
-    if a.randomize_mass or a.randomize_inertia or a.randomize_thrust:
-        env.set_randomization(amd.DynamicsRandomization.around_one(mass=a.randomize_mass, inertia=a.randomize_inertia, thrust=a.randomize_thrust))
-    if a.rotor_lag is not None:
-        env.set_rotor_lag(amd.RotorLag(a.rotor_lag))
-    if a.sensor_noise is not None:
-        env.set_sensor_noise(amd.SensorNoise(*a.sensor_noise))
-    if a.action_delay is not None:
-        env.set_action_delay(amd.ActionDelay(*a.action_delay))
-    if a.action_history is not None:
-        env.set_action_history(amd.ActionHistory(a.action_history))
+
+    def make_env(n, seed, offset, config):   # the training env, and the eval env that mirrors its vehicle, task and switches under a seed of its own
+        e = amd.GpuWaypointEnv(n, device=local, vehicle=a.vehicle, seed=seed, env_id_offset=offset, config=config, task=a.task, n_joints=a.n_joints)
+        if a.randomize_mass or a.randomize_inertia or a.randomize_thrust:
+            e.set_randomization(amd.DynamicsRandomization.around_one(mass=a.randomize_mass, inertia=a.randomize_inertia, thrust=a.randomize_thrust))
+        if a.rotor_lag is not None:
+            e.set_rotor_lag(amd.RotorLag(a.rotor_lag))
+        if a.sensor_noise is not None:
+            e.set_sensor_noise(amd.SensorNoise(*a.sensor_noise))
+        if a.action_delay is not None:
+            e.set_action_delay(amd.ActionDelay(*a.action_delay))
+        if a.action_history is not None:
+            e.set_action_history(amd.ActionHistory(a.action_history))
+        return e
+
+    env = make_env(a.envs, a.seed, sh.env_id_offset, cfg)
+    ecfg = None
+    if cfg is not None:
+        ecfg = amd._lib.Config.from_buffer_copy(cfg)
+        ecfg.num_envs, ecfg.seed, ecfg.env_id_offset = a.eval_envs, a.seed + 1_000_003, sh.rank * a.eval_envs
+    eval_env = make_env(a.eval_envs, a.seed + 1_000_003, sh.rank * a.eval_envs, ecfg)
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
     lr = 2e-4 if a.lr_schedule == "constant" else (lambda progress_remaining: 2e-4 * progress_remaining)
@@ -111,7 +124,8 @@ def main():
 
     import time
     t0 = time.time()
-    model.learn(a.timesteps, log_fn=show if sh.rank == 0 else None)
+    model.learn(a.timesteps, log_fn=show if sh.rank == 0 else None, **(dict(eval_env=eval_env, eval_freq=a.eval_freq, best_model_save_path=a.save + "_best")
+                                                                     if a.eval_freq else {}))
     seconds = time.time() - t0
     if sh.rank == 0:
         print("saved", model.save(a.save))
@@ -120,8 +134,12 @@ def main():
             mean, var, count = norm.get()
             np.savez(a.save + "_vec_normalize.npz", mean=mean, var=var, count=count, clip_obs=norm.clip_obs, epsilon=norm.epsilon)
             print("saved", a.save + "_vec_normalize.npz")
-        mean_reward, std_reward = amd.evaluate_policy(model, env, n_eval_episodes=max(10, a.envs))      # rl_train.py:60-61
-        print(f"Mean reward: {mean_reward} +/- {std_reward}")
+        # rl_train.py:60-61, in one launch on the eval env: the deterministic bf16 behaviour policy, the normaliser frozen
+        if norm is not None and a.action_history is not None:   # (the one combination the fused forms are not built for)
+            (mean_reward, std_reward), eval_info = amd.evaluate_policy(model, eval_env, n_eval_episodes=max(10, a.eval_envs)), None
+        else:
+            mean_reward, std_reward, eval_info = amd.evaluate_policy(model, eval_env, n_eval_episodes=max(10, a.eval_envs), fused=True, return_info=True)
+        print(f"Mean reward: {mean_reward} +/- {std_reward}  {eval_info}")
         if curve and curve[-1].get("success_rate", 1.0) < 0.5 and a.warm_start_pid is None and not a.resume:
             print("this run stayed on the hover plateau (about one seed in six does within 90 M steps, profiles/r03/ppo_seed_sweep_quad/): "
                   "try another --seed, or --warm-start-pid 3 (actor cloned from the PID baseline), which leaves it from the first iterations")
@@ -132,7 +150,10 @@ def main():
                 json.dump({"command": " ".join(sys.argv), "learn_seconds": seconds, "timesteps": a.timesteps, "timesteps_to_90pct_success": first90,
                            "final_success_rate_mean_of_last_10_iterations": sum(c["success_rate"] for c in curve[-10:]) / max(1, len(curve[-10:])),
                            "n_updates": model.n_updates, "iterations_stopped_early_by_target_kl": sum(c["kl_early_stop"] for c in curve),
-                           "evaluate_policy_mean_reward": mean_reward, "evaluate_policy_std_reward": std_reward, "curve_every_20th_iteration": curve[::20]}, f, indent=1)
+                           "evaluate_policy_mean_reward": mean_reward, "evaluate_policy_std_reward": std_reward, "evaluate_policy_info": eval_info,
+                           "eval_curve": [{k: c[k] for k in ("timesteps", "eval_mean_reward", "eval_std_reward", "eval_success_rate", "eval_ep_len_mean")}
+                                          for c in curve if "eval_mean_reward" in c],
+                           "best_eval_mean_reward": model.best_mean_reward if a.eval_freq else None, "curve_every_20th_iteration": curve[::20]}, f, indent=1)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -414,6 +414,34 @@ int amenv_rollout_policy_norm(amenv* env, amenv_obsnorm* norm, int32_t update, f
                               uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards, uint8_t* dones,
                               uint32_t* info_bits, float* terminal_obs, void* stream);
 
+/* Closed-loop policy EVALUATION in ONE launch (SB3 evaluate_policy / EvalCallback): the loop of amenv_rollout_policy
+ * -- obs -> MLPs (bf16 matrix cores) -> action -> clip -> env step with auto-reset -- with the episode accounting on the device and NO
+ * per-step output.  Always the one-lane-per-env form (the arithmetic of amenv_rollout_policy[_norm] on a handle that runs that form,
+ * applied action for applied action, bit for bit), 16 envs per workgroup (arm vehicles: 64) at every batch size.
+ *   deterministic != 0: the applied action is clip(mean); == 0: the rollout's sample clip(mean + exp(log_std) z), z keyed by
+ *                       (seed, global env id, draw0 + t) exactly as amenv_rollout_policy draws it
+ *   norm               NULL, or the observation normaliser, FROZEN: its statistics are read at entry (amenv_rollout_policy_norm's
+ *                       update == 0 semantics) and are bit-identical afterwards; clip, eps as there (ignored when norm is NULL)
+ *   episodes_per_env   every env counts the first episodes_per_env episodes that END in it during the call; the episode already running
+ *                       at entry counts when it ends.  An env that has filled its quota keeps stepping and adds nothing
+ *   max_steps          the launch ends after max_steps steps, or as soon as every env has filled its quota (decided per workgroup)
+ *   returns  [N][2] f64 device: sum and sum of squares of the counted episodes' returns (each the fp32 Monitor return, added in episode order)
+ *   counts   [N][AMENV_EVAL_COUNT_COLS] i32 device: episodes, length_sum, success, crashed, out_of_bounds, truncated -- a flag column
+ *            counts the episodes whose end bits carry AMENV_INFO_SUCCESS / _CRASHED / _OOB / _TRUNCATED (not exclusive of each other)
+ *   steps_run [1] i32 device: the largest number of steps a workgroup executed; zeroed by the call, on the stream
+ * No host sync, no allocation, graph-capturable.  AFTERWARDS the handle's state is wherever its lanes stopped (envs are mid-episode, and
+ * not all at the same number of steps: amenv_reset before the handle is used for anything that needs a defined start); the Monitor totals
+ * (amenv_stats) are UNTOUCHED: evaluation episodes and steps are not counted there.  Served: what amenv_rollout_policy[_norm] serve through
+ * their one-lane-per-env kernels -- fp32 rigid vehicles with 4 or 6 rotors on every task with every admitted switch set, with or without
+ * the normaliser; the 6-rotor vehicle with a 1..3-link arm on 1..4 waypoints (no normaliser).  AMENV_ERR_INVALID with a message naming
+ * the reason, before anything is launched: NULL pointers; episodes_per_env <= 0 or max_steps <= 0; an fp64 handle; a handle without
+ * AMENV_FLAG_AUTO_RESET; a rotor count other than 4 or 6; a normaliser on an arm vehicle, of the wrong dimension or on another device;
+ * the normaliser together with the action history. */
+#define AMENV_EVAL_COUNT_COLS 6   /* episodes, length_sum, success, crashed, out_of_bounds, truncated */
+int amenv_evaluate_policy(amenv* env, amenv_obsnorm* norm /* NULL: none */, float clip, double eps, const float* flat_params, int32_t deterministic,
+                          uint64_t seed, uint32_t draw0, int32_t episodes_per_env, int32_t max_steps, double* returns /* [N][2]: sum, sum of squares */,
+                          int32_t* counts /* [N][6] */, int32_t* steps_run /* [1], device */, void* stream);
+
 /* ---- per-episode dynamics randomisation --------------------------------------------------------------------
  * For every env and every episode the rigid vehicle's mass, inertia and rotor thrusts are scaled by factors drawn uniformly:
  *   km  mass factor: the body's mass is km * m.  Action scaling keeps the NOMINAL mass (F = a0 * m * g in fp32, as without), so the

@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("AMENV_LIB") or os.path.join(HERE, "libamenv.so")
 
 MAX_ROTORS, MAX_WAYPOINTS, MAX_JOINTS = 8, 4, 3
 MAX_ACTION_DELAY = 8
+EVAL_COUNT_COLS = 6   # amenv_evaluate_policy's counts: episodes, length_sum, success, crashed, out_of_bounds, truncated
 ABI_VERSION = 2
 F32, F64 = 0, 1
 FLAG_AUTO_RESET, FLAG_NAN_GUARD = 1, 2
@@ -125,6 +126,7 @@ SYMBOLS = {
     "amenv_rollout": (C.c_int, [_P, C.c_int32] + [_P] * 6),
     "amenv_rollout_policy": (C.c_int, [_P, C.c_int32, _P, C.c_uint64, C.c_uint32] + [_P] * 9),
     "amenv_rollout_policy_norm": (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_double, C.c_int32, _P, C.c_uint64, C.c_uint32] + [_P] * 9),
+    "amenv_evaluate_policy": (C.c_int, [_P, _P, C.c_float, C.c_double, _P, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "amenv_get_state": (C.c_int, [_P] * 4),
     "amenv_set_state": (C.c_int, [_P] * 4),
     "amenv_observe": (C.c_int, [_P, _P, _P]),

@@ -328,6 +328,34 @@ class GpuWaypointEnv:
             self._check(self.lib.amenv_rollout_policy_norm(self._h, obs_normalizer._h, 1 if update_normalizer else 0, float(obs_normalizer.clip_obs),
                                                            float(obs_normalizer.epsilon), *tail), "amenv_rollout_policy_norm")
 
+    def evaluate_policy(self, flat_params, episodes_per_env, max_steps=None, deterministic=True, seed=0, draw0=0, obs_normalizer=None, reset=True):
+        """Closed-loop EVALUATION in ONE launch (amenv_evaluate_policy, include/amenv.h): the loop of rollout_policy() with the episode
+        accounting on the device and no per-step output.  Every env counts the first `episodes_per_env` episodes that end in it; the launch
+        ends when all have, or after `max_steps` steps (default: episodes_per_env * (max_episode_steps + 2)).  deterministic: the applied
+        action is clip(mean); otherwise rollout_policy()'s sample under (seed, draw0).  obs_normalizer: used FROZEN, never updated.
+        reset=True calls reset() first; with reset=False the episodes already running count when they end.
+
+        Returns device tensors, without a sync: {"returns": [N, 2] f64 (sum, sum of squares of the counted episodes' returns), "counts":
+        [N, 6] i32 (EVAL_COUNT_COLS: episodes, length_sum, success, crashed, out_of_bounds, truncated), "steps_run": 0-dim i32}.
+        Afterwards the env is wherever its lanes stopped (reset() before anything that needs a defined start); stats() is untouched."""
+        if max_steps is None:
+            max_steps = int(episodes_per_env) * (int(self.cfg.task.max_episode_steps) + 2)
+        fp = flat_params.detach()
+        if fp.device != self.device or fp.dtype != torch.float32 or not fp.is_contiguous():
+            raise L.AmenvError("evaluate_policy: flat_params must be a contiguous fp32 tensor on this env's device")
+        if reset:
+            self.reset()
+        n, dev = self.num_envs, self.device
+        out = {"returns": torch.empty(n, 2, dtype=torch.float64, device=dev), "counts": torch.empty(n, L.EVAL_COUNT_COLS, dtype=torch.int32, device=dev),
+               "steps_run": torch.empty((), dtype=torch.int32, device=dev)}
+        nz = obs_normalizer
+        self._check(self.lib.amenv_evaluate_policy(self._h, None if nz is None else nz._h, 0.0 if nz is None else float(nz.clip_obs),
+                                                   0.0 if nz is None else float(nz.epsilon), C.c_void_p(fp.data_ptr()), 1 if deterministic else 0,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFF, int(episodes_per_env), int(max_steps),
+                                                   C.c_void_p(out["returns"].data_ptr()), C.c_void_p(out["counts"].data_ptr()),
+                                                   C.c_void_p(out["steps_run"].data_ptr()), self._stream()), "amenv_evaluate_policy")
+        return out
+
     def observe(self):
         o = torch.empty(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
         self._check(self.lib.amenv_observe(self._h, C.c_void_p(o.data_ptr()), self._stream()), "amenv_observe")

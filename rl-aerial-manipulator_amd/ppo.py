@@ -899,12 +899,36 @@ class PPO:
         rec.update(n_updates=self.n_updates, learning_rate=self.learning_rate, clip_range=self.clip_range)
         return rec
 
-    def learn(self, total_timesteps, log_fn=None, save_freq=None, save_path=None, name_prefix="ppo_model"):
+    def _evaluate(self, eval_env, n_eval_episodes, deterministic):
+        """One fused evaluation for `learn`: (mean, std, info).  Touches neither `_gen` nor `_draw` (a stochastic evaluation draws under its own
+        key, the eval env's seed) nor the normaliser's statistics (used frozen)."""
+        return _evaluate_fused(self, eval_env, n_eval_episodes, deterministic, None, seed=int(eval_env.cfg.seed), draw0=0)
+
+    def learn(self, total_timesteps, log_fn=None, save_freq=None, save_path=None, name_prefix="ppo_model", eval_env=None, eval_freq=None,
+              n_eval_episodes=None, eval_deterministic=True, best_model_save_path=None):
         """`model.learn(total_timesteps, callback=CheckpointCallback(save_freq, save_path, name_prefix))` (v2/rl_train.py:14-18,56):
         alternate rollouts and updates until the whole job has taken `total_timesteps` env steps.  Per iteration one record: losses +
         the Monitor episode statistics of the rollout.  `save_freq` counts env steps of the whole job (SB3 counts `VecEnv.step`
         calls: the reference's 12,500 calls x 8 envs = 100,000 steps); rank 0 writes `<save_path>/<name_prefix>_<steps>_steps.zip`
-        at the first iteration boundary at or past every multiple."""
+        at the first iteration boundary at or past every multiple.
+
+        `eval_env` + `eval_freq` (SB3's `EvalCallback(eval_env, eval_freq=..., n_eval_episodes=..., deterministic=...,
+        best_model_save_path=...)`): at the first iteration boundary at or past every multiple of `eval_freq` env steps (the `save_freq` rule)
+        the policy is evaluated on `eval_env` -- a SEPARATE `GpuWaypointEnv` (the training env is refused: evaluation would cut its
+        episodes) -- in one launch (`evaluate_policy(fused=True)`: the bf16 behaviour policy, the normaliser frozen), `n_eval_episodes`
+        episodes (default: one per eval env).  That iteration's record gains eval_mean_reward, eval_std_reward, eval_success_rate and
+        eval_ep_len_mean; with `best_model_save_path` rank 0 writes `<path>/best_model.zip` whenever the mean is strictly greater than
+        every earlier one (`self.best_mean_reward`).  Evaluation does not perturb training: it consumes neither the minibatch generator
+        nor the action-noise counter and updates no normaliser.  With `dist` every rank evaluates on its own eval env (its shard) and the
+        record says so (eval_scope="rank"): the figures are this rank's, not agreed across ranks."""
+        if eval_env is not None and eval_env is self.env:
+            raise L.AmenvError("learn: eval_env must be a separate GpuWaypointEnv (evaluating on the training env would cut the rollout's episode continuity)")
+        if (eval_env is None) != (not eval_freq):
+            raise L.AmenvError("learn: eval_env and eval_freq go together")
+        n_eval = None if eval_env is None else int(n_eval_episodes if n_eval_episodes is not None else eval_env.num_envs)
+        if not hasattr(self, "best_mean_reward"):
+            self.best_mean_reward = -math.inf
+        next_eval = None if eval_env is None else (self.num_timesteps // int(eval_freq) + 1) * int(eval_freq)
         target = self.num_timesteps + int(total_timesteps)
         next_save = None if not save_freq else (self.num_timesteps // int(save_freq) + 1) * int(save_freq)
         while self.num_timesteps < target:
@@ -921,6 +945,17 @@ class PPO:
             n_ep = max(int(ep["episodes"]), 1)
             rec.update(timesteps=self.num_timesteps, episodes=int(ep["episodes"]), ep_rew_mean=ep["return_sum"] / n_ep,
                        ep_len_mean=ep["length_sum"] / n_ep, success_rate=ep["success"] / n_ep)
+            if next_eval is not None and self.num_timesteps >= next_eval:
+                mean, std, info = self._evaluate(eval_env, n_eval, eval_deterministic)
+                rec.update(eval_mean_reward=mean, eval_std_reward=std, eval_success_rate=info["success_rate"], eval_ep_len_mean=info["ep_len_mean"])
+                if self.world > 1:
+                    rec.update(eval_scope="rank")
+                if mean > self.best_mean_reward:   # SB3's EvalCallback: strictly better
+                    self.best_mean_reward = mean
+                    if best_model_save_path is not None and (self.dist is None or self.dist.get_rank() == 0):
+                        os.makedirs(best_model_save_path, exist_ok=True)
+                        self.save(os.path.join(best_model_save_path, "best_model"))
+                next_eval = (self.num_timesteps // int(eval_freq) + 1) * int(eval_freq)
             self.log.append(rec)
             if log_fn is not None:
                 log_fn(rec)
@@ -1059,11 +1094,60 @@ def clone_pid_policy(env, policy, steps=600, epochs=400, dagger_rounds=0, noise=
     return mse
 
 
-def evaluate_policy(model, env, n_eval_episodes=10, deterministic=True, check_every=64, max_steps=None):
+def reduce_evaluation(returns, counts, steps_run=None):
+    """The numbers of an evaluation from `GpuWaypointEnv.evaluate_policy`'s two arrays (host arrays or tensors): returns [N, 2] (per env: sum
+    and sum of squares of the counted episodes' returns), counts [N, 6] (episodes, length_sum, success, crashed, out_of_bounds, truncated).
+    Returns (mean, std, info) over ALL counted episodes -- std is the population value, as `evaluate_policy` reports it -- with info =
+    {episodes, ep_len_mean, success_rate, crash_rate, oob_rate, truncated_rate, steps_run}.  Raises when no episode was counted."""
+    r = np.asarray(returns.cpu() if torch.is_tensor(returns) else returns, dtype=np.float64).reshape(-1, 2)
+    c = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts).astype(np.int64).reshape(-1, L.EVAL_COUNT_COLS)
+    tot = c.sum(0)
+    k = int(tot[0])
+    if k == 0:
+        raise L.AmenvError("evaluate_policy: no episode finished within the step limit")
+    mean = float(r[:, 0].sum()) / k
+    var = max(float(r[:, 1].sum()) / k - mean * mean, 0.0)
+    info = dict(episodes=k, ep_len_mean=float(tot[1]) / k, success_rate=float(tot[2]) / k, crash_rate=float(tot[3]) / k, oob_rate=float(tot[4]) / k,
+                truncated_rate=float(tot[5]) / k, steps_run=None if steps_run is None else int(steps_run))
+    return mean, math.sqrt(var), info
+
+
+def _evaluate_fused(model, env, n_eval_episodes, deterministic, max_steps, seed=0, draw0=0):
+    """evaluate_policy(fused=True): one launch, one device-to-host transfer -> (mean, std, info)."""
+    policy = getattr(model, "policy", model)
+    if not hasattr(policy, "flat_param"):
+        raise L.AmenvError("evaluate_policy(fused=True) needs a PPO or an ActorCritic (something with flat_param); other models: fused=False")
+    if policy.flat_param is None or policy.flat_param.data_ptr() != policy.log_std.data_ptr():   # (not, or no longer, the parameters' home)
+        policy.flatten_()
+    per_env = -(-int(n_eval_episodes) // env.num_envs)
+    out = env.evaluate_policy(policy.flat_param, per_env, max_steps=max_steps, deterministic=deterministic, seed=seed, draw0=draw0,
+                              obs_normalizer=getattr(model, "obs_normalizer", None), reset=True)
+    # one transfer: the three arrays as raw bytes
+    host = torch.cat([out["returns"].reshape(-1).view(torch.uint8), out["counts"].reshape(-1).view(torch.uint8),
+                      out["steps_run"].reshape(1).view(torch.uint8)]).cpu().numpy()
+    n, nb = env.num_envs, env.num_envs * 16
+    returns = host[:nb].view(np.float64).reshape(n, 2)
+    counts = host[nb:nb + n * 4 * L.EVAL_COUNT_COLS].view(np.int32).reshape(n, L.EVAL_COUNT_COLS)
+    steps_run = int(host[nb + n * 4 * L.EVAL_COUNT_COLS:].view(np.int32)[0])
+    return reduce_evaluation(returns, counts, steps_run)
+
+
+def evaluate_policy(model, env, n_eval_episodes=10, deterministic=True, check_every=64, max_steps=None, fused=False, return_info=False):
     """SB3 `evaluate_policy(model, env, n_eval_episodes)` (v2/rl_train.py:60) on the batched env: every env contributes the
     same number of episodes (ceil(n / num_envs), SB3's rule for vectorised envs), returns (mean, std) of the episode returns.
     `model`: a `PPO`, an `ActorCritic` or anything with `.predict(obs, deterministic)`.  The loop stays on the device; the host
-    looks at the completion counters once every `check_every` steps."""
+    looks at the completion counters once every `check_every` steps.
+
+    fused=True (a `PPO` or an `ActorCritic`): the whole evaluation is ONE launch (`GpuWaypointEnv.evaluate_policy`) and one device-to-host
+    transfer; a `PPO`'s `obs_normalizer` is used frozen.  Same (mean, std) definition over all counted episodes, same error when none
+    finished.  It evaluates the bf16 BEHAVIOUR policy of the fused rollout (the MLPs on the matrix cores), not the fp32
+    modules that `predict` runs: the means differ by ~1e-2 of their scale.  return_info=True (fused only): a third value, the dict of
+    `reduce_evaluation` (episodes, ep_len_mean, success_rate, crash_rate, oob_rate, truncated_rate, steps_run)."""
+    if fused:
+        mean, std, info = _evaluate_fused(model, env, n_eval_episodes, deterministic, max_steps)
+        return (mean, std, info) if return_info else (mean, std)
+    if return_info:
+        raise L.AmenvError("evaluate_policy: return_info needs fused=True (the step-by-step loop keeps no end flags)")
     n = env.num_envs
     per_env = -(-int(n_eval_episodes) // n)
     obs = env.reset()
