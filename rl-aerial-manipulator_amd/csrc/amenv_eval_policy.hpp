@@ -1,8 +1,8 @@
 // amenv_eval_policy.hpp -- closed-loop policy EVALUATION in one launch (amenv_evaluate_policy): the evaluation forms of the two
 // one-lane-per-env rollout kernels, rollout_policy_kernel_rigid (amenv_rigid_policy.hpp) and rollout_policy_kernel_lane (amenv_lane_policy.hpp).
-//   * the same closed loop: the MLP half (wavefronts 0..3, packed bf16 fragments, v_mfma_f32_16x16x32_bf16, the rigid form's two-part first
-//     layer), five barriers per step, the Philox keying (seed, global env id, draw0 + t) and step_lane -- applied action for applied action
-//     the trajectories are the rollout kernels', bit for bit;
+//   * the same closed loop: the MLP half (policy_mlp_waves, amenv_policy_mlp.hpp: the rollout kernels' call with the exit test on), five barriers
+//     per step, the Philox keying (seed, global env id, draw0 + t) and step_lane -- applied action for applied action the trajectories are the
+//     rollout kernels', bit for bit;
 //   * the action: `deterministic` != 0 applies clip(mean) (no draw), otherwise the rollout's sample clip(mean + std z);
 //   * nothing per step goes to global memory (the action delay's ring, which is env state, aside): no obs / actions / logp / values / rewards /
 //     dones / terminal rows.  The MLP input tile in LDS is written every step.  The critic half runs (it is the rollout's code), its value is not read;
@@ -10,7 +10,7 @@
 //     episode return as step_lane hands it out goes into two fp64 sums (sum, sum of squares), the length into an int32 sum, and the counters
 //     episodes / success / crashed / out_of_bounds / truncated go up by one where the end bits carry the AMENV_INFO_* bit (not exclusive).
 //     After its quota a lane keeps stepping (the barriers need it) and adds nothing;
-//   * early exit per workgroup (eval_mlp_waves below holds the argument); steps_run = max over workgroups of the steps executed;
+//   * early exit per workgroup (THE EXIT PROTOCOL, amenv_policy_mlp.hpp, holds the argument); steps_run = max over workgroups of the steps executed;
 //   * one workgroup shape: 16 envs for the rigid vehicles (the finest early exit), 64 envs (one env wavefront) for the arm;
 //   * the Monitor totals (amenv_stats) are not touched: no accumulate_stats call.
 // The env state goes back to the blob at the end as the rollout kernels store it: the handle is wherever its lanes stopped.
@@ -78,124 +78,6 @@ struct EvalAccLds {
   }
 };
 
-// THE EXIT PROTOCOL.  `pend` is one LDS word with ONE writer, lane 0 of the workgroup's only env wavefront:
-//   (w0) before its barrier B0 of step 0 it writes "an env of this workgroup is short of its quota";
-//   (w)  after its barrier B4 of step t it writes the same for the state after step t.
-// EVERY wavefront (the four MLP ones here, the env one through eval_pending) reads `pend` directly behind B0 of step t and leaves the loop when it is 0.
-// Why all five read the same value: the write (w) of step t - 1 (or (w0)) precedes the writer's arrival at B0(t), so it is visible behind B0(t) to
-// all; the NEXT write happens behind the writer's B4(t), which it passes only after every wavefront has arrived at B1(t) .. B4(t), and a wavefront
-// arrives at B1(t) only after it has branched on the value read behind B0(t) (the read has returned by then).  So no read of
-// step t can see the write of step t, all five wavefronts take the same decision in the same iteration, and each has executed exactly 5 t barriers
-// when it leaves: none is left waiting.  max_steps bounds the loop for all alike (a kernel argument).  No barrier follows the loop.
-__device__ __forceinline__ bool eval_pending(const int* pend) { return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int*>(pend)) != 0; }
-
-// The MLP wavefronts' half: rollout_policy_kernel_rigid's (LO: two-part first layer, 4-wide mean rows) or rollout_policy_kernel_lane's (8-wide mean rows),
-// operation for operation, with the exit test behind B0
-template <int NE, bool LO, int MW>
-__device__ __forceinline__ void eval_mlp_waves(const PolicyIO& io, int wave, int lane, int max_steps, const __bf16* xin, const __bf16* xlo, __bf16* h1, __bf16* h2,
-                                               float* meanb, float* valb, const int* pend) {
-  constexpr int NT = NE / 16;
-  __bf16* h3 = h1;
-  uint4 wf[kPolFrags], wlo[LO ? 4 : 1];
-  f32x4 bias[kPolBias];
-  if constexpr (LO) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) wlo[k] = io.pack[size_t(kPolLoBase) + size_t(4 * wave + k) * 64 + lane];
-  }
-  {
-    const uint4* src = io.pack + size_t(wave) * (kPolFrags + kPolBias) * 64 + lane;
-#pragma unroll
-    for (int k = 0; k < kPolFrags; k++) wf[k] = src[k * 64];
-#pragma unroll
-    for (int k = 0; k < kPolBias; k++) { const uint4 b = src[(kPolFrags + k) * 64]; bias[k] = f32x4{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)}; }
-  }
-  const int nrow = lane & 15, kq = lane >> 4;
-  auto load_b = [&](const __bf16* base, int stride, int et, int ks) {   // operand B: 8 consecutive inputs of env 16 et + nrow
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + (16 * et + nrow) * stride + 32 * ks + 8 * kq));
-  };
-  auto store_d = [&](__bf16* base, int stride, int et, int tile16, const f32x4& acc) {   // tanh, 4 consecutive neurons of that env
-    const f32x4 t{fast_tanh(acc[0]), fast_tanh(acc[1]), fast_tanh(acc[2]), fast_tanh(acc[3])};
-    *reinterpret_cast<uint2*>(base + (16 * et + nrow) * stride + 16 * tile16 + 4 * kq) = __builtin_bit_cast(uint2, __builtin_convertvector(t, bf16x4));
-  };
-  const int net23 = wave >> 1;                                  // layers 2, 3: wavefronts 0, 1 the actor, 2, 3 the critic
-  for (int t = 0; t < max_steps; t++) {
-    __syncthreads();                                            // (B0) the observation tile is complete
-    if (!eval_pending(pend)) break;                             // (the exit protocol above: the env wavefront leaves in this iteration too)
-#pragma unroll
-    for (int et = 0; et < NT; et++) {                            // layer 1, K = 32 (LO: hi.hi + hi.lo + lo.hi, amenv_quad_policy.hpp)
-      const bf16x8 B = load_b(xin, kXS, et, 0);
-      bf16x8 Bl;
-      if constexpr (LO) Bl = load_b(xlo, kXS, et, 0);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int T = 4 * wave + j, net = T >> 3;
-        f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (LO) {
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wlo[j]), B, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), Bl, acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), B, acc, 0, 0, 0);
-        store_d(h1 + net * NE * kH1S, kH1S, et, T & 7, acc);
-      }
-    }
-    __syncthreads();                                            // (B1)
-#pragma unroll
-    for (int et = 0; et < NT; et++) {
-      bf16x8 B[4];
-#pragma unroll
-      for (int ks = 0; ks < 4; ks++) B[ks] = load_b(h1 + net23 * NE * kH1S, kH1S, et, ks);
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        f32x4 acc = bias[j];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[4 + 4 * j + ks]), B[ks], acc, 0, 0, 0);
-        store_d(h2 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-      }
-    }
-    __syncthreads();                                            // (B2) h1 has been read by everyone: layer 3 may overwrite it
-#pragma unroll
-    for (int et = 0; et < NT; et++) {
-      bf16x8 B[2];
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) B[ks] = load_b(h2 + net23 * NE * kH2S, kH2S, et, ks);
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        f32x4 acc = bias[2 + j];
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[12 + 2 * j + ks]), B[ks], acc, 0, 0, 0);
-        store_d(h3 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-      }
-    }
-    __syncthreads();                                            // (B3)
-    if (wave < 2) {   // heads: wavefront 0 the action mean, wavefront 1 the value (row 0)
-#pragma unroll
-      for (int et = 0; et < NT; et++) {
-        f32x4 acc = bias[4];
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[16 + ks]), load_b(h3 + wave * NE * kH2S, kH2S, et, ks), acc, 0, 0, 0);
-        if (wave == 0) { if (kq < MW / 4) *reinterpret_cast<float4*>(meanb + (16 * et + nrow) * MW + 4 * kq) = make_float4(acc[0], acc[1], acc[2], acc[3]); }
-        else if (kq == 0) valb[16 * et + nrow] = acc[0];
-      }
-    }
-    __syncthreads();                                            // (B4) means and values are there
-  }
-}
-
-// the four unit normals of Philox block b for (seed, env, draw): the rollout kernels' mapping
-__device__ __forceinline__ void eval_normal4(const PolicyIO& io, uint32_t g_lo, uint32_t g_hi, uint32_t draw, uint32_t b, float* z) {
-  uint32_t w4[4];
-  philox4x32_10(io.seed_lo ^ 0x5bd1e995u, io.seed_hi ^ 0x27d4eb2fu, g_lo, g_hi, draw, b, w4);
-#pragma unroll
-  for (int p = 0; p < 2; p++) {
-    const float u1 = float((w4[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f, u2 = float(w4[2 * p + 1] >> 8) * 5.9604644775390625e-08f;
-    const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1));
-    const float ang = 6.28318530717958647692f * u2;
-    z[2 * p] = rad * __cosf(ang);
-    z[2 * p + 1] = rad * __sinf(ang);
-  }
-}
-
 // Rigid vehicles (4 or 6 rotors, fp32, every task, every admitted switch set, with or without the frozen normaliser): NE = 16
 template <int NROT, int KW, int VAR, bool NORM, unsigned DYN = 0>
 __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int max_steps, const PolicyIO io,
@@ -214,14 +96,14 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
   __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors (amenv_rigid_policy.hpp)
   constexpr bool kNoiseLds = NOISE && NORM;
   __shared__ float zl[kNoiseLds ? 13 * NE : 1];
-  __shared__ int pend;                                                    // the exit protocol's word (eval_mlp_waves)
+  __shared__ int pend;                                                    // the exit protocol's word (policy_mlp_waves)
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
   if constexpr (NORM) {
     for (int j = int(threadIdx.x); j < OD; j += int(blockDim.x)) { md[j] = N.buf[j]; md[OD + j] = 1.0 / sqrt(N.buf[OD + j] + N.eps); }
     __syncthreads();
   }
-  if (wave < 4) { eval_mlp_waves<NE, true, 4>(io, wave, lane, max_steps, xin, xlo, h1, h2, meanb, valb, &pend); return; }
+  if (wave < 4) { policy_mlp_waves<NE, true, 4, true>(io, wave, lane, max_steps, xin, xlo, h1, h2, meanb, valb, &pend); return; }
   // ---- the env wavefront: lanes 0..15 an env each; the others only pass the barriers
   const int el = lane;
   const bool mine = el < NE;
@@ -297,7 +179,7 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
   int t = 0;
   for (; t < max_steps; t++) {
     __syncthreads();   // (B0) observation tile published
-    if (!eval_pending(&pend)) break;                              // the exit protocol (eval_mlp_waves): the MLP wavefronts leave in this iteration too
+    if (!eval_pending(&pend)) break;                              // the exit protocol (policy_mlp_waves): the MLP wavefronts leave in this iteration too
     __syncthreads();   // (B1)
     __syncthreads();   // (B2)
     __syncthreads();   // (B3)
@@ -308,12 +190,12 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
       float act[AD] = {m.x, m.y, m.z, m.w};
       if (E.deterministic == 0) {   // the rollout's sample: raw = mean + std z
         float z[4];
-        eval_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
+        policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
 #pragma unroll
         for (int c = 0; c < AD; c++) act[c] = fma_(std_a[c], z[c], act[c]);
       }
 #pragma unroll
-      for (int c = 0; c < AD; c++) act[c] = clamp_(act[c], c == 0 ? 0.0f : -1.0f, c == 0 ? 2.0f : 1.0f);
+      for (int c = 0; c < AD; c++) act[c] = policy_clip(act[c], c);
       DelayLane dl; float4 given;
       if constexpr (DELAY) {
         given = make_float4(act[0], act[1], act[2], act[3]);
@@ -375,10 +257,10 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_lane(void* __restr
   __shared__ float valb[NE];
   __shared__ double accd[2 * NE];                                         // the lanes' sums (EvalAccLds)
   __shared__ int32_t accc[5 * NE];
-  __shared__ int pend;                                                    // the exit protocol's word (eval_mlp_waves)
+  __shared__ int pend;                                                    // the exit protocol's word (policy_mlp_waves)
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
-  if (wave < 4) { eval_mlp_waves<NE, false, 8>(io, wave, lane, max_steps, xin, nullptr, h1, h2, meanb, valb, &pend); return; }
+  if (wave < 4) { policy_mlp_waves<NE, false, 8, true>(io, wave, lane, max_steps, xin, nullptr, h1, h2, meanb, valb, &pend); return; }
   // ---- the env wavefront: one lane per env
   const int el = lane;
   const int i = int(blockIdx.x) * NE + el;
@@ -418,7 +300,7 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_lane(void* __restr
   int t = 0;
   for (; t < max_steps; t++) {
     __syncthreads();   // (B0) observation tile published
-    if (!eval_pending(&pend)) break;                              // the exit protocol (eval_mlp_waves): the MLP wavefronts leave in this iteration too
+    if (!eval_pending(&pend)) break;                              // the exit protocol (policy_mlp_waves): the MLP wavefronts leave in this iteration too
     __syncthreads();   // (B1)
     __syncthreads();   // (B2)
     __syncthreads();   // (B3)
@@ -430,13 +312,13 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_lane(void* __restr
     }
     if (E.deterministic == 0) {   // the rollout's sample: Philox block 0 -> wrench entries, block 1 -> joints
       float z[8];
-      eval_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
-      eval_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 1u, z + 4);
+      policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
+      policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 1u, z + 4);
 #pragma unroll
       for (int c = 0; c < 4 + PNJ; c++) act[c] = fma_(std_a[c], z[c], act[c]);
     }
 #pragma unroll
-    for (int c = 0; c < 4; c++) act[c] = clamp_(act[c], c == 0 ? 0.0f : -1.0f, c == 0 ? 2.0f : 1.0f);
+    for (int c = 0; c < 4; c++) act[c] = policy_clip(act[c], c);
 #pragma unroll
     for (int c = 0; c < 3; c++) act[4 + c] = c < PNJ ? clamp_(act[4 + c], -1.0f, 1.0f) : 0.0f;   // a phantom joint: no command
     float reward; bool was_reset; int ep_len; float ep_ret;

@@ -3,13 +3,13 @@
 // for the environment.  The lane-team form spends 16 lanes on an env to be short; from ~8192 envs on every SIMD holds several of its
 // wavefronts and the step is bound by their vector-ALU work (~360 wave-instructions per env-step against ~60 for a lane that owns an env).
 //   * a workgroup = EW x 64 envs (EW = 1 or 2 env wavefronts, 320 or 384 threads): wavefronts 4.. integrate them (the lane kernel's
-//     step_lane: same arithmetic as amenv_step's lane / helper kernels, bit for bit), wavefronts 0..3 run the two MLPs on the matrix
-//     cores exactly as the team kernel does (same packed fragments in registers, bf16 inputs, fp32 accumulation, D = W . X^T) over the
-//     workgroup's 4 EW column tiles of 16 envs.  The env code needs ~210 registers, so a SIMD holds two wavefronts and a CU one
-//     workgroup: EW = 2 covers 32768 envs with one wave of workgroups on the 256 CUs;
+//     step_lane: same arithmetic as amenv_step's lane / helper kernels, bit for bit), wavefronts 0..3 run the two MLPs over the workgroup's
+//     4 EW column tiles of 16 envs (amenv_policy_mlp.hpp's policy_mlp_waves, single-part first layer: the team kernel's network).  The env
+//     code needs ~210 registers, so a SIMD holds two wavefronts and a CU one workgroup: EW = 2 covers 32768 envs with one wave of workgroups
+//     on the 256 CUs;
 //   * the two halves alternate: five workgroup barriers per step, activations / action means / values through LDS;
-//   * the action noise is drawn with the team kernel's Philox keying and Box-Muller mapping, the log-probability is summed in its order:
-//     for the same observation both kernels produce the same action, bit for bit;
+//   * the action noise is policy_normal4's (block 0 -> wrench entries, block 1 -> joints: the team kernel's mapping), the log-probability is
+//     summed in the team kernel's order: for the same observation both kernels produce the same action, bit for bit;
 //   * KW = 1 (one waypoint) or AMENV_MAX_WAYPOINTS (2..4), any joint axes (step_lane branches on them);
 //   * PNJ = the caller's joints.  A 1- or 2-link arm runs, inside, the 3-joint vehicle with phantom links (amenv_create pad_arm_config),
 //     exactly as amenv_step does; the kernel publishes the CALLER's rows: obs / terminal_obs 23 + 2 PNJ wide in arm_cut_obs_kernel's
@@ -19,7 +19,7 @@
 //     the lane that wrote it.
 #pragma once
 #include "amenv_kernels.hpp"
-#include "amenv_team_policy.hpp"
+#include "amenv_policy_mlp.hpp"
 
 namespace amenv_dev {
 
@@ -31,7 +31,7 @@ template <int NROT, int EW, int KW, int PNJ>
 __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps, const PolicyIO io,
                                                                   unsigned long long* __restrict__ stats, const HotParams<float, NROT> P, const ColdParams C,
                                                                   const ArmArg<float, 3> AA, float* __restrict__ term29) {
-  constexpr int OD = 29, AD = 7, NE = 64 * EW, NT = 4 * EW, NJ = 3;   // envs / 16-env column tiles per workgroup
+  constexpr int OD = 29, AD = 7, NE = 64 * EW, NJ = 3;   // envs per workgroup (4 EW column tiles of 16)
   constexpr int POD = 23 + 2 * PNJ, PAD = 4 + PNJ;                      // the caller's row widths
   static_assert(PNJ >= 1 && PNJ <= 3, "1..3 public joints");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -39,86 +39,9 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
   __shared__ __attribute__((aligned(16))) __bf16 h2[2 * NE * kH2S];
   __shared__ __attribute__((aligned(16))) float meanb[NE * 8];
   __shared__ float valb[NE];
-  __bf16* h3 = h1;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
-  if (wave < 4) {
-    // ---- MLP wavefronts: this wavefront's neuron subset (as packed for the team kernel) for all four column tiles of 16 envs
-    uint4 wf[kPolFrags];
-    f32x4 bias[kPolBias];
-    {
-      const uint4* src = io.pack + size_t(wave) * (kPolFrags + kPolBias) * 64 + lane;
-#pragma unroll
-      for (int k = 0; k < kPolFrags; k++) wf[k] = src[k * 64];
-#pragma unroll
-      for (int k = 0; k < kPolBias; k++) { const uint4 b = src[(kPolFrags + k) * 64]; bias[k] = f32x4{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)}; }
-    }
-    const int nrow = lane & 15, kq = lane >> 4;
-    auto load_b = [&](const __bf16* base, int stride, int et, int ks) {   // operand B: 8 consecutive inputs of env 16 et + nrow
-      return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + (16 * et + nrow) * stride + 32 * ks + 8 * kq));
-    };
-    auto store_d = [&](__bf16* base, int stride, int et, int tile16, const f32x4& acc) {   // tanh, 4 consecutive neurons of that env
-      const f32x4 t{fast_tanh(acc[0]), fast_tanh(acc[1]), fast_tanh(acc[2]), fast_tanh(acc[3])};
-      *reinterpret_cast<uint2*>(base + (16 * et + nrow) * stride + 16 * tile16 + 4 * kq) = __builtin_bit_cast(uint2, __builtin_convertvector(t, bf16x4));
-    };
-    const int net23 = wave >> 1;                                  // layers 2, 3: wavefronts 0, 1 the actor, 2, 3 the critic
-    for (int t = 0; t < n_steps; t++) {
-      __syncthreads();                                            // (B0) the observation tile is complete
-#pragma unroll
-      for (int et = 0; et < NT; et++) {                            // layer 1: 4 tiles of the combined [actor | critic] 256 neurons, K = 32
-        const bf16x8 B = load_b(xin, kXS, et, 0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const int T = 4 * wave + j, net = T >> 3;
-          f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), B, acc, 0, 0, 0);
-          store_d(h1 + net * NE * kH1S, kH1S, et, T & 7, acc);
-        }
-      }
-      __syncthreads();                                            // (B1)
-#pragma unroll
-      for (int et = 0; et < NT; et++) {
-        bf16x8 B[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) B[ks] = load_b(h1 + net23 * NE * kH1S, kH1S, et, ks);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          f32x4 acc = bias[j];
-#pragma unroll
-          for (int ks = 0; ks < 4; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[4 + 4 * j + ks]), B[ks], acc, 0, 0, 0);
-          store_d(h2 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-        }
-      }
-      __syncthreads();                                            // (B2) h1 has been read by everyone: layer 3 may overwrite it
-#pragma unroll
-      for (int et = 0; et < NT; et++) {
-        bf16x8 B[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) B[ks] = load_b(h2 + net23 * NE * kH2S, kH2S, et, ks);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          f32x4 acc = bias[2 + j];
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[12 + 2 * j + ks]), B[ks], acc, 0, 0, 0);
-          store_d(h3 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-        }
-      }
-      __syncthreads();                                            // (B3)
-      if (wave < 2) {   // heads: wavefront 0 the action mean (rows 0..6), wavefront 1 the value (row 0)
-#pragma unroll
-        for (int et = 0; et < NT; et++) {
-          f32x4 acc = bias[4];
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[16 + ks]), load_b(h3 + wave * NE * kH2S, kH2S, et, ks), acc, 0, 0, 0);
-          if (wave == 0) { if (kq < 2) *reinterpret_cast<float4*>(meanb + (16 * et + nrow) * 8 + 4 * kq) = make_float4(acc[0], acc[1], acc[2], acc[3]); }
-          else if (kq == 0) valb[16 * et + nrow] = acc[0];
-        }
-      }
-      __syncthreads();                                            // (B4) means and values are there
-    }
-    return;
-  }
+  if (wave < 4) { policy_mlp_waves<NE, false, 8, false>(io, wave, lane, n_steps, xin, nullptr, h1, h2, meanb, valb, nullptr); return; }
   // ---- env wavefronts: one lane per env
   const int el = (wave - 4) * 64 + lane;                          // env within the workgroup
   const int i = int(blockIdx.x) * NE + el;
@@ -171,34 +94,22 @@ __global__ __launch_bounds__(256 + 64 * EW) void rollout_policy_kernel_lane(void
       mean[0] = m0.x; mean[1] = m0.y; mean[2] = m0.z; mean[3] = m0.w; mean[4] = m1.x; mean[5] = m1.y; mean[6] = m1.z; mean[7] = m1.w;
     }
     const float value = valb[el];
-    // ---- sample: raw = mean + std z, logp, clip (DiagGaussianDistribution + collect_rollouts' clip); Philox block 0 -> wrench entries,
-    // block 1 -> joints, pairs (w0, w1) -> entries 0 (cos), 1 (sin), (w2, w3) -> entries 2, 3: the team kernel's mapping
+    // ---- sample: raw = mean + std z, logp, clip (DiagGaussianDistribution + collect_rollouts' clip); Philox block 0 -> wrench entries, 1 -> joints
     float z[8];
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-      uint32_t w4[4];
-      philox4x32_10(io.seed_lo ^ 0x5bd1e995u, io.seed_hi ^ 0x27d4eb2fu, g_lo, g_hi, io.draw0 + uint32_t(t), uint32_t(b), w4);
-#pragma unroll
-      for (int p = 0; p < 2; p++) {
-        const float u1 = float((w4[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f, u2 = float(w4[2 * p + 1] >> 8) * 5.9604644775390625e-08f;
-        const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1));
-        const float ang = 6.28318530717958647692f * u2;
-        z[4 * b + 2 * p] = rad * __cosf(ang);
-        z[4 * b + 2 * p + 1] = rad * __sinf(ang);
-      }
-    }
+    policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
+    policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 1u, z + 4);
     float act[AD], raw[AD], lp[4];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       raw[c] = fma_(std_a[c], z[c], mean[c]);
-      lp[c] = fma_(-0.5f * z[c], z[c], -ls_a[c]) - 0.918938533204672742f;
-      act[c] = clamp_(raw[c], c == 0 ? 0.0f : -1.0f, c == 0 ? 2.0f : 1.0f);
+      lp[c] = fma_(-0.5f * z[c], z[c], -ls_a[c]) - kHalfLog2Pi;
+      act[c] = policy_clip(raw[c], c);
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       if (c < PNJ) {
         raw[4 + c] = fma_(std_a[4 + c], z[4 + c], mean[4 + c]);
-        lp[c] = lp[c] + (fma_(-0.5f * z[4 + c], z[4 + c], -ls_a[4 + c]) - 0.918938533204672742f);
+        lp[c] = lp[c] + (fma_(-0.5f * z[4 + c], z[4 + c], -ls_a[4 + c]) - kHalfLog2Pi);
         act[4 + c] = clamp_(raw[4 + c], -1.0f, 1.0f);
       } else {
         act[4 + c] = 0.0f;                                        // a phantom joint: no command

@@ -114,7 +114,7 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, cons
 __host__ __device__ constexpr int prod_a(int i) { return (0x001102 >> (4 * i)) & 15; }   // A parts 2 0 1 1 0 0
 __host__ __device__ constexpr int prod_b(int i) { return (0x010120 >> (4 * i)) & 15; }   // B parts 0 2 1 0 1 0
 
-// trunk / head parameter offsets inside the flat buffer (SB3 order, see amenv_team_policy.hpp PolLayout)
+// trunk / head parameter offsets inside the flat buffer (SB3 order, see amenv_policy_mlp.hpp PolLayout)
 struct MlpNet {
   const float *W1, *b1, *W2, *b2, *W3, *b3, *W4, *b4;   // row-major originals
   int n_out;                                             // head rows: A (actor) or 1 (critic)

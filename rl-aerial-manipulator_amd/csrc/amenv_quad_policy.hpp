@@ -1,13 +1,13 @@
 // amenv_quad_policy.hpp -- closed-loop rollout in ONE launch for the RIGID vehicles (the reference's quadrotor, the hexacopter): observation ->
 // actor / critic MLPs -> Gaussian sample -> clip -> env step, T times (v2/rl_train.py:38-56 through SB3's collect_rollouts; the reference trains
-// exactly this vehicle, runsim_scaledObs.py:15 flies its checkpoint).  The MLP part is amenv_team_policy.hpp's: a 256-thread workgroup = 16 envs,
-// the two [128, 64, 64] tanh MLPs on v_mfma_f32_16x16x32_bf16 with the weight fragments resident in the four wavefronts' registers (20 inputs +
-// bias column = one K step), activations through LDS, 5 barriers per step.  The env part is amenv_quad.hpp's lane-quad step (4 lanes per env, DPP):
+// exactly this vehicle, runsim_scaledObs.py:15 flies its checkpoint).  The network is amenv_policy_mlp.hpp's (two-part first layer; 20 inputs +
+// bias column = one K step) on a 256-thread workgroup = 16 envs.  The env part is amenv_quad.hpp's lane-quad step (4 lanes per env, DPP):
 // the workgroup's 16 envs are ONE wavefront's work, so wavefront 0 samples, steps and publishes while the other three wait at the step's barrier.
-// Same Philox keying / Box-Muller mapping / clip as the lane-team form (block 0 = the four wrench entries).
+// The shared forward pass lives in amenv_policy_mlp.hpp (policy_mlp_waves); this kernel keeps its own copy of the layers: wavefront 0 runs the MLP
+// AND holds the env state in registers, so it cannot call a function that owns the step loop.
 #pragma once
+#include "amenv_policy_mlp.hpp"
 #include "amenv_quad.hpp"
-#include "amenv_team_policy.hpp"
 
 namespace amenv_dev {
 
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel_quad(void* __restri
   quad_load(tile, i, L, E);                                  // (every wavefront loads; only wavefront 0 uses and stores it)
   const uint4 ac = io.pack[size_t(4) * (kPolFrags + kPolBias) * 64 + L.lane];
   const float std_w = __uint_as_float(ac.x), ls_w = __uint_as_float(ac.y);
-  const float lo_w = L.cc == 0 ? 0.0f : -1.0f, hi_w = L.cc == 0 ? 2.0f : 1.0f;
+  const float lo_w = policy_box_lo(L.cc), hi_w = policy_box_hi(L.cc);
   const int64_t gid = C.gid0 + i;
   const uint32_t g_lo = uint32_t(uint64_t(gid)), g_hi = uint32_t(uint64_t(gid) >> 32);
   const size_t n = size_t(n_envs);
@@ -82,10 +82,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel_quad(void* __restri
   bool any_reset = false;
   for (int t = 0; t < n_steps; t++) {
     __syncthreads();                                            // the observation tile is complete
-    {   // layer 1: 4 tiles of the combined [actor | critic] 256 neurons, K = 32 (20 inputs + bias column + padding).  The observation enters as
-        // TWO bf16 parts (x = hi + lo to ~2^-17 relative): a trained controller's first layer amplifies the 2^-9 rounding of a single bf16 input
-        // to ~0.1 in the action (measured on the reference checkpoint, 0.03 with the input split); so do the first layer's weights (W1 = hi + lo):
-        // three products hi.hi + hi.lo + lo.hi per tile, the first layer at ~fp32 accuracy for two more MFMAs
+    {   // layer 1: 4 tiles of the combined [actor | critic] 256 neurons, K = 32 (20 inputs + bias column + padding), two-part: hi.hi + hi.lo + lo.hi
       const bf16x8 B = load_b(xin, kXS, 0), Bl = load_b(xlo, kXS, 0);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(256) void rollout_policy_kernel_quad(void* __restri
         z = rad * ((L.cc & 1) ? __sinf(ang) : __cosf(ang));
       }
       const float raw = fma_(std_w, z, mean_w);
-      const float logp = sum4(fma_(-0.5f * z, z, -ls_w) - 0.918938533204672742f);
+      const float logp = sum4(fma_(-0.5f * z, z, -ls_w) - kHalfLog2Pi);
       const float act = clamp_(raw, lo_w, hi_w);
       const size_t tn = size_t(t) * n;
       if (active) {

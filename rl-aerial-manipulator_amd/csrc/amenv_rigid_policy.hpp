@@ -4,10 +4,9 @@
 //   * env part: ONE LANE PER ENV, step_lane<float, NROT, KW, VAR, 0> -- the arithmetic of amenv_step's LANE / HELPER kernels, so replaying the
 //     recorded clipped actions through amenv_step on such a handle reproduces every row bit for bit.  Tile addressing is by the env index
 //     (i & 63), the blob layout is the step kernels';
-//   * MLP part: amenv_quad_policy.hpp's -- packed weight fragments resident in four wavefronts, v_mfma_f32_16x16x32_bf16, five barriers
-//     per step, and the rigid-vehicle first layer: two-part bf16 inputs (xin / xlo) and two-part first-layer weights (wlo, kPolLoBase).
-//     one bf16 rounding of the input moved a trained controller's action by up to 0.107; normalised inputs reach +-10;
-//   * sampling: the quad form's Philox keying (block 0 = the four wrench entries), Box-Muller mapping and log-prob association: for the same
+//   * MLP part: amenv_policy_mlp.hpp's policy_mlp_waves with the two-part first layer (xin / xlo; DESIGN 4g: one bf16 rounding of the input
+//     moved a trained controller's action by up to 0.107; normalised inputs reach +-10);
+//   * sampling: policy_normal4, block 0 = the four wrench entries; the log-probability is summed in the lane-quad form's association: for the same
 //     observation both forms draw the same noise;
 //   * workgroup = NE envs: NE = 16 (one 16-env column tile, 256 workgroups at 4096 envs: every CU busy) or NE = 64 EW (EW = 1, 2 env
 //     wavefronts; the large-batch shape of amenv_lane_policy.hpp).  Wavefronts 0..3 run the MLPs, wavefronts 4.. the envs; with NE = 16
@@ -20,7 +19,7 @@
 #pragma once
 #include "amenv_kernels.hpp"
 #include "amenv_obsnorm.hpp"
-#include "amenv_team_policy.hpp"
+#include "amenv_policy_mlp.hpp"
 
 namespace amenv_dev {
 
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
                                                                                          const DynArg<float, NROT, DYN> DA) {
   static_assert(dyn_admitted<float, 0>(DYN), "a switch set that is not built (amenv_model.hpp)");
   constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
-  constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, NT = NE / 16, EW = NE < 64 ? 1 : NE / 64;   // 16-env column tiles / env wavefronts per workgroup
+  constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, EW = NE < 64 ? 1 : NE / 64;   // env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
   __shared__ __attribute__((aligned(16))) __bf16 xlo[NE * kXS];          // the observation's second bf16 part (x - bf16(x))
@@ -60,94 +59,13 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors, [2 NROT + 2][NE]: each lane reads and writes its own column
   constexpr bool kNoiseLds = NOISE && NORM;
   __shared__ float zl[kNoiseLds ? 13 * NE : 1];                           // sensor noise: the perturbed copy of the 13 state numbers, [13][NE]
-  __bf16* h3 = h1;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
   if constexpr (NORM) {
     for (int j = int(threadIdx.x); j < OD; j += int(blockDim.x)) { md[j] = N.buf[j]; md[OD + j] = 1.0 / sqrt(N.buf[OD + j] + N.eps); }
     __syncthreads();
   }
-  if (wave < 4) {
-    // ---- MLP wavefronts: this wavefront's neuron subset for every 16-env column tile
-    uint4 wf[kPolFrags], wlo[4];
-    f32x4 bias[kPolBias];
-#pragma unroll
-    for (int k = 0; k < 4; k++) wlo[k] = io.pack[size_t(kPolLoBase) + size_t(4 * wave + k) * 64 + lane];
-    {
-      const uint4* src = io.pack + size_t(wave) * (kPolFrags + kPolBias) * 64 + lane;
-#pragma unroll
-      for (int k = 0; k < kPolFrags; k++) wf[k] = src[k * 64];
-#pragma unroll
-      for (int k = 0; k < kPolBias; k++) { const uint4 b = src[(kPolFrags + k) * 64]; bias[k] = f32x4{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)}; }
-    }
-    const int nrow = lane & 15, kq = lane >> 4;
-    auto load_b = [&](const __bf16* base, int stride, int et, int ks) {   // operand B: 8 consecutive inputs of env 16 et + nrow
-      return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + (16 * et + nrow) * stride + 32 * ks + 8 * kq));
-    };
-    auto store_d = [&](__bf16* base, int stride, int et, int tile16, const f32x4& acc) {   // tanh, 4 consecutive neurons of that env
-      const f32x4 t{fast_tanh(acc[0]), fast_tanh(acc[1]), fast_tanh(acc[2]), fast_tanh(acc[3])};
-      *reinterpret_cast<uint2*>(base + (16 * et + nrow) * stride + 16 * tile16 + 4 * kq) = __builtin_bit_cast(uint2, __builtin_convertvector(t, bf16x4));
-    };
-    const int net23 = wave >> 1;                                  // layers 2, 3: wavefronts 0, 1 the actor, 2, 3 the critic
-    for (int t = 0; t < n_steps; t++) {
-      __syncthreads();                                            // (B0) the observation tile is complete
-#pragma unroll
-      for (int et = 0; et < NT; et++) {                            // layer 1, K = 32: hi.hi + hi.lo + lo.hi (amenv_quad_policy.hpp)
-        const bf16x8 B = load_b(xin, kXS, et, 0), Bl = load_b(xlo, kXS, et, 0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const int T = 4 * wave + j, net = T >> 3;
-          f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f};
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wlo[j]), B, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), Bl, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[j]), B, acc, 0, 0, 0);
-          store_d(h1 + net * NE * kH1S, kH1S, et, T & 7, acc);
-        }
-      }
-      __syncthreads();                                            // (B1)
-#pragma unroll
-      for (int et = 0; et < NT; et++) {
-        bf16x8 B[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) B[ks] = load_b(h1 + net23 * NE * kH1S, kH1S, et, ks);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          f32x4 acc = bias[j];
-#pragma unroll
-          for (int ks = 0; ks < 4; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[4 + 4 * j + ks]), B[ks], acc, 0, 0, 0);
-          store_d(h2 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-        }
-      }
-      __syncthreads();                                            // (B2) h1 has been read by everyone: layer 3 may overwrite it
-#pragma unroll
-      for (int et = 0; et < NT; et++) {
-        bf16x8 B[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) B[ks] = load_b(h2 + net23 * NE * kH2S, kH2S, et, ks);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          f32x4 acc = bias[2 + j];
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[12 + 2 * j + ks]), B[ks], acc, 0, 0, 0);
-          store_d(h3 + net23 * NE * kH2S, kH2S, et, (2 * wave + j) & 3, acc);
-        }
-      }
-      __syncthreads();                                            // (B3)
-      if (wave < 2) {   // heads: wavefront 0 the action mean (rows 0..3), wavefront 1 the value (row 0)
-#pragma unroll
-        for (int et = 0; et < NT; et++) {
-          f32x4 acc = bias[4];
-#pragma unroll
-          for (int ks = 0; ks < 2; ks++)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[16 + ks]), load_b(h3 + wave * NE * kH2S, kH2S, et, ks), acc, 0, 0, 0);
-          if (wave == 0) { if (kq == 0) *reinterpret_cast<float4*>(meanb + (16 * et + nrow) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]); }
-          else if (kq == 0) valb[16 * et + nrow] = acc[0];
-        }
-      }
-      __syncthreads();                                            // (B4) means and values are there
-    }
-    return;
-  }
+  if (wave < 4) { policy_mlp_waves<NE, true, 4, false>(io, wave, lane, n_steps, xin, xlo, h1, h2, meanb, valb, nullptr); return; }
   // ---- env wavefronts: one lane per env (NE = 16: lanes 0..15; the others only pass the barriers)
   const int el = (wave - 4) * 64 + lane;                          // env within the workgroup
   const bool mine = NE >= 64 || el < NE;
@@ -239,26 +157,15 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     const float4 m = *reinterpret_cast<const float4*>(meanb + el * 4);
     const float mean[4] = {m.x, m.y, m.z, m.w};
     const float value = valb[el];
-    // ---- sample: raw = mean + std z, logp, clip; Philox block 0, pairs (w0, w1) -> entries 0 (cos), 1 (sin), (w2, w3) -> 2, 3
+    // ---- sample: raw = mean + std z, logp, clip; Philox block 0
     float z[4];
-    {
-      uint32_t w4[4];
-      philox4x32_10(io.seed_lo ^ 0x5bd1e995u, io.seed_hi ^ 0x27d4eb2fu, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, w4);
-#pragma unroll
-      for (int p = 0; p < 2; p++) {
-        const float u1 = float((w4[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f, u2 = float(w4[2 * p + 1] >> 8) * 5.9604644775390625e-08f;
-        const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1));
-        const float ang = 6.28318530717958647692f * u2;
-        z[2 * p] = rad * __cosf(ang);
-        z[2 * p + 1] = rad * __sinf(ang);
-      }
-    }
+    policy_normal4(io, g_lo, g_hi, io.draw0 + uint32_t(t), 0u, z);
     float act[AD], raw[AD], lp[AD];
 #pragma unroll
     for (int c = 0; c < AD; c++) {
       raw[c] = fma_(std_a[c], z[c], mean[c]);
-      lp[c] = fma_(-0.5f * z[c], z[c], -ls_a[c]) - 0.918938533204672742f;
-      act[c] = clamp_(raw[c], c == 0 ? 0.0f : -1.0f, c == 0 ? 2.0f : 1.0f);
+      lp[c] = fma_(-0.5f * z[c], z[c], -ls_a[c]) - kHalfLog2Pi;
+      act[c] = policy_clip(raw[c], c);
     }
     const float logp = (lp[0] + lp[1]) + (lp[2] + lp[3]);       // (the quad form's sum4 association)
     const size_t tn = size_t(t) * n;

@@ -12,7 +12,11 @@ the kernel's own symbol, and the function index inside local labels (.LBB12_3, .
 their place, the bools read as a bit mask (first bool = bit 0): `k<float, 4, true, true, false, false>` -> `k<float, 4, 3u>`.
 
 Prints the counts, every kernel that is in one file only, and for every kernel that differs both sets of resource numbers and the first
-differing line; exit status 1 unless the two files hold the same kernels with identical text and metadata."""
+differing line; exit status 1 unless the two files hold the same kernels with identical text and metadata.
+
+--brief, for a library whose kernels differ by the hundred: one line per differing kernel with the resource numbers that moved (`a>b`; every
+number of RES and the occupancy that is not listed is equal), the differing kernels in which none moved counted per kernel name, and with
+--list-same the identical kernels counted per kernel name."""
 import argparse
 import re
 import subprocess
@@ -91,11 +95,15 @@ def load(path, nfold):
     return kernels
 
 
-def resources(text):
+def numbers(text):
     meta = text[text.index("; metadata"):]
     got = {k: next((x.split()[-1] for x in meta if x.strip(" -").startswith("." + k + ":")), "?") for k in RES}
     got["occupancy"] = next((x.split()[-1] for x in text if x.startswith("; Occupancy:")), "?")
-    return " ".join(f"{k}={v}" for k, v in got.items())
+    return got
+
+
+def resources(text):
+    return " ".join(f"{k}={v}" for k, v in numbers(text).items())
 
 
 if __name__ == "__main__":
@@ -104,6 +112,7 @@ if __name__ == "__main__":
     ap.add_argument("b")
     ap.add_argument("--fold-bools", type=int, default=0, metavar="N")
     ap.add_argument("--list-same", action="store_true", help="also list the kernels that are identical, with their resource numbers")
+    ap.add_argument("--brief", action="store_true", help="one line per differing kernel; --list-same counts the identical ones per kernel name")
     a = ap.parse_args()
     A, B = load(a.a, a.fold_bools), load(a.b, 0)
     both = sorted(set(A) & set(B))
@@ -113,11 +122,23 @@ if __name__ == "__main__":
     for tag, only in (("A", sorted(set(A) - set(B))), ("B", sorted(set(B) - set(A)))):
         for k in only:
             print(f"only in {tag}: {k}")
-    for k in diff:
+    if a.brief:
+        moved = {k: " ".join(f"{r}={x}>{y}" for (r, x), y in zip(numbers(A[k]).items(), numbers(B[k]).values()) if x != y) for k in diff}
+        for k in diff:
+            if moved[k]:
+                print(f"different: {k} | {moved[k]}")
+        names = [k.split("<")[0] for k in diff if not moved[k]]
+        for k in sorted(set(names)):
+            print(f"different, every resource number equal: {names.count(k)} x {k}")
+    for k in () if a.brief else diff:
         at = next((i for i, (x, y) in enumerate(zip(A[k], B[k])) if x != y), min(len(A[k]), len(B[k])))
         print(f"different: {k}\n  A: {resources(A[k])}\n  B: {resources(B[k])}\n  first difference at line {at} of {len(A[k])} / {len(B[k])}:"
               f"\n  A| {A[k][at] if at < len(A[k]) else '<end>'}\n  B| {B[k][at] if at < len(B[k]) else '<end>'}")
-    if a.list_same:
+    if a.list_same and a.brief:
+        names = [k.split("<")[0] for k in same]
+        for k in sorted(set(names)):
+            print(f"identical: {names.count(k)} x {k}")
+    elif a.list_same:
         for k in same:
             print(f"identical: {k} | {resources(A[k])}")
     sys.exit(0 if len(same) == len(A) == len(B) else 1)

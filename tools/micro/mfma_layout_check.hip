@@ -1,4 +1,4 @@
-// Checks the operand / result lane maps of v_mfma_f32_16x16x32_bf16 that csrc/amenv_team_policy.hpp relies on, with exact small integers
+// Checks the operand / result lane maps of v_mfma_f32_16x16x32_bf16 that csrc/amenv_policy_mlp.hpp relies on, with exact small integers
 // and an asymmetric pattern:  lane l holds A[row l&15][k = 8(l>>4)+j], B[k = 8(l>>4)+j][col l&15]; D: col = l&15, row = 4(l>>4)+reg.
 //   hipcc --offload-arch=gfx950 -O2 tools/micro/mfma_layout_check.hip -o tools/micro/mfma_layout_check && tools/micro/mfma_layout_check
 #include <hip/hip_runtime.h>
