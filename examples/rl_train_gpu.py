@@ -57,8 +57,12 @@ def main():
                          "--action-delay / --rotor-lag (fp32 rigid vehicles; not with --normalize-obs --fused-rollout; DESIGN 4n)")
     ap.add_argument("--target-kl", type=float, default=None, metavar="X",
                     help="SB3's target_kl: leave an update once a minibatch's approx_kl exceeds 1.5 X (decided on the GPU, no extra synchronisation; one rank only)")
-    ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear"],
-                    help="linear: learning_rate = 2e-4 * progress_remaining (SB3's linear schedule), evaluated once per iteration")
+    ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear", "adaptive"],
+                    help="linear: learning_rate = 2e-4 * progress_remaining (SB3's linear schedule), evaluated once per iteration; adaptive: 2e-4 is the starting "
+                         "value and every minibatch's approx_kl moves it (amd.KlAdaptiveLr, rsl_rl's rule, on the GPU with no extra synchronisation; one rank "
+                         "only; DESIGN 4u)")
+    ap.add_argument("--desired-kl", type=float, default=0.01, metavar="X", help="--lr-schedule adaptive: the approx_kl the rule steers to (the rate moves outside [X / 2, 2 X])")
+    ap.add_argument("--clip-range-vf", type=float, default=None, metavar="C", help="SB3's clipped value loss: the value prediction moves at most C from the rollout's value")
     ap.add_argument("--eval-freq", type=int, default=None, metavar="STEPS",
                     help="evaluate the deterministic policy every STEPS env steps on a separate eval env, in one launch (SB3's EvalCallback; DESIGN 4s): the "
                          "learning curve gains eval_mean_reward / eval_success_rate, the best model goes to <save>_best/best_model.zip")
@@ -103,8 +107,9 @@ def main():
     eval_env = make_env(a.eval_envs, a.seed + 1_000_003, sh.rank * a.eval_envs, ecfg)
     norm = amd.ObsNormalizer(env.obs_dim, device=local) if a.normalize_obs else None
     v1 = a.task != "v2"     # rl_train_vecN.py: 10 epochs, ent .01 (v2/rl_train.py: 12 epochs, ent 5e-4)
-    lr = 2e-4 if a.lr_schedule == "constant" else (lambda progress_remaining: 2e-4 * progress_remaining)
-    model = amd.PPO(env, learning_rate=lr, target_kl=a.target_kl, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
+    lr = (lambda progress_remaining: 2e-4 * progress_remaining) if a.lr_schedule == "linear" else 2e-4
+    rule = amd.KlAdaptiveLr(desired_kl=a.desired_kl) if a.lr_schedule == "adaptive" else None
+    model = amd.PPO(env, learning_rate=lr, adaptive_lr=rule, clip_range_vf=a.clip_range_vf, target_kl=a.target_kl, n_steps=a.n_steps, batch_size=a.envs * a.n_steps // 128, n_epochs=10 if v1 else 12, gamma=0.995,
                     gae_lambda=0.9, clip_range=0.2, ent_coef=0.01 if v1 else (1e-4 if a.resume else 5e-4), dist=dist, fused_rollout=a.fused_rollout,
                     seed=a.seed, obs_normalizer=norm, reward_normalizer=amd.RewardNormalizer(env.num_envs, device=local) if a.norm_reward else None)
     if a.resume:

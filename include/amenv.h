@@ -694,6 +694,48 @@ int amenv_ppo_mlp_step_ctl(const float* flat_params, int32_t obs_dim, int32_t ac
 int amenv_ppo_adam_step_ctl(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6,
                             float* grad_norm_out, uint32_t* ticket, amenv_ppo_ctl* ctl, void* stream);
 
+/* ---- KL-adaptive learning rate on the device and SB3's clipped value loss ----------------------------------------------
+ * The learning rate of the GPU-parallel PPO implementations (rsl_rl, rl_games), driven by every minibatch's approx_kl -- SB3's estimator,
+ * the block's kl_last, not the analytic Gaussian KL (the rollout buffer holds no old means).  All in fp32:
+ *   if      kl > band * desired_kl:           lr = fmaxf(lr / factor, lr_min)
+ *   else if kl > 0 && kl < desired_kl / band: lr = fminf(lr * factor, lr_max)
+ *   else                                      lr unchanged                        (a NaN kl: unchanged)
+ * A host-side rule would cost one device-to-host synchronisation per minibatch; here the number lives in hyper6[0] and the Adam step moves it.
+ *
+ * amenv_ppo_lr_rule is a HOST struct, copied into the launch.  amenv_ppo_adam_step_adapt is amenv_ppo_adam_step_ctl with the rule in front of
+ * the step -- the order within a minibatch is the gate's: loss -> approx_kl -> rule -> optimiser step, taken with the NEW rate:
+ *   - `stop` is tested first: with it set NOTHING changes, hyper6, the step counter and the ticket included;
+ *   - otherwise every thread reads hyper6[0] and the block's kl_last at entry and evaluates the rule itself (all agree to the last bit); the
+ *     workgroup that finishes last stores the new rate into hyper6[0] (hence non-const); hyper6[1..5] are only read.
+ * The rate is NOT in the block: amenv_ppo_ctl keeps its 64 bytes and amenv_ppo_ctl_arm still zeroes all of them.
+ * AMENV_ERR_INVALID, nothing enqueued: ctl or rule NULL, rule->struct_size != sizeof(amenv_ppo_lr_rule), a value that is not finite or
+ * violates desired_kl > 0, band >= 1, factor > 1, 0 < lr_min <= lr_max, and everything amenv_ppo_adam_step_ctl refuses. */
+typedef struct amenv_ppo_lr_rule {
+  uint32_t struct_size; /* = sizeof(amenv_ppo_lr_rule): guard, set by the caller */
+  float desired_kl;     /* > 0; rsl_rl's default 0.01 */
+  float band;           /* >= 1; the rate moves when kl leaves [desired_kl / band, band * desired_kl]; 2 */
+  float factor;         /* > 1; 1.5 */
+  float lr_min;         /* > 0; 1e-5 */
+  float lr_max;         /* >= lr_min; 1e-2 */
+} amenv_ppo_lr_rule;
+int amenv_ppo_adam_step_adapt(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, float* hyper6,
+                              float* grad_norm_out, uint32_t* ticket, amenv_ppo_ctl* ctl, const amenv_ppo_lr_rule* rule, void* stream);
+
+/* SB3 2.6.0's clipped value loss (clip_range_vf): v_pred = v_old + clamp(v - v_old, -c, c), value_loss = mean((returns - v_pred)^2); the gradient
+ * passes where -c <= v - v_old <= c (torch.clamp's backward).  The two entry points take the _ctl argument lists plus old_values [n] f32
+ * (gathered through `index` like old_logp) and clip_range_vf (> 0 and finite, else AMENV_ERR_INVALID; old_values NULL likewise) in front of the
+ * stream; ctl may be NULL.  They launch a third form of the loss kernels; every other kernel of the step is the _ctl (ctl given) or the plain
+ * (ctl NULL) one.  An unclipped sample enters with v itself: with clip_range_vf above every |v - v_old| the results are the _ctl entry
+ * points' bit for bit. */
+int amenv_ppo_loss_grad_vclip(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
+                              const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
+                              float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats,
+                              void* workspace, amenv_ppo_ctl* ctl, const float* old_values, float clip_range_vf, void* stream);
+int amenv_ppo_mlp_step_vclip(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
+                             const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef,
+                             float vf_coef, int32_t normalize_advantage, float* flat_grad, float* stats, void* workspace, amenv_ppo_ctl* ctl,
+                             const float* old_values, float clip_range_vf, void* stream);
+
 /* Parity gate of the arm vehicle's arithmetic (no reference dynamics exist for it; DESIGN.md "arm"): the 19 state derivatives of n states
  * [n, 19] = (p, v, q, w, th, thd) under post-mixer wrenches [n, 4] = (F, Mx, My, Mz) and joint commands [n, 3], deriv [n, 19], all of `dtype`
  * (AMENV_F32 | AMENV_F64), on the current device.  form 0: the per-link Newton-Euler sums the lane and two-wave kernels run; form 1: the staged

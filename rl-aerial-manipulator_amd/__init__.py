@@ -20,6 +20,6 @@ from .obs_norm import GpuVecNormalize, ObsNormalizer
 from .reward_norm import RewardNormalizer
 from . import baselines, ppo
 from .baselines import MinSnapTrajectory, PidController, PidWaypointPolicy
-from .ppo import PPO, ActorCritic, evaluate_policy, reduce_evaluation, clone_pid_policy
+from .ppo import PPO, ActorCritic, KlAdaptiveLr, evaluate_policy, reduce_evaluation, clone_pid_policy
 
-__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "RewardNormalizer", "PPO", "ActorCritic", "evaluate_policy", "reduce_evaluation", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]
+__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "RewardNormalizer", "PPO", "ActorCritic", "KlAdaptiveLr", "evaluate_policy", "reduce_evaluation", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]

@@ -92,6 +92,12 @@ class PpoCtl(C.Structure):
                 ("applied", C.c_uint32), ("kl_sum", C.c_float), ("kl_last", C.c_float), ("sum", C.c_float * 5), ("reserved", C.c_uint32 * 3)]
 
 
+class PpoLrRule(C.Structure):
+    """amenv_ppo_lr_rule: the KL-adaptive learning rate's five numbers (include/amenv.h), a host struct copied into the launch."""
+    _fields_ = [("struct_size", C.c_uint32), ("desired_kl", C.c_float), ("band", C.c_float), ("factor", C.c_float), ("lr_min", C.c_float),
+                ("lr_max", C.c_float)]
+
+
 class AmenvError(RuntimeError):
     pass
 
@@ -159,6 +165,9 @@ SYMBOLS = {
     "amenv_ppo_loss_grad_ctl": (C.c_int, [_P] * 7 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "amenv_ppo_mlp_step_ctl": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P]),
     "amenv_ppo_adam_step_ctl": (C.c_int, [_P] * 5 + [C.c_int64, _P, _P, _P, _P, _P]),
+    "amenv_ppo_adam_step_adapt": (C.c_int, [_P] * 5 + [C.c_int64, _P, _P, _P, _P, C.POINTER(PpoLrRule), _P]),
+    "amenv_ppo_loss_grad_vclip": (C.c_int, [_P] * 7 + [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P]),
+    "amenv_ppo_mlp_step_vclip": (C.c_int, [_P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_float, _P]),
     "amenv_arm_rhs": (C.c_int, [C.POINTER(Config), C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     "amenv_pid_default_params": (C.c_int, [C.POINTER(PidParams)]),
     "amenv_pid_run": (C.c_int, [C.POINTER(PidParams), C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),

@@ -935,10 +935,11 @@ constexpr size_t kMlpWsAdv = size_t(2) * kPpoMaxBlocks * sizeof(double);
 constexpr size_t kMlpWsWt = size_t(2) * kMlpFragsPerNet * 1024;
 constexpr size_t kMlpWsPart = size_t(2) * kMlpMaxBlocks * kAccSize * sizeof(float);
 constexpr size_t kMlpLds = kMlpLdsBytes;
-template <bool kCtl, int D, int A>
+template <bool kCtl, int D, int A, bool kVclip = false>   // kVclip: the third form (ctl may be NULL there), with the old values and clip_range_vf
 hipError_t launch_mlp_step(const float* Pm, const u32x4* WS, const float* obs, const float* actions, const float* old_logp, const float* adv, const float* ret,
                            const int64_t* index, int64_t n,
-                           float clip, float vf, int normalize, const double* adv_part, int adv_blocks, float* part, int blocks, amenv_ppo_ctl* ctl, hipStream_t s) {
+                           float clip, float vf, int normalize, const double* adv_part, int adv_blocks, float* part, int blocks, amenv_ppo_ctl* ctl, hipStream_t s,
+                           const float* old_values = nullptr, float clip_vf = 0.0f) {
   // > 64 KB of dynamic LDS needs the attribute on the device the launch goes to (the PPO entry points run on the CURRENT device): kept per
   // device, under a lock -- a process that drives several GPUs would otherwise launch without it on the second one
   {
@@ -949,13 +950,17 @@ hipError_t launch_mlp_step(const float* Pm, const u32x4* WS, const float* obs, c
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(mu);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-      e = hipFuncSetAttribute(kCtl ? reinterpret_cast<const void*>(&ppo_mlp_fused_kernel_ctl<D, A>) : reinterpret_cast<const void*>(&ppo_mlp_fused_kernel<D, A>),
+      e = hipFuncSetAttribute(kVclip ? reinterpret_cast<const void*>(&ppo_mlp_fused_kernel_vclip<D, A>)
+                              : kCtl ? reinterpret_cast<const void*>(&ppo_mlp_fused_kernel_ctl<D, A>) : reinterpret_cast<const void*>(&ppo_mlp_fused_kernel<D, A>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, int(kMlpLds));
       if (e != hipSuccess) return e;
       if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
   }
-  if (kCtl)
+  if (kVclip)
+    hipLaunchKernelGGL((ppo_mlp_fused_kernel_vclip<D, A>), dim3(blocks, 2), dim3(256), kMlpLds, s, ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf, normalize,
+                       adv_part, adv_blocks, part, old_values, clip_vf);
+  else if (kCtl)
     hipLaunchKernelGGL((ppo_mlp_fused_kernel_ctl<D, A>), dim3(blocks, 2), dim3(256), kMlpLds, s, ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf, normalize,
                        adv_part, adv_blocks, part);
   else
@@ -1859,7 +1864,7 @@ int amenv_ppo_ctl_arm(amenv_ppo_ctl* ctl, float kl_limit, void* stream) {
 static int ppo_loss_grad_launch(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
                                 const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
                                 float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
-                                void* workspace, amenv_ppo_ctl* ctl, int blocks, void* stream) {
+                                void* workspace, amenv_ppo_ctl* ctl, int blocks, void* stream, const float* old_values = nullptr, float clip_range_vf = 0.0f) {
   if (reinterpret_cast<uintptr_t>(ctl) & 3u) return AMENV_ERR_INVALID;
   if (!mean || !value || !log_std || !actions || !old_logp || !advantages || !returns || !d_mean || !d_value || !d_log_std || !stats4 ||
       !workspace || n <= 0 || !(clip_range >= 0.0f) || (reinterpret_cast<uintptr_t>(workspace) & 7u) || !act_dim_built(act_dim))
@@ -1871,7 +1876,10 @@ static int ppo_loss_grad_launch(const float* mean, const float* value, const flo
   if (ctl) hipLaunchKernelGGL(ppo_adv_partials_ctl, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, advantages, (int64_t)n, adv_part, (const int64_t*)nullptr);
   else hipLaunchKernelGGL(ppo_adv_partials, dim3(blocks), dim3(kPpoBlock), 0, s, advantages, (int64_t)n, adv_part, (const int64_t*)nullptr);
   (void)with_act_dim(act_dim, [&](auto a) {   // (a launch error is read below)
-    if (ctl)
+    if (old_values)   // the value-clip form, ctl or none; the launches around it are the _ctl or the plain ones
+      hipLaunchKernelGGL(ppo_loss_grad_vclip<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, mean, value, log_std, actions, old_logp, advantages, returns,
+                         (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part, old_values, clip_range_vf);
+    else if (ctl)
       hipLaunchKernelGGL(ppo_loss_grad_ctl<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, mean, value, log_std, actions, old_logp, advantages, returns,
                          (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part);
     else
@@ -1902,6 +1910,16 @@ int amenv_ppo_loss_grad_ctl(const float* mean, const float* value, const float* 
                               d_value, d_log_std, stats4, workspace, ctl, blocks, stream);
 }
 
+int amenv_ppo_loss_grad_vclip(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
+                              const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
+                              float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
+                              void* workspace, amenv_ppo_ctl* ctl, const float* old_values, float clip_range_vf, void* stream) {
+  if (!old_values || !(clip_range_vf > 0.0f) || !std::isfinite(clip_range_vf)) return AMENV_ERR_INVALID;
+  const int blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
+  return ppo_loss_grad_launch(mean, value, log_std, actions, old_logp, advantages, returns, n, act_dim, clip_range, ent_coef, vf_coef, normalize_advantage, d_mean,
+                              d_value, d_log_std, stats4, workspace, ctl, blocks, stream, old_values, clip_range_vf);
+}
+
 // Bench / profiling utility: a copy of known size with a chosen access width per lane, so that the PMC traffic counters (FETCH_SIZE,
 // WRITE_SIZE) can be calibrated on the access pattern of the kernel under test (16 B per lane: one-lane-per-env kernels; 4 B per lane:
 // lane-team kernels) -- /opt/skills/guides/MI355X_MICROARCH.md, HBM section.
@@ -1918,7 +1936,7 @@ size_t amenv_ppo_mlp_workspace_bytes(void) { return kMlpWsAdv + kMlpWsWt + kMlpW
 static int ppo_mlp_step_launch(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
                                const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
                                int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, amenv_ppo_ctl* ctl, int adv_blocks, int blocks,
-                               void* stream) {
+                               void* stream, const float* old_values = nullptr, float clip_range_vf = 0.0f) {
   if ((reinterpret_cast<uintptr_t>(ctl) & 3u) || !flat_params || !obs || !actions || !old_logp || !advantages || !returns || !flat_grad || !stats4 || !workspace || n <= 0 || !(clip_range >= 0.0f) ||
       (reinterpret_cast<uintptr_t>(workspace) & 15u) || !policy_shape_built(obs_dim, act_dim))
     return AMENV_ERR_INVALID;
@@ -1934,6 +1952,9 @@ static int ppo_mlp_step_launch(const float* flat_params, int32_t obs_dim, int32_
   const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
     constexpr int D_ = decltype(d)::value, A_ = decltype(a)::value;
     const u32x4* ws4 = reinterpret_cast<const u32x4*>(WS);
+    if (old_values)   // the value-clip form, ctl or none
+      return launch_mlp_step<true, D_, A_, true>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
+                                                 part, blocks, ctl, s, old_values, clip_range_vf);
     return ctl ? launch_mlp_step<true, D_, A_>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
                                                part, blocks, ctl, s)
                : launch_mlp_step<false, D_, A_>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
@@ -1972,6 +1993,18 @@ int amenv_ppo_mlp_step_ctl(const float* flat_params, int32_t obs_dim, int32_t ac
                              flat_grad, stats4, workspace, ctl, adv_blocks, blocks, stream);
 }
 
+int amenv_ppo_mlp_step_vclip(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
+                             const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
+                             int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, amenv_ppo_ctl* ctl, const float* old_values,
+                             float clip_range_vf, void* stream) {
+  if (!old_values || !(clip_range_vf > 0.0f) || !std::isfinite(clip_range_vf)) return AMENV_ERR_INVALID;
+  const int adv_blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
+  const int64_t ntiles = (n + 31) / 32;
+  const int blocks = int(std::min<int64_t>(128, (ntiles + 3) / 4));   // 128 x 2 nets x 4 wavefronts = one wavefront per SIMD
+  return ppo_mlp_step_launch(flat_params, obs_dim, act_dim, obs, actions, old_logp, advantages, returns, index, n, clip_range, ent_coef, vf_coef, normalize_advantage,
+                             flat_grad, stats4, workspace, ctl, adv_blocks, blocks, stream, old_values, clip_range_vf);
+}
+
 static int ppo_adam_step_launch(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6, float* grad_norm_out,
                                 uint32_t* ticket, amenv_ppo_ctl* ctl, int blocks, void* stream) {
   if ((reinterpret_cast<uintptr_t>(ctl) & 3u) || !flat_params || !flat_grad || !exp_avg || !exp_avg_sq || !step || !hyper6 || !ticket || n <= 0 || !aligned16(flat_grad)) return AMENV_ERR_INVALID;
@@ -1994,6 +2027,21 @@ int amenv_ppo_adam_step_ctl(float* flat_params, const float* flat_grad, float* e
                             uint32_t* ticket, amenv_ppo_ctl* ctl, void* stream) {
   const int blocks = int(std::min<int64_t>(kAdamMaxBlocks, (n + kAdamBlock - 1) / kAdamBlock));
   return ppo_adam_step_launch(flat_params, flat_grad, exp_avg, exp_avg_sq, step, n, hyper6, grad_norm_out, ticket, ctl, blocks, stream);
+}
+
+// The KL-adaptive form: its own launch, the rule copied into it; geometry as amenv_ppo_adam_step's.
+int amenv_ppo_adam_step_adapt(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, float* hyper6, float* grad_norm_out,
+                              uint32_t* ticket, amenv_ppo_ctl* ctl, const amenv_ppo_lr_rule* rule, void* stream) {
+  if (!ctl || (reinterpret_cast<uintptr_t>(ctl) & 3u) || !rule || rule->struct_size != sizeof(amenv_ppo_lr_rule)) return AMENV_ERR_INVALID;
+  const amenv_ppo_lr_rule r = *rule;
+  if (!std::isfinite(r.desired_kl) || !std::isfinite(r.band) || !std::isfinite(r.factor) || !std::isfinite(r.lr_min) || !std::isfinite(r.lr_max) ||
+      !(r.desired_kl > 0.0f) || !(r.band >= 1.0f) || !(r.factor > 1.0f) || !(r.lr_min > 0.0f) || !(r.lr_min <= r.lr_max))
+    return AMENV_ERR_INVALID;
+  if (!flat_params || !flat_grad || !exp_avg || !exp_avg_sq || !step || !hyper6 || !ticket || n <= 0 || !aligned16(flat_grad)) return AMENV_ERR_INVALID;
+  const int blocks = int(std::min<int64_t>(kAdamMaxBlocks, (n + kAdamBlock - 1) / kAdamBlock));
+  hipLaunchKernelGGL(adam_clip_kernel_adapt, dim3(blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, ctl, flat_params, (const float*)flat_grad, exp_avg, exp_avg_sq, step, (int64_t)n, hyper6,
+                     grad_norm_out, ticket, r);
+  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
 // Right-hand side of the arm vehicle for n states, per-link (form 0) or staged / aggregated (form 1) formulation, fp32 or fp64: the logic gate of

@@ -364,16 +364,20 @@ struct MlpLoss { float clip, vf_coef, inv_n, mu, inv_sd; };
 #endif
 
 // One PPO minibatch: forward + loss + backward + weight gradients of both nets.  grid = (blocks, 2), 256 threads.
-template <bool kCtl, int D, int A>
+// kVclip: the third form, SB3's clipped value loss on the critic's lane -- one more load per sample (the old value, fetched with the
+// other loss inputs) and a few VALU instructions; the expressions are ppo_loss_grad_body's.  In that form `ctl` may be NULL (tested at run time).
+template <bool kCtl, int D, int A, bool kVclip = false>
 __device__ __forceinline__ void ppo_mlp_fused_body(amenv_ppo_ctl* ctl, const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
                                                    const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
                                                    const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
                                                    float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
-                                                   float* __restrict__ part) {
+                                                   float* __restrict__ part, const float* __restrict__ old_value = nullptr, float clip_vf = 0.0f) {
   if constexpr (kCtl) {   // the gate: read once, by every thread, before the first barrier; one thread hands what was read to the reduction launch
-    const uint32_t st = ctl->stop;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ctl->stop_seen = st;
-    if (st != 0u) return;
+    if (!kVclip || ctl != nullptr) {
+      const uint32_t st = ctl->stop;
+      if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ctl->stop_seen = st;
+      if (st != 0u) return;
+    }
   }
   extern __shared__ __attribute__((aligned(16))) float mlp_lds[];   // transposes [kXposeRows][kXs] | stats [4 wavefronts][16]
   float* xz = mlp_lds;
@@ -433,7 +437,8 @@ __device__ __forceinline__ void ppo_mlp_fused_body(amenv_ppo_ctl* ctl, const flo
     float act4[4], olp_s, adv_s;
 #pragma unroll
     for (int r = 0; r < 4; r++) { const int k = r + 4 * h; act4[r] = net == 0 ? actions[sc * A + (k < A ? k : A - 1)] : 0.0f; }   // (rows >= A are masked where used)
-    olp_s = net == 0 ? old_logp[sc] : 0.0f;
+    if constexpr (kVclip) olp_s = net == 0 ? old_logp[sc] : old_value[sc];   // critic: the old value, in the register the actor's old log-prob takes
+    else olp_s = net == 0 ? old_logp[sc] : 0.0f;
     adv_s = net == 0 ? adv[sc] : ret[sc];                  // critic: the return
     MlpRing ring;
     {
@@ -478,8 +483,15 @@ __device__ __forceinline__ void ppo_mlp_fused_body(amenv_ppo_ctl* ctl, const flo
       }
       if (sv && h == 0) { s_pol += -fminf(s1, s2); s_clipn += fabsf(ratio - 1.0f) > clip ? 1.0f : 0.0f; if (kCtl) s_kl += (ratio - 1.0f) - lr; }   // (SB3's approx_kl estimator)
     } else if (h == 0) {
-      const float dv = adv_s - Y[0][0];
-      dY[0][0] = sv ? -2.0f * vf_coef * dv * Lp.inv_n : 0.0f;
+      float dv = adv_s - Y[0][0];
+      bool pass = sv;
+      if constexpr (kVclip) {                               // (ppo_loss_grad_body's expressions: an unclipped sample uses the value itself)
+        const float dd = Y[0][0] - olp_s;
+        if (dd > clip_vf) dv = adv_s - (olp_s + clip_vf);
+        else if (dd < -clip_vf) dv = adv_s - (olp_s - clip_vf);
+        pass = sv && dd >= -clip_vf && dd <= clip_vf;
+      }
+      dY[0][0] = pass ? -2.0f * vf_coef * dv * Lp.inv_n : 0.0f;
       if (sv) s_val += dv * dv;
     }
     Bf3 dYS[1][2];
@@ -601,6 +613,14 @@ __global__ __launch_bounds__(256) void ppo_mlp_fused_kernel_ctl(amenv_ppo_ctl* c
                                                                 float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
                                                                 float* __restrict__ part) {
   ppo_mlp_fused_body<true, D, A>(ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf_coef, normalize, adv_part, adv_blocks, part);
+}
+template <int D, int A>
+__global__ __launch_bounds__(256) void ppo_mlp_fused_kernel_vclip(amenv_ppo_ctl* ctl, const float* __restrict__ Pm, const u32x4* __restrict__ WS, const float* __restrict__ obs,
+                                                                  const float* __restrict__ actions, const float* __restrict__ old_logp, const float* __restrict__ adv,
+                                                                  const float* __restrict__ ret, const int64_t* __restrict__ index, int64_t n, float clip,
+                                                                  float vf_coef, int normalize, const double* __restrict__ adv_part, int adv_blocks,
+                                                                  float* __restrict__ part, const float* __restrict__ old_value, float clip_vf) {
+  ppo_mlp_fused_body<true, D, A, true>(ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf_coef, normalize, adv_part, adv_blocks, part, old_value, clip_vf);
 }
 
 // The forward passes alone: mean [n, A] = action_net(pi trunk(obs)), value [n] = value_net(vf trunk(obs)) for large batches (the rollout
@@ -755,14 +775,23 @@ __global__ __launch_bounds__(64 * kRedGroups) void mlp_grad_reduce_kernel_ctl(am
 // correct too but 20 us instead of 3.  `step` is torch's capturable-Adam step counter (a float on the device): read by every workgroup at
 // entry, incremented by the last one to finish (ticket), after every workgroup has read it.
 // hyper: [0] lr  [1] beta1  [2] beta2  [3] eps  [4] max_grad_norm (<= 0: no clipping)  [5] grad_scale (1 / world size after a sum all-reduce)
+// kAdapt (the third form, adam_clip_kernel_adapt): the KL-adaptive learning rate.  hyper[0] and ctl->kl_last are read at entry by every
+// thread, behind the `stop` test and before the first barrier -- as step[0] is; every thread evaluates ppo_lr_rule_step itself (pure: all agree to
+// the last bit) and steps with the NEW rate; the workgroup that takes the last ticket stores it into hyper[0], where it stores step[0]: by then every
+// workgroup has passed its entry reads (each adds to the ticket after them).  `hyper` is writable and unrestricted in that form only.
 constexpr int kAdamBlock = 1024, kAdamMaxBlocks = 64;
-template <bool kCtl>
+template <bool kAdapt> struct AdamHyperPtr { typedef const float* __restrict__ type; };
+template <> struct AdamHyperPtr<true> { typedef float* type; };
+template <bool kCtl, bool kAdapt = false>
 __device__ __forceinline__ void adam_clip_body(amenv_ppo_ctl* ctl, float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
-                                               float* __restrict__ step, int64_t n, const float* __restrict__ hyper, float* __restrict__ grad_norm,
-                                               unsigned int* __restrict__ ticket) {
+                                               float* __restrict__ step, int64_t n, typename AdamHyperPtr<kAdapt>::type hyper, float* __restrict__ grad_norm,
+                                               unsigned int* __restrict__ ticket, const amenv_ppo_lr_rule* rule = nullptr) {
+  static_assert(kCtl || !kAdapt, "the adaptive form reads the control block");
   __shared__ float sh[kAdamBlock / 64];
   if (ppo_ctl_stopped<kCtl>(ctl)) return;   // the gate (amenv_train.hpp): nothing is touched, the ticket included; `stop` is not written by this kernel
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], max_norm = hyper[4], scale = hyper[5];
+  float lr = hyper[0];
+  const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], max_norm = hyper[4], scale = hyper[5];
+  if constexpr (kAdapt) lr = ppo_lr_rule_step(*rule, lr, ctl->kl_last);
   const float t = step[0] + 1.0f;
   float ss = 0.0f;
   {   // 16-byte loads, eight in flight per thread (the buffer is 16-byte aligned: checked by the caller); the sum order is fixed by (thread, i)
@@ -810,6 +839,7 @@ __device__ __forceinline__ void adam_clip_body(amenv_ppo_ctl* ctl, float* __rest
     __threadfence();
     if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
       step[0] = t; *ticket = 0u;
+      if constexpr (kAdapt) hyper[0] = lr;
       if constexpr (kCtl) { ctl->applied += 1u; ctl->sum[4] += gn; }
     }
   }
@@ -823,6 +853,11 @@ __global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel_ctl(amenv_ppo_ctl
                                                                    float* __restrict__ v, float* __restrict__ step, int64_t n, const float* __restrict__ hyper,
                                                                    float* __restrict__ grad_norm, unsigned int* __restrict__ ticket) {
   adam_clip_body<true>(ctl, param, grad, m, v, step, n, hyper, grad_norm, ticket);
+}
+__global__ __launch_bounds__(kAdamBlock) void adam_clip_kernel_adapt(amenv_ppo_ctl* ctl, float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
+                                                                     float* __restrict__ v, float* __restrict__ step, int64_t n, float* hyper,
+                                                                     float* __restrict__ grad_norm, unsigned int* __restrict__ ticket, amenv_ppo_lr_rule rule) {
+  adam_clip_body<true, true>(ctl, param, grad, m, v, step, n, hyper, grad_norm, ticket, &rule);
 }
 
 }  // namespace amenv_dev

@@ -137,6 +137,15 @@ __global__ void ppo_ctl_arm_kernel(amenv_ppo_ctl* ctl, float kl_limit) {
   *ctl = z;
 }
 
+// The KL-adaptive learning rate (include/amenv.h amenv_ppo_lr_rule): rsl_rl's rule on SB3's approx_kl.  Pure fp32, no contraction
+// (-ffp-contract=off), IEEE division: every thread of adam_clip_kernel_adapt evaluates it and all agree to the last bit; KlAdaptiveLr.step
+// (ppo.py) is the same expression in numpy.float32.  A NaN kl fails both comparisons: unchanged.
+__host__ __device__ __forceinline__ float ppo_lr_rule_step(const amenv_ppo_lr_rule& r, float lr, float kl) {
+  if (kl > r.band * r.desired_kl) return fmaxf(lr / r.factor, r.lr_min);
+  if (kl > 0.0f && kl < r.desired_kl / r.band) return fminf(lr * r.factor, r.lr_max);
+  return lr;
+}
+
 // body of ppo_adv_partials for block `blk` of `nblk` (also called from the fused minibatch step's prologue kernel, amenv_mlp_train.hpp)
 __device__ __forceinline__ void ppo_adv_partials_block(const float* __restrict__ adv, int64_t n, double* __restrict__ part, const int64_t* __restrict__ index,
                                                        int blk, int nblk) {
@@ -166,16 +175,20 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_adv_partials_ctl(const amenv_pp
   ppo_adv_partials_block(adv, n, part, index, int(blockIdx.x), int(gridDim.x));
 }
 
-template <bool kCtl, int A>
+// kVclip: the third form, SB3's clipped value loss.  v_pred = v_old + clamp(v - v_old, -c, c), written so that an unclipped sample
+// uses v itself (v_old + (v - v_old) is not v in fp32): with c above every |v - v_old| the form gives the bits of the _ctl one.  The gradient
+// passes on the closed interval, as torch.clamp's backward does.  `ctl` may be NULL in this form (a run-time test: it has no plain twin).
+template <bool kCtl, int A, bool kVclip = false>
 __device__ __forceinline__ void ppo_loss_grad_body(const amenv_ppo_ctl* ctl, const float* __restrict__ mean, const float* __restrict__ value,
                                                    const float* __restrict__ log_std, const float* __restrict__ actions,
                                                    const float* __restrict__ old_logp, const float* __restrict__ adv,
                                                    const float* __restrict__ ret, int64_t n, float clip, float vf_coef,
                                                    int normalize, const double* __restrict__ adv_part, int adv_blocks,
                                                    float* __restrict__ d_mean, float* __restrict__ d_value,
-                                                   float* __restrict__ part) {
+                                                   float* __restrict__ part, const float* __restrict__ old_value = nullptr, float clip_vf = 0.0f) {
   __shared__ float sh[kPpoBlock / 64][kPpoPartial];
-  if (ppo_ctl_stopped<kCtl>(ctl)) return;
+  if constexpr (kVclip) { if (ctl != nullptr && ctl->stop != 0u) return; }
+  else if (ppo_ctl_stopped<kCtl>(ctl)) return;
   constexpr int NP = kCtl ? A + 4 : A + 3;                                   // partial slots in use: approx_kl only with a control block
   // advantage statistics: every block sums the (few hundred) partials in the same fixed order
   float mu = 0.0f, inv_sd = 1.0f;
@@ -212,8 +225,14 @@ __device__ __forceinline__ void ppo_loss_grad_body(const amenv_ppo_ctl* ctl, con
       d_mean[i * A + k] = g_lp * z[k] * isd[k];
       acc[k] += g_lp * fma_(z[k], z[k], -1.0f);
     }
-    const float dv = ret[i] - value[i];
-    d_value[i] = -2.0f * vf_coef * dv * inv_n;
+    float dv = ret[i] - value[i];
+    if constexpr (kVclip) {
+      const float vo = old_value[i], dd = value[i] - vo;
+      if (dd > clip_vf) dv = ret[i] - (vo + clip_vf);
+      else if (dd < -clip_vf) dv = ret[i] - (vo - clip_vf);
+      d_value[i] = (dd >= -clip_vf && dd <= clip_vf) ? -2.0f * vf_coef * dv * inv_n : 0.0f;
+    } else
+      d_value[i] = -2.0f * vf_coef * dv * inv_n;
     acc[A] += -fminf(s1, s2);
     acc[A + 1] += dv * dv;
     acc[A + 2] += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
@@ -249,6 +268,16 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad_ctl(const amenv_ppo_c
                                                                int64_t n, float clip, float vf_coef, int normalize, const double* __restrict__ adv_part,
                                                                int adv_blocks, float* __restrict__ d_mean, float* __restrict__ d_value, float* __restrict__ part) {
   ppo_loss_grad_body<true, A>(ctl, mean, value, log_std, actions, old_logp, adv, ret, n, clip, vf_coef, normalize, adv_part, adv_blocks, d_mean, d_value, part);
+}
+template <int A>
+__global__ __launch_bounds__(kPpoBlock) void ppo_loss_grad_vclip(const amenv_ppo_ctl* ctl, const float* __restrict__ mean, const float* __restrict__ value,
+                                                                 const float* __restrict__ log_std, const float* __restrict__ actions,
+                                                                 const float* __restrict__ old_logp, const float* __restrict__ adv, const float* __restrict__ ret,
+                                                                 int64_t n, float clip, float vf_coef, int normalize, const double* __restrict__ adv_part,
+                                                                 int adv_blocks, float* __restrict__ d_mean, float* __restrict__ d_value, float* __restrict__ part,
+                                                                 const float* __restrict__ old_value, float clip_vf) {
+  ppo_loss_grad_body<true, A, true>(ctl, mean, value, log_std, actions, old_logp, adv, ret, n, clip, vf_coef, normalize, adv_part, adv_blocks, d_mean, d_value, part,
+                                    old_value, clip_vf);
 }
 
 // d_log_std[k] = sum of partials + ent_coef * d(-mean entropy)/d log_std = ... - ent_coef ; stats = {policy loss, value loss,

@@ -287,6 +287,52 @@ def gaussian_act(mean, log_std, low, high, raw_out, clipped_out, logp_out, seed,
         raise L.AmenvError(f"amenv_gaussian_act failed ({rc}): act_dim must be 4..7")
 
 
+class KlAdaptiveLr:
+    """The KL-adaptive learning rate of the GPU-parallel PPO implementations (rsl_rl's rule and defaults), driven by every
+    minibatch's `approx_kl` (SB3's estimator):
+
+        if      kl > band * desired_kl:           lr = max(lr / factor, lr_min)
+        else if kl > 0 and kl < desired_kl / band: lr = min(lr * factor, lr_max)
+        else                                       lr unchanged                   (a NaN kl: unchanged)
+
+    A plain value class.  `step(lr, kl)` IS the rule, in numpy.float32 -- the arithmetic of `amenv_ppo_adam_step_adapt`, bit for bit; the
+    host update paths call it, the fused path hands `struct()` to the kernel.  The value checks are the C ABI's."""
+    FIELDS = ("desired_kl", "factor", "band", "lr_min", "lr_max")
+
+    def __init__(self, desired_kl=0.01, factor=1.5, band=2.0, lr_min=1e-5, lr_max=1e-2):
+        try:
+            v = [np.float32(x) for x in (desired_kl, factor, band, lr_min, lr_max)]
+        except (TypeError, ValueError) as e:
+            raise L.AmenvError(f"KlAdaptiveLr: five numbers expected ({e})") from None
+        self.desired_kl, self.factor, self.band, self.lr_min, self.lr_max = v
+        if not all(np.isfinite(x) for x in v):
+            raise L.AmenvError(f"KlAdaptiveLr: every value must be finite in float32 (got {self!r})")
+        if not (self.desired_kl > 0 and self.band >= 1 and self.factor > 1 and 0 < self.lr_min <= self.lr_max):
+            raise L.AmenvError(f"KlAdaptiveLr needs desired_kl > 0, band >= 1, factor > 1 and 0 < lr_min <= lr_max (got {self!r})")
+
+    def step(self, lr, kl):
+        """The learning rate after a minibatch whose approx_kl is `kl`, as numpy.float32."""
+        lr, kl = np.float32(lr), np.float32(kl)
+        if kl > self.band * self.desired_kl:
+            return np.maximum(lr / self.factor, self.lr_min)
+        if kl > 0 and kl < self.desired_kl / self.band:
+            return np.minimum(lr * self.factor, self.lr_max)
+        return lr
+
+    def struct(self):
+        return L.PpoLrRule(C.sizeof(L.PpoLrRule), float(self.desired_kl), float(self.band), float(self.factor), float(self.lr_min), float(self.lr_max))
+
+    def state_dict(self):
+        """The five numbers as Python floats (each holds its float32 exactly: JSON brings them back bit for bit)."""
+        return {k: float(getattr(self, k)) for k in self.FIELDS}
+
+    def __eq__(self, other):
+        return isinstance(other, KlAdaptiveLr) and self.state_dict() == other.state_dict()
+
+    def __repr__(self):
+        return "KlAdaptiveLr(" + ", ".join(f"{k}={float(getattr(self, k))!r}" for k in self.FIELDS) + ")"
+
+
 class MinibatchStep:
     """One PPO minibatch update (SB3 `PPO.train` inner loop body): loss, backward, gradient exchange, clip, Adam.
 
@@ -309,14 +355,39 @@ class MinibatchStep:
     its hyper-parameters when they change and the eager paths read them on every call; CAPTURED GRAPHS have `clip_range` baked in (a launch
     argument) and, with torch's Adam, the learning rate too: such a change drops them and the next full minibatch captures again (one
     capture per change, i.e. per iteration under a schedule).  With the fused Adam step the learning rate lives in a device buffer that the
-    replayed launch reads, so a change of the learning rate alone is one small upload and the graphs stay."""
+    replayed launch reads, so a change of the learning rate alone is one small upload and the graphs stay.
+
+    `adaptive_lr` (a `KlAdaptiveLr`): the learning rate follows every minibatch's approx_kl, in the gate's order -- loss ->
+    approx_kl -> (stop?) -> rule -> optimiser step with the new rate; after a stop nothing moves.  Where the whole step is HIP the rule runs
+    ON THE DEVICE (`amenv_ppo_adam_step_adapt`, `device_rule`): the rate lives in `hyper6[0]`, which the host uploads before an update's first
+    step and then leaves alone; `readout` brings it back with the update's one transfer and writes it to `param_groups[0]["lr"]`.  Every
+    other path runs `KlAdaptiveLr.step` on the host after the loss, one synchronisation per minibatch, and sets `param_groups[0]["lr"]`.
+    Refused with captured graphs and with several ranks, as `target_kl` is and for its reasons.
+
+    `clip_range_vf` (SB3's clipped value loss; None = off): v_pred = v_old + clamp(v - v_old, -c, c).  The step then takes the rollout's old
+    values as a sixth tensor (`old_values`); the HIP paths launch the `_vclip` entry points, the torch path states the same formula."""
 
     def __init__(self, policy, optimizer, *, clip_range=0.2, ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5,
-                 normalize_advantage=True, dist=None, use_graph=None, split_graphs=None, fused_loss=None, fused_mlp=None, target_kl=None):
+                 normalize_advantage=True, dist=None, use_graph=None, split_graphs=None, fused_loss=None, fused_mlp=None, target_kl=None,
+                 adaptive_lr=None, clip_range_vf=None):
         if policy.flat_grad is None:
             policy.flatten_()
         self.policy, self.optimizer, self.dist = policy, optimizer, dist
         self.world = dist.get_world_size() if dist is not None else 1
+        if adaptive_lr is not None and not isinstance(adaptive_lr, KlAdaptiveLr):
+            raise L.AmenvError(f"adaptive_lr must be a KlAdaptiveLr or None (got {type(adaptive_lr).__name__})")
+        self.adaptive_lr = adaptive_lr
+        if adaptive_lr is not None:
+            if self.world > 1:
+                raise L.AmenvError("adaptive_lr with several ranks is not built: every rank would move its learning rate by its own shard's approx_kl and "
+                                   "the ranks would step with different rates; train with adaptive_lr=None")
+            if use_graph:
+                raise L.AmenvError("adaptive_lr with use_graph=True is not built: the rule sits between the loss and the optimiser step, inside "
+                                   "what a captured graph replays as one piece; leave use_graph unset (adaptive_lr runs the eager paths)")
+            use_graph = False
+        self.clip_range_vf = None if clip_range_vf is None else float(clip_range_vf)
+        if self.clip_range_vf is not None and not (self.clip_range_vf > 0.0 and math.isfinite(self.clip_range_vf)):
+            raise L.AmenvError(f"clip_range_vf must be positive and finite (got {clip_range_vf!r}); None switches the value clip off")
         self.target_kl = None if target_kl is None else float(target_kl)
         if self.target_kl is not None:
             if not self.target_kl > 0.0:
@@ -358,6 +429,8 @@ class MinibatchStep:
         self._eager_calls = 0
         # the device control block (amenv_ppo_ctl) of the HIP paths: the gate where the whole step is HIP, approx_kl and the running sums everywhere
         self.device_gate = self.target_kl is not None and self.fused_mlp and self.fused_adam
+        self.device_rule = self.adaptive_lr is not None and self.fused_mlp and self.fused_adam   # the rule inside the fused Adam step
+        self._lr_on_device = False                       # device_rule: an update has started, hyper6[0] is the device's until `readout`
         self._ctl = None
         if dev.type == "cuda" and (self.fused_loss or self.fused_mlp):
             if L.load().amenv_ppo_ctl_bytes() != C.sizeof(L.PpoCtl):
@@ -385,11 +458,16 @@ class MinibatchStep:
         self._acc.zero_()
         self.evaluated = self.applied = 0
         self.stopped = False
+        self._lr_on_device = False
 
-    def set_hyper(self, learning_rate=None, clip_range=None):
+    def set_hyper(self, learning_rate=None, clip_range=None, clip_range_vf=None):
         changed = False
         if clip_range is not None and float(clip_range) != self.clip_range:
             self.clip_range, changed = float(clip_range), True
+        if clip_range_vf is not None and float(clip_range_vf) != self.clip_range_vf:
+            if self.clip_range_vf is None or not (float(clip_range_vf) > 0.0 and math.isfinite(float(clip_range_vf))):
+                raise L.AmenvError("set_hyper: clip_range_vf changes a value clip that was built in (positive, finite); it does not switch one on")
+            self.clip_range_vf, changed = float(clip_range_vf), True
         if learning_rate is not None:
             for g in self.optimizer.param_groups:
                 if isinstance(g["lr"], torch.Tensor):
@@ -405,11 +483,17 @@ class MinibatchStep:
             self._graphs = self._static = None
 
     # -- the arithmetic (shared by the eager and the captured path) --------------------------------
-    def _forward_backward(self, obs, actions, old_logp, adv, ret):
+    def _old_values(self, old_values):
+        if (self.clip_range_vf is None) != (old_values is None):
+            raise L.AmenvError("old_values go with clip_range_vf: the clipped value loss needs the rollout's values, and nothing else reads them")
+        return old_values
+
+    def _forward_backward(self, obs, actions, old_logp, adv, ret, old_values=None):
+        self._old_values(old_values)
         if self.fused_mlp:
-            return self._forward_backward_mlp(obs, actions, old_logp, adv, ret)
+            return self._forward_backward_mlp(obs, actions, old_logp, adv, ret, None, old_values)
         if self.fused_loss:
-            return self._forward_backward_fused(obs, actions, old_logp, adv, ret)
+            return self._forward_backward_fused(obs, actions, old_logp, adv, ret, old_values)
         if self.normalize_advantage and adv.numel() > 1:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         values, logp, entropy = self.policy.evaluate_actions(obs, actions)
@@ -417,6 +501,8 @@ class MinibatchStep:
         ratio = torch.exp(log_ratio)
         c = self.clip_range
         pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1.0 - c, 1.0 + c)).mean()
+        if old_values is not None:                       # SB3: values_pred = old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)
+            values = old_values + torch.clamp(values - old_values, -self.clip_range_vf, self.clip_range_vf)
         vl = torch.nn.functional.mse_loss(ret, values)
         el = -entropy.mean()
         # gradients straight into the flat buffer with ONE concatenation (autograd's per-parameter accumulate-into-.grad would
@@ -428,7 +514,7 @@ class MinibatchStep:
             self.stats[3] = ((ratio.detach() - 1.0).abs() > c).float().mean()
             self.kl[0] = ((ratio.detach() - 1.0) - log_ratio.detach()).mean()         # SB3's approx_kl
 
-    def _forward_backward_fused(self, obs, actions, old_logp, adv, ret):
+    def _forward_backward_fused(self, obs, actions, old_logp, adv, ret, old_values=None):
         """Same loss, with everything between the network outputs and the backward pass in the HIP kernels of
         `amenv_ppo_loss_grad` (3 launches for ~60): autograd only walks the two MLPs, seeded with d L / d mean and d L / d value."""
         pol = self.policy
@@ -441,9 +527,13 @@ class MinibatchStep:
         d_mean, d_value, d_log_std, ws = self._fused_buf
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         m, v = mean.detach().contiguous(), values.detach().contiguous()
-        rc = L.load().amenv_ppo_loss_grad_ctl(p(m), p(v), p(pol.log_std.detach()), p(actions), p(old_logp), p(adv), p(ret), n, a, self.clip_range,
-                                              self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(d_mean), p(d_value), p(d_log_std),
-                                              p(self.stats), p(ws), self._ctl_ptr(), C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
+        args = (p(m), p(v), p(pol.log_std.detach()), p(actions), p(old_logp), p(adv), p(ret), n, a, self.clip_range, self.ent_coef, self.vf_coef,
+                1 if self.normalize_advantage else 0, p(d_mean), p(d_value), p(d_log_std), p(self.stats), p(ws), self._ctl_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream)
+        if old_values is None:
+            rc = L.load().amenv_ppo_loss_grad_ctl(*args, stream)
+        else:
+            rc = L.load().amenv_ppo_loss_grad_vclip(*args, p(old_values.contiguous()), self.clip_range_vf, stream)
         if rc != 0:
             raise L.AmenvError(f"amenv_ppo_loss_grad failed ({rc})")
         grads = torch.autograd.grad([mean, values], self._net_params, grad_outputs=[d_mean, d_value])
@@ -459,7 +549,7 @@ class MinibatchStep:
                 and not g.get("amsgrad") and not g.get("maximize") and g.get("weight_decay", 0) == 0 and not g.get("decoupled_weight_decay", False)
                 and not isinstance(g["lr"], torch.Tensor))
 
-    def _forward_backward_mlp(self, obs, actions, old_logp, adv, ret, index=None):
+    def _forward_backward_mlp(self, obs, actions, old_logp, adv, ret, index=None, old_values=None):
         """Forward, SB3's loss, backward and every weight gradient in ONE kernel (csrc/amenv_mlp_train.hpp): the gradient lands in the flat
         buffer, the four reported scalars in `stats`.  fp32 throughout (v_mfma_f32_32x32x2_f32), autograd is not involved.  With `index`
         (int64 [n]) the minibatch is rows `index` of the given tensors, gathered inside the kernel."""
@@ -469,9 +559,14 @@ class MinibatchStep:
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         obs, actions = obs.contiguous(), actions.contiguous()
         n = obs.shape[0] if index is None else index.shape[0]
-        rc = L.load().amenv_ppo_mlp_step_ctl(p(pol.flat_param.detach()), pol.obs_dim, pol.act_dim, p(obs), p(actions), p(old_logp), p(adv), p(ret),
-                                             None if index is None else p(index), n, self.clip_range, self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(pol.flat_grad), p(self.stats),
-                                             p(self._mlp_ws), self._ctl_ptr(), C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
+        args = (p(pol.flat_param.detach()), pol.obs_dim, pol.act_dim, p(obs), p(actions), p(old_logp), p(adv), p(ret),
+                None if index is None else p(index), n, self.clip_range, self.ent_coef, self.vf_coef, 1 if self.normalize_advantage else 0, p(pol.flat_grad), p(self.stats),
+                p(self._mlp_ws), self._ctl_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        if self._old_values(old_values) is None:
+            rc = L.load().amenv_ppo_mlp_step_ctl(*args, stream)
+        else:
+            rc = L.load().amenv_ppo_mlp_step_vclip(*args, p(old_values.contiguous()), self.clip_range_vf, stream)
         if rc != 0:
             raise L.AmenvError(f"amenv_ppo_mlp_step failed ({rc})")
 
@@ -493,9 +588,14 @@ class MinibatchStep:
             st["exp_avg_sq"] = torch.zeros_like(pol.flat_param)
         self._adam_upload_hyper()
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        rc = L.load().amenv_ppo_adam_step_ctl(p(pol.flat_param.detach()), p(pol.flat_grad), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"]), pol.flat_param.numel(),
-                                              p(self._adam_hyper), C.c_void_p(self.stats.data_ptr() + 16), p(self._adam_ticket), self._ctl_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream(leaf.device).cuda_stream))
+        args = (p(pol.flat_param.detach()), p(pol.flat_grad), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"]), pol.flat_param.numel(),
+                p(self._adam_hyper), C.c_void_p(self.stats.data_ptr() + 16), p(self._adam_ticket), self._ctl_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(leaf.device).cuda_stream)
+        if self.device_rule:                             # the rule inside the launch; from here to `readout` hyper6[0] is the device's
+            rc = L.load().amenv_ppo_adam_step_adapt(*args, C.byref(self.adaptive_lr.struct()), stream)
+            self._lr_on_device = True
+        else:
+            rc = L.load().amenv_ppo_adam_step_ctl(*args, stream)
         if rc != 0:
             raise L.AmenvError(f"amenv_ppo_adam_step failed ({rc})")
 
@@ -505,6 +605,12 @@ class MinibatchStep:
         g = self.optimizer.param_groups[0]
         key = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0, 1.0 / self.world)
+        if self._lr_on_device and self._adam_key is not None:
+            # adaptive_lr on the device, an update under way: the host's copy of the rate is stale and hyper6[0] is not the host's to write
+            if key[1:] != self._adam_key[1:]:
+                self._adam_hyper[1:].copy_(torch.tensor(key[1:], dtype=torch.float32))
+                self._adam_key = self._adam_key[:1] + key[1:]
+            return
         if key != self._adam_key:
             dev = g["params"][0].device
             if self._adam_hyper is None:
@@ -539,23 +645,38 @@ class MinibatchStep:
             self._acc[4] += self.stats[4]
             self.applied += 1
 
+    def _host_rule(self):
+        """`KlAdaptiveLr.step` where the step is not all HIP: after the loss (and the stop test), before the optimiser step; one host
+        synchronisation, as the host `target_kl` check takes.  (Never beside the device gate: gate and rule are on the device together.)"""
+        if self.adaptive_lr is None or self.device_rule:
+            return
+        for g in self.optimizer.param_groups:
+            lr = g["lr"]
+            new = float(self.adaptive_lr.step(float(lr), float(self.kl)))
+            if isinstance(lr, torch.Tensor):
+                lr.fill_(new)
+            else:
+                g["lr"] = new
+
     def _eager(self, *mb):
         if self.stopped:
             return
         self._forward_backward(*mb)
         if self._host_gate():
             return
+        self._host_rule()
         self._exchange()
         self._apply()
         self._applied()
 
-    def indexed(self, obs, actions, old_logp, adv, ret, index):
+    def indexed(self, obs, actions, old_logp, adv, ret, index, old_values=None):
         """One minibatch step on rows `index` of the whole-rollout tensors (fused path only): no gathered copies, no graph."""
         if self.stopped:
             return
-        self._forward_backward_mlp(obs, actions, old_logp, adv, ret, index)
+        self._forward_backward_mlp(obs, actions, old_logp, adv, ret, index, old_values)
         if self._host_gate():
             return
+        self._host_rule()
         self._exchange()
         self._apply()
         self._applied()
@@ -569,6 +690,9 @@ class MinibatchStep:
         parts = [total.to(torch.float32).view(torch.int32), self._acc.view(torch.int32)]   # (as raw words: the block's counters are integers)
         if self._ctl is not None:
             parts.append(self._ctl)
+        lr_back = self.device_rule and self._adam_hyper is not None
+        if lr_back:                                      # the learning rate the device rule arrived at, with the same transfer
+            parts.append(self._adam_hyper[:1].view(torch.int32))
         parts += [v.detach().reshape(1).to(torch.float32).view(torch.int32) for v in extra.values()]
         host = torch.cat(parts).cpu().numpy().view(np.float32)
         tot, acc = host[:6].astype(np.float64), host[6:12].astype(np.float64)
@@ -580,6 +704,13 @@ class MinibatchStep:
             if self.device_gate:
                 acc = np.array([c.sum[0], c.sum[1], c.sum[2], c.sum[3], c.sum[4], c.kl_sum], dtype=np.float64)
                 evaluated, applied, stopped = int(c.evaluated), int(c.applied), bool(c.stop)
+        if lr_back:                                      # back to the host: param_groups and the upload key agree with hyper6[0] again
+            lr = float(host[k])
+            k += 1
+            self.optimizer.param_groups[0]["lr"] = lr
+            if self._adam_key is not None:
+                self._adam_key = (lr,) + self._adam_key[1:]
+            self._lr_on_device = False
         if self.target_kl is None:
             s = tot / max(n_batches, 1)
             n_updates, stopped = None, False
@@ -615,8 +746,8 @@ class MinibatchStep:
                 self._apply()
             self._graphs = (g1, g2)
 
-    def __call__(self, obs, actions, old_logp, adv, ret):
-        mb = (obs, actions, old_logp, adv, ret)
+    def __call__(self, obs, actions, old_logp, adv, ret, old_values=None):
+        mb = (obs, actions, old_logp, adv, ret) + (() if self._old_values(old_values) is None else (old_values,))
         full = self._static is None or obs.shape[0] == self._static[0].shape[0]
         if not self.use_graph or not full:
             return self._eager(*mb)
@@ -643,7 +774,7 @@ class MinibatchStep:
 
 def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *, batch_size, n_epochs, clip_range=0.2,
                ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None, dist=None, step=None, target_kl=None,
-               extra=None):
+               extra=None, adaptive_lr=None, clip_range_vf=None, old_values=None):
     """SB3 `PPO.train()` on flattened rollout tensors (obs [n, D], actions [n, A], the rest [n]).  Device-agnostic torch;
     with `dist` (an initialised torch.distributed, RCCL on GPUs) every minibatch gradient is averaged over ranks with ONE
     all-reduce of the policy's flat gradient buffer.  `step`: a persistent `MinibatchStep` (keeps its captured graphs
@@ -653,13 +784,24 @@ def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *
     `target_kl`: SB3's early stop (see `MinibatchStep`).  On the all-HIP path the loop below keeps launching and the device gate makes
     the remaining launches no-ops: still one host sync per update.  On the other paths the host checks every minibatch and breaks.  With
     it the six scalars are means over every evaluated minibatch of the update.  `extra`: name -> 0-dim device tensor, or a callable
-    returning one that is evaluated after the last minibatch; fetched with the same transfer and returned under its name."""
+    returning one that is evaluated after the last minibatch; fetched with the same transfer and returned under its name.
+
+    `adaptive_lr` (a `KlAdaptiveLr`): the learning rate follows every minibatch's approx_kl (see `MinibatchStep`); `optimizer.param_groups[0]
+    ["lr"]` holds the rate the update arrived at when this returns.  `clip_range_vf` + `old_values` [n]: SB3's clipped value loss against
+    the rollout's values.  As with `target_kl`, a `step` that is passed in holds its own settings."""
     n = obs.shape[0]
     if step is None:
         step = MinibatchStep(policy, optimizer, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
-                             normalize_advantage=normalize_advantage, dist=dist, use_graph=False, target_kl=target_kl)
+                             normalize_advantage=normalize_advantage, dist=dist, use_graph=False, target_kl=target_kl, adaptive_lr=adaptive_lr,
+                             clip_range_vf=clip_range_vf)
     elif target_kl is not None and step.target_kl != float(target_kl):
         raise L.AmenvError(f"ppo_update: target_kl={target_kl!r} but the MinibatchStep given was built with target_kl={step.target_kl!r}")
+    elif adaptive_lr is not None and step.adaptive_lr != adaptive_lr:
+        raise L.AmenvError(f"ppo_update: adaptive_lr={adaptive_lr!r} but the MinibatchStep given was built with adaptive_lr={step.adaptive_lr!r}")
+    elif clip_range_vf is not None and step.clip_range_vf != float(clip_range_vf):
+        raise L.AmenvError(f"ppo_update: clip_range_vf={clip_range_vf!r} but the MinibatchStep given was built with clip_range_vf={step.clip_range_vf!r}")
+    step._old_values(old_values)
+    vclip = () if old_values is None else (old_values,)
     step.arm()
     total = torch.zeros(6, device=obs.device)
     n_batches = 0
@@ -671,12 +813,13 @@ def ppo_update(policy, optimizer, obs, actions, old_logp, advantages, returns, *
         indexed = step.fused_mlp and not step.use_graph
         if not indexed:
             obs_s, act_s, olp_s, adv_s, ret_s = obs[perm], actions[perm], old_logp[perm], advantages[perm], returns[perm]
+            val_s = None if old_values is None else old_values[perm]
         for start in range(0, n, batch_size):
             sl = slice(start, min(start + batch_size, n))
             if indexed:                                  # the kernel reads rows perm[sl] itself
-                step.indexed(obs, actions, old_logp, advantages, returns, perm[sl])
+                step.indexed(obs, actions, old_logp, advantages, returns, perm[sl], *vclip)
             else:
-                step(obs_s[sl], act_s[sl], olp_s[sl], adv_s[sl], ret_s[sl])
+                step(obs_s[sl], act_s[sl], olp_s[sl], adv_s[sl], ret_s[sl], *(() if val_s is None else (val_s[sl],)))
             if step.stopped:
                 break
             if epoch == n_epochs - 1:   # losses are reported for the last epoch only (no host sync inside the loop)
@@ -700,12 +843,17 @@ class PPO:
     bit), THEN the time-limit bootstrap gamma * V(terminal_observation) is added, then GAE -- SB3's order, where the bootstrap is added to
     the already normalised reward.  Its discount is the normaliser's own `gamma` (SB3's VecNormalize default .99, not PPO's).  With `dist`
     the return statistics are per rank, as the observation normaliser's are: every rank scales with the statistics of its own shard.
-    `env.stats()` and the logged `ep_rew_mean` stay raw."""
+    `env.stats()` and the logged `ep_rew_mean` stay raw.
+
+    `adaptive_lr` (a `KlAdaptiveLr`): `learning_rate` is the starting value and every minibatch's approx_kl moves it -- inside the
+    fused Adam step on the GPU's default update path, on the host elsewhere (`MinibatchStep`); the record's `learning_rate` is the value
+    after the update; a `learning_rate` schedule beside it, several ranks and `use_graph=True` raise.  `clip_range_vf` (a float or a
+    schedule of progress_remaining; None = off): SB3's clipped value loss against `buffer.values`."""
 
     def __init__(self, env, policy=None, learning_rate=2e-4, n_steps=2048, batch_size=128, n_epochs=12, gamma=0.995,
                  gae_lambda=0.9, clip_range=0.2, ent_coef=5e-4, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True,
                  net_arch=(128, 64, 64), seed=0, obs_normalizer=None, bootstrap_truncated=True, dist=None, use_graph=None, fused_rollout=False, fused_mlp=None, fused_rollout_fp32_stats=True,
-                 reward_normalizer=None, target_kl=None):
+                 reward_normalizer=None, target_kl=None, adaptive_lr=None, clip_range_vf=None):
         if env.state_dtype != torch.float32:
             raise L.AmenvError("PPO needs the fp32 environment")
         self.env, self.dist = env, dist
@@ -714,9 +862,22 @@ class PPO:
         if self.target_kl is not None and self.world > 1:
             raise L.AmenvError("target_kl with several ranks is not built: every rank would take the stop decision from its own shard's approx_kl and "
                                "the ranks would disagree on it (no multi-GPU machine was available to test an agreed stop); train with target_kl=None")
+        self.adaptive_lr = adaptive_lr
+        if adaptive_lr is not None:
+            if not isinstance(adaptive_lr, KlAdaptiveLr):
+                raise L.AmenvError(f"adaptive_lr must be a KlAdaptiveLr or None (got {type(adaptive_lr).__name__})")
+            if callable(learning_rate):
+                raise L.AmenvError("a learning_rate schedule together with adaptive_lr: two masters for one number; pass the starting value as a float")
+            if self.world > 1:
+                raise L.AmenvError("adaptive_lr with several ranks is not built: every rank would move its learning rate by its own shard's approx_kl and "
+                                   "the ranks would step with different rates; train with adaptive_lr=None")
         # SB3's Schedule: a float, or a callable of progress_remaining (1 at the start of `learn`, towards 0 at its end)
         self._lr_fn = learning_rate if callable(learning_rate) else None
         self._clip_fn = clip_range if callable(clip_range) else None
+        self._clip_vf_fn = clip_range_vf if callable(clip_range_vf) else None
+        if self._clip_vf_fn is not None:
+            clip_range_vf = float(self._clip_vf_fn(1.0))
+        self.clip_range_vf = None if clip_range_vf is None else float(clip_range_vf)
         self._progress = 1.0
         if self._lr_fn is not None:
             learning_rate = float(self._lr_fn(1.0))
@@ -741,7 +902,8 @@ class PPO:
         self.optimizer = torch.optim.Adam([self._leaf], lr=learning_rate, eps=1e-5, capturable=self.device.type == "cuda")
         self._step = MinibatchStep(self.policy, self.optimizer, clip_range=self.clip_range, ent_coef=self.ent_coef, vf_coef=self.vf_coef,
                                    max_grad_norm=self.max_grad_norm, normalize_advantage=self.normalize_advantage,
-                                   dist=dist if self.world > 1 else None, use_graph=use_graph, fused_mlp=fused_mlp, target_kl=self.target_kl)
+                                   dist=dist if self.world > 1 else None, use_graph=use_graph, fused_mlp=fused_mlp, target_kl=self.target_kl,
+                                   adaptive_lr=adaptive_lr, clip_range_vf=self.clip_range_vf)
         self.n_updates = 0   # optimiser steps applied so far (SB3's `_n_updates` counts epochs; with an early stop inside an epoch steps are the honest unit)
         self.obs_normalizer = obs_normalizer
         self.reward_normalizer = reward_normalizer
@@ -889,11 +1051,12 @@ class PPO:
         b, T = self.buffer, self.n_steps
         n = T * b.n_envs
         self._step.set_hyper(None if self._lr_fn is None else float(self._lr_fn(self._progress)),
-                             None if self._clip_fn is None else float(self._clip_fn(self._progress)))
-        self.clip_range = self._step.clip_range
+                             None if self._clip_fn is None else float(self._clip_fn(self._progress)),
+                             None if self._clip_vf_fn is None else float(self._clip_vf_fn(self._progress)))
+        self.clip_range, self.clip_range_vf = self._step.clip_range, self._step.clip_range_vf
         rec = ppo_update(self.policy, self.optimizer, b.obs[:T].reshape(n, -1), b.actions.reshape(n, -1), b.logp.reshape(n),
                          b.advantages.reshape(n), b.returns.reshape(n), batch_size=self.batch_size, n_epochs=self.n_epochs,
-                         generator=self._gen, step=self._step,
+                         generator=self._gen, step=self._step, old_values=None if self.clip_range_vf is None else b.values.reshape(n),
                          extra=dict(explained_variance=explained_variance(b.values, b.returns), std=lambda: self.policy.log_std.detach().exp().mean()))
         self.n_updates += int(rec["n_updates"])
         rec.update(n_updates=self.n_updates, learning_rate=self.learning_rate, clip_range=self.clip_range)
@@ -975,12 +1138,14 @@ class PPO:
     def save(self, path):
         """A zip with SB3's member names: `policy.pth` (SB3 keys: loadable into an SB3 `ActorCriticPolicy`),
         `policy.optimizer.pth` (this class's Adam state) and `data` (hyper-parameters as plain JSON: under a schedule the CURRENT numeric
-        learning_rate / clip_range -- schedules are not serialised, whoever resumes passes them again -- plus target_kl and n_updates); with a reward normaliser one more
+        learning_rate / clip_range / clip_range_vf -- schedules are not serialised, whoever resumes passes them again -- plus target_kl, n_updates and, with
+        `adaptive_lr`, the rule's five numbers; the learning rate is the one the rule arrived at, as a float that holds its float32 exactly); with a reward normaliser one more
         member, `reward_normalizer.npz` (its `state_dict`), which `load` restores into this model's normaliser.  It is NOT a complete
         SB3 archive (SB3's `data` holds cloudpickled objects); use `policy.pth` to move weights either way."""
         path = path if str(path).endswith(".zip") else str(path) + ".zip"
         data = {k: getattr(self, k) for k in ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range", "ent_coef",
-                                              "vf_coef", "max_grad_norm", "normalize_advantage", "num_timesteps", "seed", "target_kl", "n_updates")}
+                                              "vf_coef", "max_grad_norm", "normalize_advantage", "num_timesteps", "seed", "target_kl", "n_updates", "clip_range_vf")}
+        data.update(adaptive_lr=None if self.adaptive_lr is None else self.adaptive_lr.state_dict())
         data.update(format="amenv-ppo", draw=int(self._draw), learning_rate=self.optimizer.param_groups[0]["lr"], net_arch=list(self.policy.net_arch),
                     obs_dim=self.policy.obs_dim, act_dim=self.policy.act_dim)
         with zipfile.ZipFile(path, "w") as z:
@@ -1011,7 +1176,8 @@ class PPO:
         return self
 
     def load(self, path):
-        """Full resume from a zip written by `save()`: weights, Adam moments / step count, learning rate and the timestep counter
+        """Full resume from a zip written by `save()`: weights, Adam moments / step count, learning rate (bit for bit; under `adaptive_lr` the
+        rule's numbers too, into a model that was built with a rule) and the timestep counter
         (`PPO.load(CHECKPOINT_PATH, env=...)` followed by `learn`, v2/rl_train.py:33-35,56).  An SB3 archive has no optimiser state
         this class can read without unpickling: for those use `load_policy` (weights only)."""
         with zipfile.ZipFile(path if str(path).endswith(".zip") else str(path) + ".zip") as z:
@@ -1037,6 +1203,8 @@ class PPO:
             self.num_timesteps = int(data.get("num_timesteps", self.num_timesteps))
             self.n_updates = int(data.get("n_updates", self.n_updates))
             self._draw = int(data.get("draw", self._draw))   # action-noise counter: resumed rollouts draw fresh noise
+            if data.get("adaptive_lr") is not None and self.adaptive_lr is not None:   # the rule's numbers, into a model built with one
+                self.adaptive_lr = self._step.adaptive_lr = KlAdaptiveLr(**data["adaptive_lr"])
             if "reward_normalizer.npz" in names and self.reward_normalizer is not None:
                 with np.load(io.BytesIO(z.read("reward_normalizer.npz")), allow_pickle=False) as sd:
                     self.reward_normalizer.load_state_dict({k: sd[k] for k in sd.files})

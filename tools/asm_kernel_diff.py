@@ -14,6 +14,10 @@ their place, the bools read as a bit mask (first bool = bit 0): `k<float, 4, tru
 Prints the counts, every kernel that is in one file only, and for every kernel that differs both sets of resource numbers and the first
 differing line; exit status 1 unless the two files hold the same kernels with identical text and metadata.
 
+--no-block-names: drop the IR block names the compiler prints as comments behind labels (`.LBB3_15: ; %_ZN..bodyILb0EEE...exit`, `; %bb.67: ;
+%...exit1051.i`): they carry the mangled names of INLINED functions, so a new defaulted template parameter or argument of a __forceinline__
+body renames them in kernels whose instructions did not move.  Everything that is not such a comment is still compared.
+
 --brief, for a library whose kernels differ by the hundred: one line per differing kernel with the resource numbers that moved (`a>b`; every
 number of RES and the occupancy that is not listed is equal), the differing kernels in which none moved counted per kernel name, and with
 --list-same the identical kernels counted per kernel name."""
@@ -63,8 +67,10 @@ def fold(name, n):
     return f"{head}<{', '.join(parts[:-n] + [str(mask) + 'u'])}>"
 
 
-def load(path, nfold):
+def load(path, nfold, no_block_names=False):
     lines = open(path).read().split("\n")
+    if no_block_names:
+        lines = [re.sub(r"(^; %bb\.\d+:|:)\s*; %\S+$", r"\1", ln) for ln in lines]
     label = {ln.split(":", 1)[0]: i for i, ln in enumerate(lines) if re.match(r"[A-Za-z_][\w$.]*:", ln)}   # `symbol:   ; @symbol`
     syms = [ln.split()[1] for ln in lines if ln.startswith("\t.amdhsa_kernel ")]
     dem = demangle(syms)
@@ -112,9 +118,10 @@ if __name__ == "__main__":
     ap.add_argument("b")
     ap.add_argument("--fold-bools", type=int, default=0, metavar="N")
     ap.add_argument("--list-same", action="store_true", help="also list the kernels that are identical, with their resource numbers")
+    ap.add_argument("--no-block-names", action="store_true", help="ignore the IR block names in label comments (names of inlined functions)")
     ap.add_argument("--brief", action="store_true", help="one line per differing kernel; --list-same counts the identical ones per kernel name")
     a = ap.parse_args()
-    A, B = load(a.a, a.fold_bools), load(a.b, 0)
+    A, B = load(a.a, a.fold_bools, a.no_block_names), load(a.b, 0, a.no_block_names)
     both = sorted(set(A) & set(B))
     same = [k for k in both if A[k] == B[k]]
     diff = [k for k in both if A[k] != B[k]]

@@ -5,7 +5,9 @@
                                                     another build of it (e.g. the parent commit's), alternating in ONE process, at 65,536 and
                                                     1,024 samples; with --json FILE the table is written there.  Both libraries are called
                                                     through the plain entry points; this tree's also through the _ctl ones, gate open and gate shut
-                                                    (what a minibatch step costs after target_kl tripped: four early-exit launches).
+                                                    (what a minibatch step costs after target_kl tripped: four early-exit launches), with the
+                                                    KL-adaptive Adam step (amenv_ppo_adam_step_adapt) and with the clipped value loss
+                                                    (amenv_ppo_mlp_step_vclip), DESIGN 4u.
 """
 import argparse
 import ctypes as C
@@ -57,13 +59,16 @@ _MLP = [_P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_int64, C.c_float, C.c_float,
 _ADAM = [_P] * 5 + [C.c_int64, _P, _P, _P]
 
 
-def _bind(path, ctl):
+def _bind(path, new):
     lib = C.CDLL(path)
     lib.amenv_ppo_mlp_workspace_bytes.restype = C.c_size_t
     lib.amenv_ppo_mlp_step.argtypes, lib.amenv_ppo_adam_step.argtypes = _MLP + [_P], _ADAM + [_P]
-    if ctl:
+    if hasattr(lib, "amenv_ppo_ctl_arm"):
         lib.amenv_ppo_mlp_step_ctl.argtypes, lib.amenv_ppo_adam_step_ctl.argtypes = _MLP + [_P, _P], _ADAM + [_P, _P]
         lib.amenv_ppo_ctl_arm.argtypes = [_P, C.c_float, _P]
+    if new:
+        lib.amenv_ppo_adam_step_adapt.argtypes = _ADAM + [_P, C.POINTER(amd._lib.PpoLrRule), _P]
+        lib.amenv_ppo_mlp_step_vclip.argtypes = _MLP + [_P, _P, C.c_float, _P]
     return lib
 
 
@@ -79,6 +84,8 @@ def ab(other, reps, rounds, out):
         P0 = pol.flat_param.detach().clone()
         obs = torch.randn(n, D, device="cuda"); actions = torch.randn(n, A, device="cuda"); olp = torch.randn(n, device="cuda") * 0.1 - 9
         adv = torch.randn(n, device="cuda"); ret = torch.randn(n, device="cuda")
+        old_values = torch.randn(n, device="cuda") * 0.5
+        rule = amd.KlAdaptiveLr().struct()
         k = P0.numel()
         grad, m, v = (torch.zeros(k, device="cuda") for _ in range(3))
         stp = torch.zeros((), device="cuda")
@@ -90,13 +97,17 @@ def ab(other, reps, rounds, out):
         def one(lib, use_ctl):
             a = (p(prm), D, A, p(obs), p(actions), p(olp), p(adv), p(ret), None, n, 0.2, 5e-4, 0.5, 1, p(grad), p(stats), p(ws))
             b = (p(prm), p(grad), p(m), p(v), p(stp), k, p(hyper), C.c_void_p(stats.data_ptr() + 16), p(ticket))
-            if use_ctl:
+            if use_ctl == "adapt":
+                assert lib.amenv_ppo_mlp_step_ctl(*a, p(ctl), None) == 0 and lib.amenv_ppo_adam_step_adapt(*b, p(ctl), C.byref(rule), None) == 0
+            elif use_ctl == "vclip":
+                assert lib.amenv_ppo_mlp_step_vclip(*a, p(ctl), p(old_values), 0.2, None) == 0 and lib.amenv_ppo_adam_step_ctl(*b, p(ctl), None) == 0
+            elif use_ctl:
                 assert lib.amenv_ppo_mlp_step_ctl(*a, p(ctl), None) == 0 and lib.amenv_ppo_adam_step_ctl(*b, p(ctl), None) == 0
             else:
                 assert lib.amenv_ppo_mlp_step(*a, None) == 0 and lib.amenv_ppo_adam_step(*b, None) == 0
 
         def timed(lib, use_ctl, limit):
-            prm.copy_(P0); m.zero_(); v.zero_(); stp.zero_()
+            prm.copy_(P0); m.zero_(); v.zero_(); stp.zero_(); hyper[0] = 2e-4
             if use_ctl:
                 assert lib.amenv_ppo_ctl_arm(p(ctl), limit, None) == 0
             for _ in range(5): one(lib, use_ctl)
@@ -107,15 +118,22 @@ def ab(other, reps, rounds, out):
             e1.record(); torch.cuda.synchronize()
             return e0.elapsed_time(e1) / reps * 1e3
 
-        cases = [("other plain", "other", False, 0.0), ("this plain", "this", False, 0.0), ("other plain (again)", "other", False, 0.0),
-                 ("this ctl, gate open", "this", True, 0.0), ("this ctl, gate shut", "this", True, 1e-12)]
+        other_ctl = hasattr(libs["other"], "amenv_ppo_ctl_arm")      # (a parent from before the control block has no _ctl entry points)
+        cases = [("other plain", "other", False, 0.0), ("this plain", "this", False, 0.0), ("other plain (again)", "other", False, 0.0)]
+        if other_ctl:
+            cases += [("other ctl, gate open", "other", True, 0.0)]
+        cases += [
+                 ("this ctl, gate open", "this", True, 0.0), ("this ctl, gate shut", "this", True, 1e-12),
+                 ("this ctl + adam_step_adapt", "this", "adapt", 0.0), ("this mlp_step_vclip + ctl", "this", "vclip", 0.0)]
+        if other_ctl:
+            cases += [("other ctl, gate open (again)", "other", True, 0.0)]
         res = {name: [] for name, *_ in cases}
         for _ in range(rounds):                       # alternating: every round visits every case once
             for name, which, use_ctl, limit in cases:
                 res[name].append(timed(libs[which], use_ctl, limit))
         table[str(n)] = {name: dict(median_us=round(statistics.median(x), 2), min_us=round(min(x), 2), max_us=round(max(x), 2)) for name, x in res.items()}
         for name, r in table[str(n)].items():
-            print(f"n={n:6d} {name:22s} median {r['median_us']:8.2f} us  [{r['min_us']:.2f} .. {r['max_us']:.2f}] per minibatch step ({rounds} rounds x {reps} steps)")
+            print(f"n={n:6d} {name:28s} median {r['median_us']:8.2f} us  [{r['min_us']:.2f} .. {r['max_us']:.2f}] per minibatch step ({rounds} rounds x {reps} steps)")
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
