@@ -440,9 +440,18 @@ __device__ __forceinline__ uint32_t step_lane(const HotParams<T, NROT>& P, const
     __builtin_amdgcn_sched_barrier(0);                                                       \
   } while (0)
 #define AMENV_STAMP_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// the constant-frequency counter (100 MHz, one for the device): puts waves of different workgroups -- whose s_memtime clocks are their
+// own XCD's -- on one time axis
+#define AMENV_STAMP_RT(k)                                                                    \
+  do {                                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+    stamps_[k] = __builtin_amdgcn_s_memrealtime();                                           \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+  } while (0)
 #else
 #define AMENV_STAMP(k)
 #define AMENV_STAMP_DRAIN()
+#define AMENV_STAMP_RT(k)
 #endif
 constexpr int kStampSlots = 8, kStampWaves = 64, kStampBase = kStatsReplicas * kStatsStride;
 

@@ -324,6 +324,12 @@ template <typename A, typename... R> __device__ __forceinline__ void team_arg(A 
 // last env) are masked by their OFFSET instead of by EXEC, so the store tail of the step kernel has no branches
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t team_rsrc(void* p, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(bytes), 0x00020000); }
 constexpr uint32_t kOob = 0xFFFFFFFFu;
+// Cache policy of every store of the step kernel (the builtins' last argument): 0 = default (the line stays dirty in the XCD's L2 and the
+// release at the kernel boundary writes it back), 16 = sc1, write-through.  Measured both ways, DESIGN section 4c "The end of a launch".
+#ifndef AMENV_TEAM_STORE_POLICY
+#define AMENV_TEAM_STORE_POLICY 0
+#endif
+constexpr int kTeamStorePolicy = AMENV_TEAM_STORE_POLICY;
 
 // The wave-uniform parameters of the step kernel: scalar loads from the device block behind the per-lane table (see team_block_bytes).
 // Each role reads them inside its branch through a pointer it has passed through an empty asm (team_launder): loads the compiler can tell
@@ -385,7 +391,8 @@ template <typename X> __device__ __forceinline__ ColdParams team_late_cold() {
 // and episode-end code (rarely run on any one CU) costs ~7 clocks per instruction: with everything inline those waves ran 2,100 clocks
 // (0.9 us of 5.8) longer than the rest (tools/stamp_team.py).  So the helper wave evaluates team_reset while the main wave integrates and
 // leaves the values in LDS; after the kernel's ONE barrier the main wave's episode-end path is three LDS reads and the reset observation
-// (+ three terminal-observation stores after its regular stores), and the helper writes Monitor's return / length and adds the ended episodes to its replica of the
+// (+ the rewrite of the row's state, observation and info bits, which like every row's left before the barrier, its terminal observation
+// and Monitor's return / length), and the helper adds the ended episodes to its replica of the
 // totals (owned for the launch when the grid has at most kStatsReplicas workgroups: plain read-modify-write; otherwise atomics).
 // Round 3: the helper shares every SIMD with some main wave, so it only spends the reset's ~200 instructions on rows that CAN end their
 // episode in this step -- a conservative test on the loaded state (time limit: exact; hold counter at its limit; height / range within one
@@ -408,12 +415,19 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   __shared__ uint32_t have[ROWS];                   // per row: the helper has left reset values
   __shared__ unsigned long long acc[S_COUNT];      // this launch's additions to the Monitor totals
 #ifdef AMENV_STAMPS
-  unsigned long long stamps_[kStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // Both roles stamp: a wave fills TWO rows of the stamp area (kTeamStampSlots words; tools/stamp_team.py names them), all MW + 1 waves
+  // of kTeamStampGroups workgroups spread evenly over the grid.  Words 9 / 10 are the constant-frequency counter at the wave's first and
+  // last stamp: s_memtime orders the waves of one workgroup, the constant-frequency counter those of different workgroups.
+  constexpr int kTeamStampSlots = 2 * kStampSlots, kTeamStampGroups = kStampWaves / (2 * (MW + 1));
+  unsigned long long stamps_[kTeamStampSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int stamp_stride_ = int(gridDim.x) >= kTeamStampGroups ? int(gridDim.x) / kTeamStampGroups : 1;
+  const int stamp_group_ = int(blockIdx.x) % stamp_stride_ == 0 && int(blockIdx.x) / stamp_stride_ < kTeamStampGroups ? int(blockIdx.x) / stamp_stride_ : -1;
 #endif
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int role = wave == MW ? 1 : 0;             // waves 0..MW-1 integrate four envs each, the last wave helps all of them
   team_arg(blob, n_envs, n_blocks, actions, lane_consts);   // what the first loads need: ONE small batch of argument loads, nothing else in front of it
   AMENV_STAMP(0);
+  AMENV_STAMP_RT(9);
   // The arguments of the first loads arrive in ONE batch of scalar loads issued at wave start (team_arg above); the role branch follows at
   // once, and each role issues only the loads it uses.  An integrating wave: state, actions, then the per-lane table (vector loads
   // return in order: the state stands in front).  The scheduling fence behind its loads keeps them in front of the (second, dependent)
@@ -440,6 +454,8 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
       E.step = iv.x; E.counter = iv.y; E.flags = iv.z; E.episode = iv.w;
     }
     const TeamParamsT<X> P = team_load_params<X>(team_launder(lane_consts));
+    AMENV_STAMP_DRAIN();
+    AMENV_STAMP(2);        // (helper) loads landed
     const X ce[3] = {L.cc == 0 ? X(1) : X(0), L.cc == 1 ? X(1) : X(0), L.cc == 2 ? X(1) : X(0)};   // TC_E0..E2 of this lane (team_reset_draw reads nothing else)
     static_assert(TC_E0 == 0 && TC_E1 == 1 && TC_E2 == 2, "ce[] stands in for c[] in team_reset_draw");
     const bool owned = n_blocks <= kStatsReplicas;   // wave-uniform
@@ -476,15 +492,19 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
 #ifdef AMENV_TEAM_DIAG_NOPOST   // diagnostic build: the helper leaves after the barrier (no Monitor service: timing only)
     return;
 #endif
+    AMENV_STAMP(5);        // (helper) barrier passed
     const bool ended = hlead && (fl[hlead ? row : 0][0] & 1u) != 0;   // one lane per ended row
+#ifdef AMENV_STAMPS
+    stamps_[3] = __ballot(ended) != 0ull ? 1ull : 0ull;   // (not a time) did a row of this workgroup end its episode?
+    stamps_[8] = 1ull;                                    // (not a time) role
+    stamps_[12] = fetched ? 1ull : 0ull;                  // (not a time) an end was predicted
+#endif
     if (__ballot(ended) != 0ull) {   // wave-uniform
       if (!fetched && owned && L.lane < S_COUNT) mine = totals[L.lane];
       if (ended) {
         const uint32_t bits = fl[row][1];          // (ended: row < ROWS)
         const int ep_len = int(fl[row][2]);
-        const float ep_ret = __uint_as_float(fl[row][3]);
-        if (tl.ep_return) tl.ep_return[i] = ep_ret;
-        if (tl.ep_len) tl.ep_len[i] = ep_len;
+        const float ep_ret = __uint_as_float(fl[row][3]);   // (Monitor's return / length rows: the integrating wave stores them, from its registers)
         if (owned) accumulate_stats_lane(acc, 0, bits, ep_len, ep_ret);               // LDS adds
         else accumulate_stats_lane(tl.stats, int(blockIdx.x), bits, ep_len, ep_ret);  // global atomics
       }
@@ -494,6 +514,14 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
         if (L.lane < S_COUNT) totals[L.lane] = mine + acc[L.lane];
       }
     }
+    AMENV_STAMP(6);        // (helper) service done
+#ifdef AMENV_STAMPS
+    AMENV_STAMP_DRAIN();
+    AMENV_STAMP(7);        // (helper) stores acknowledged
+    AMENV_STAMP_RT(10);
+    if (L.lane == 0 && stamp_group_ >= 0)
+      for (int kk = 0; kk < kTeamStampSlots; kk++) tl.stats[kStampBase + (stamp_group_ * (MW + 1) + MW) * kTeamStampSlots + kk] = stamps_[kk];
+#endif
     return;
   }
 #ifndef AMENV_TEAM_DIAG_NOPRIO
@@ -521,25 +549,77 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
   const __amdgpu_buffer_rsrc_t r_obs = team_rsrc(A.obs, obs_bytes), r_term = team_rsrc(A.tl.terminal_obs, A.tl.terminal_obs ? obs_bytes : 0u);
   // the same for the state stores and the per-env outputs of the fp32 build: team_store's offsets depend on the lane and the env only (byte
   // offsets into this workgroup's tile; the lead lane's slot in reward / info / done, out of range for every other lane)
-  uint32_t so1 = 0, so2 = 0, voR = kOob, voD = kOob;
+  uint32_t so1 = 0, so2 = 0;
+  uint32_t voR = active && L.lead ? uint32_t(i) * 4u : kOob, voD = active && L.lead ? uint32_t(i) : kOob;
   if constexpr (sizeof(X) == 4) {
     constexpr uint32_t GB = 64u * 4u * 4u;
     const uint32_t eoff = (uint32_t(i & 63) * 4u + uint32_t(L.cc)) * 4u;
     so1 = kIntBytes + uint32_t(L.bb) * GB + eoff;                                        // quad b writes group b
     so2 = L.q2 ? eoff : kIntBytes + (L.q0 ? 5u : (L.q1 ? 6u : 4u)) * GB + eoff;         // joint angles | joint rates | int plane | waypoint
-    voR = active && L.lead ? uint32_t(i) * 4u : kOob; voD = active && L.lead ? uint32_t(i) : kOob;
-    asm volatile("" : "+v"(so1), "+v"(so2), "+v"(voR), "+v"(voD));
+    asm volatile("" : "+v"(so1), "+v"(so2));
   }
+  asm volatile("" : "+v"(voR), "+v"(voD));
   AMENV_STAMP(1);          // loads issued
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(2);          // loads landed
   TeamOutT<X> o = team_advance<NROT, true>(P, Cm, L, E, act, actj, i, active, nullptr, nullptr, nullptr);
   const bool resets = o.ended && (P.flags & AMENV_FLAG_AUTO_RESET);
+  AMENV_STAMP(4);          // mixer + RK4 + forward kinematics + task step
+  // The row's stores, by the offsets formed above.  on: this row stores at all (an out-of-range offset otherwise: no branch); wp: quad 3
+  // writes the waypoint group too (it changes at a reset only).
+  const uint32_t nb = uint32_t(n_envs);
+  auto store_state = [&](bool on, bool wp) {
+    if constexpr (sizeof(X) == 4) {
+      const __amdgpu_buffer_rsrc_t r_tile = team_rsrc(tile, tile_bytes);
+      const bool l3 = L.cc == 3;
+      const X g0 = sel(l3, E.final_yaw, E.y.P), g1 = sel(l3, E.last_distance, E.y.V), g3 = sel(l3, E.ep_return, E.y.W);
+      const X sv = sel(L.q0, g0, sel(L.q1, g1, sel(L.q2, E.y.Q, g3)));
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(sv), r_tile, int(on ? so1 : kOob), 0, kTeamStorePolicy);
+      const int ival = sel(L.cc == 0, E.step, sel(L.cc == 1, E.counter, sel(L.cc == 2, E.flags, E.episode)));
+      const float s2 = sel(L.q0, E.y.TH, sel(L.q1, E.y.THD, sel(L.q2, __int_as_float(ival), E.WP)));
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(s2), r_tile, int(on && (L.bb != 3 || wp) ? so2 : kOob), 0, kTeamStorePolicy);
+    } else {
+      if (on) team_store(tile, i, L, E, wp);
+    }
+  };
+  auto store_obs = [&](const __amdgpu_buffer_rsrc_t& r, X a, X b, X c, bool on) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(a)), r, int(on ? voA : kOob), 0, kTeamStorePolicy);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(b)), r, int(on ? voB : kOob), 0, kTeamStorePolicy);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(c)), r, int(on ? voC : kOob), 0, kTeamStorePolicy);
+  };
+  auto store_info = [&](bool on) {   // lead lane of a real env; every other lane's offset is out of range
+    if constexpr (sizeof(X) == 4) __builtin_amdgcn_raw_buffer_store_b32(int(o.bits), team_rsrc(A.info, nb * 4u), int(on ? voR : kOob), 0, kTeamStorePolicy);
+    else if (on && active && L.lead) A.info[uint32_t(i)] = o.bits;
+  };
+  // A store leaves when its value is final.  99 % of the rows end no episode, and everything such a row writes is final HERE: its stores
+  // issue in front of the flag word and the barrier and drain under the other waves' tool-point and task arithmetic, and behind the
+  // barrier the wave has nothing left to issue.  A row that ends and resets writes its pre-reset values here like any other and REWRITES
+  // state, waypoint group, observation and info bits behind the barrier: same lane, same address, and the stores of one lane to one
+  // address are performed in program order, so the later one is what memory holds.
+  // The helper of this workgroup reads P, V and the int plane of these rows with three loads at ITS start and nothing but time orders
+  // them against the state store below: the helper starts ~200 clocks after the first integrating wave and has its loads back by
+  // ~1,550 (tools/stamp_team.py), the store cannot issue before this wave's own loads have landed and the RK4's ~640 instructions have
+  // issued behind them, ~5,300 clocks in and never under ~4,800.  A margin of thousands of clocks, not an ordering the memory model gives.
+  // (Four + one workgroups only: where several workgroups share a CU -- the one + one geometry -- the early stores measured slower,
+  // and a row's stores follow the barrier, the reset values already in them.)
+  constexpr bool kEarly = MW == 4;
+  auto store_row = [&](bool wp) {
+    store_state(true, wp);
+    store_obs(r_obs, o.vA, o.vB, o.vC, true);
+    if constexpr (sizeof(X) == 4) {
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.reward), team_rsrc(A.reward_out, nb * 4u), int(voR), 0, kTeamStorePolicy);
+      __builtin_amdgcn_raw_buffer_store_b8(uint8_t(o.ended ? 1 : 0), team_rsrc(A.done, nb), int(voD), 0, kTeamStorePolicy);
+    } else {
+      if (active && L.lead) { A.reward_out[uint32_t(i)] = o.reward; A.done[uint32_t(i)] = o.ended ? 1 : 0; }
+    }
+    store_info(true);
+  };
+  if constexpr (kEarly) store_row(false);
+  AMENV_STAMP(11);         // last pre-barrier store issued
   if (L.lead) {
     fl[row][0] = (o.ended && active ? 1u : 0u) | (resets ? 2u : 0u);
     if (o.ended) { fl[row][1] = o.bits; fl[row][2] = uint32_t(o.ep_len); fl[row][3] = __float_as_uint(o.ep_ret); }
   }
-  AMENV_STAMP(4);          // mixer + RK4 + forward kinematics + task step
 #ifdef AMENV_STAMPS
   stamps_[3] = __ballot(o.ended && active) != 0ull ? 1ull : 0ull;   // (not a time) did one of this wave's envs end its episode?
 #endif
@@ -554,40 +634,26 @@ __global__ __launch_bounds__(64 * (MW + 1)) void step_kernel_team(void* __restri
     team_apply_reset(L, team_reset_obs(P, L, R), E, o);
   }
   AMENV_STAMP(5);          // barrier + reset values
-  if constexpr (sizeof(X) == 4) {   // team_store with the offsets formed above; the waypoint group (quad 3) is written at a reset only
-    const __amdgpu_buffer_rsrc_t r_tile = team_rsrc(tile, tile_bytes);
-    const bool l3 = L.cc == 3;
-    const X g0 = sel(l3, E.final_yaw, E.y.P), g1 = sel(l3, E.last_distance, E.y.V), g3 = sel(l3, E.ep_return, E.y.W);
-    const X sv = sel(L.q0, g0, sel(L.q1, g1, sel(L.q2, E.y.Q, g3)));
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(sv), r_tile, int(so1), 0, 0);
-    const int ival = sel(L.cc == 0, E.step, sel(L.cc == 1, E.counter, sel(L.cc == 2, E.flags, E.episode)));
-    const float s2 = sel(L.q0, E.y.TH, sel(L.q1, E.y.THD, sel(L.q2, __int_as_float(ival), E.WP)));
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(s2), r_tile, int(L.bb == 3 && !resets ? kOob : so2), 0, 0);
-  } else {
-    team_store(tile, i, L, E, resets);
-  }
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vA)), r_obs, int(voA), 0, 0);
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vB)), r_obs, int(voB), 0, 0);
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(o.vC)), r_obs, int(voC), 0, 0);
-  if constexpr (sizeof(X) == 4) {   // lead lane of a real env; every other lane's offset is out of range
-    const uint32_t nb = uint32_t(n_envs);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.reward), team_rsrc(A.reward_out, nb * 4u), int(voR), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b8(uint8_t(o.ended ? 1 : 0), team_rsrc(A.done, nb), int(voD), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(int(o.bits), team_rsrc(A.info, nb * 4u), int(voR), 0, 0);
-  } else {
-    if (active && L.lead) { A.reward_out[uint32_t(i)] = o.reward; A.done[uint32_t(i)] = o.ended ? 1 : 0; A.info[uint32_t(i)] = o.bits; }
-  }
-  if (any_end) {           // wave-uniform; rows that did not end store nowhere
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tA)), r_term, int(o.ended ? voA : kOob), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tB)), r_term, int(o.ended ? voB : kOob), 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(float(tC)), r_term, int(o.ended ? voC : kOob), 0, 0);
+  if constexpr (!kEarly) store_row(resets);
+  if (any_end) {           // wave-uniform; a row that did not end stores nowhere, a row that ended without a reset its terminal observation only
+    if constexpr (kEarly) {
+      store_state(resets, true);                            // the rewrite (see above): the reset state, with the new waypoint
+      store_obs(r_obs, o.vA, o.vB, o.vC, resets);           // ... the reset observation
+      store_info(resets);                                   // ... and the info bits with AMENV_INFO_WAS_RESET
+    }
+    store_obs(r_term, tA, tB, tC, o.ended);
+    // Monitor's return and length of the ended rows: in the lead lane's registers since the task step (the helper, which used to store
+    // them, had to fetch them from LDS on a path that runs a few times per launch); a null pointer makes an empty descriptor
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(o.ep_ret), team_rsrc(A.tl.ep_return, A.tl.ep_return ? nb * 4u : 0u), int(o.ended ? voR : kOob), 0, kTeamStorePolicy);
+    __builtin_amdgcn_raw_buffer_store_b32(o.ep_len, team_rsrc(A.tl.ep_len, A.tl.ep_len ? nb * 4u : 0u), int(o.ended ? voR : kOob), 0, kTeamStorePolicy);
   }
   AMENV_STAMP(6);          // stores issued
 #ifdef AMENV_STAMPS
   AMENV_STAMP_DRAIN();
   AMENV_STAMP(7);          // stores acknowledged
-  if (L.lane == 0 && blockIdx.x * MW + wave < kStampWaves)   // the integrating waves of the first workgroups
-    for (int kk = 0; kk < kStampSlots; kk++) A.tl.stats[kStampBase + (blockIdx.x * MW + wave) * kStampSlots + kk] = stamps_[kk];
+  AMENV_STAMP_RT(10);
+  if (L.lane == 0 && stamp_group_ >= 0)
+    for (int kk = 0; kk < kTeamStampSlots; kk++) A.tl.stats[kStampBase + (stamp_group_ * (MW + 1) + wave) * kTeamStampSlots + kk] = stamps_[kk];
 #endif
 }
 
