@@ -55,6 +55,10 @@ def main():
     ap.add_argument("--action-history", type=int, default=None, metavar="H",
                     help="append the last H (1 or 2) action rows each env was given to its observation rows: the commands still in flight under "
                          "--action-delay / --rotor-lag (fp32 rigid vehicles; not with --normalize-obs --fused-rollout; DESIGN 4n)")
+    ap.add_argument("--rate-control", type=float, nargs="*", default=None, metavar="X",
+                    help="body-rate actions: entries 1..3 of an action are rate commands and a rate loop inside the step forms the moments (what a PX4 "
+                         "offboard controller accepts).  No values: max_rate 5 5 2.5 rad/s, gain 25 25 10 1/s; or six: RX RY RZ GX GY GZ (fp32 rigid "
+                         "vehicles; not with --warm-start-pid; DESIGN 4v)")
     ap.add_argument("--target-kl", type=float, default=None, metavar="X",
                     help="SB3's target_kl: leave an update once a minibatch's approx_kl exceeds 1.5 X (decided on the GPU, no extra synchronisation; one rank only)")
     ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear", "adaptive"],
@@ -72,6 +76,8 @@ def main():
                     help="initialise the actor by behaviour cloning of the PID + minimum-snap baseline (amd.clone_pid_policy; 0 = plain cloning, k = k DAgger rounds). "
                          "Needed for the hexacopter vehicles: from SB3's default initialisation PPO does not leave the free-fall plateau there (profiles/r03/ppo_hexa_sweep_*.json)")
     a = ap.parse_args()
+    if a.rate_control is not None and len(a.rate_control) not in (0, 6):
+        ap.error("--rate-control takes no values or six: RX RY RZ GX GY GZ")
     import torch
     import rl_aerial_manipulator_amd as amd
     from rl_aerial_manipulator_amd import sharding
@@ -97,6 +103,8 @@ def main():
             e.set_action_delay(amd.ActionDelay(*a.action_delay))
         if a.action_history is not None:
             e.set_action_history(amd.ActionHistory(a.action_history))
+        if a.rate_control is not None:
+            e.set_rate_control(amd.RateControl(a.rate_control[:3], a.rate_control[3:]) if a.rate_control else amd.RateControl())
         return e
 
     env = make_env(a.envs, a.seed, sh.env_id_offset, cfg)

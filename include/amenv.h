@@ -608,6 +608,36 @@ int amenv_set_action_history(amenv* env, int32_t rows);
 /* the row width every obs / terminal_obs buffer of this handle must have now: base + 4 rows */
 int32_t amenv_obs_dim(const amenv* env);
 
+/* ---- body-rate actions with an inner rate loop -----------------------------------------------------------------
+ * Opt-in, per handle, off by default; composes with randomisation, rotor lag, sensor noise, the action delay and the action history.
+ * While it is on, entries 1..3 of an action row are body-rate COMMANDS in units of max_rate (the thrust entry keeps its meaning), and a
+ * rate loop inside the step turns them into the moment action the unchanged step consumes.  With a the row the step is about to apply
+ * (behind the latency: the delayed command), w the env's body rates at the start of the step, I the NOMINAL inertia of the config (not the
+ * randomised one) and ms = task.moment_scale, in fp32 and in this order:
+ *   w_cmd_k = a_k * max_rate_k;   u_k = gain_k * (w_cmd_k - w_k);   tau = I u  (+ w x (I w) with gyro_feedforward);   a'_k = tau_k * float(1 / ms)
+ * Everything behind a' is the step as without the switch: M = a' * ms, mixer, per-rotor clamp, lag, RK4, reward, observation.  Nothing clips
+ * a'; the rotor clamp is the actuator limit.  The loop is proportional plus feed-forward and keeps no state: the state layout, amenv_get_state
+ * / amenv_set_state, the reset draws and sharding by global env id are unaffected.  The rows of the action history, of the delay's buffer and
+ * of the closed loop's `actions` are the commands as given, never a'.
+ * Served: fp32 handles of what amenv_set_action_delay serves (rigid vehicles with 4 or 6 rotors, every task, lane and helper-wave step
+ * kernels, amenv_rollout, amenv_rollout_policy[_norm] and amenv_evaluate_policy in the one-lane-per-env form: a config the lane-quad closed
+ * loop would serve runs the one-lane form while rate control is on).
+ * Refused with AMENV_ERR_INVALID, the handle untouched: arm vehicles, other rotor counts, fp64 handles, a handle whose step kernel is the
+ * lane-quad one, a max_rate or gain that is not finite and > 0, gain_k * task.dt >= 1 (past that bound the held torque overshoots the
+ * command within one step).  A configuration call without allocation or launch; it applies from the next launch. */
+typedef struct amenv_rate_control {
+  double max_rate[3];        /* rad/s per unit of action, body x, y, z */
+  double gain[3];            /* 1/s */
+  int32_t gyro_feedforward;  /* != 0: add w x (I w) */
+  int32_t reserved;
+} amenv_rate_control;
+/* r NULL = off: the handle launches exactly the kernels it launched before. */
+int amenv_set_rate_control(amenv* env, const amenv_rate_control* r);
+/* actions [N, 4] f32 commands, out [N, 4] f32 (device; may be the same buffer): [a_0, a'_x, a'_y, a'_z] from the handle's CURRENT body rates
+ * by the kernels' own device function.  It converts the rows it is given: the latency is ignored.  Only enqueues.  Refused while rate
+ * control is off. */
+int amenv_rate_moment_actions(amenv* env, const float* actions, float* out, void* stream);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

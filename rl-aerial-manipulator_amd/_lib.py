@@ -86,6 +86,10 @@ class ActionDelayC(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_steps", C.c_int32), ("max_steps", C.c_int32)]
 
 
+class RateControlC(C.Structure):
+    _fields_ = [("max_rate", C.c_double * 3), ("gain", C.c_double * 3), ("gyro_feedforward", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PpoCtl(C.Structure):
     """amenv_ppo_ctl: the device control block of a PPO update (include/amenv.h); this is the layout of the bytes read back from it."""
     _fields_ = [("struct_size", C.c_uint32), ("kl_limit", C.c_float), ("stop", C.c_uint32), ("stop_seen", C.c_uint32), ("evaluated", C.c_uint32),
@@ -126,6 +130,8 @@ SYMBOLS = {
     "amenv_set_action_delay_state": (C.c_int, [_P, _P, _P, _P]),
     "amenv_set_action_history": (C.c_int, [_P, C.c_int32]),
     "amenv_obs_dim": (C.c_int32, [_P]),
+    "amenv_set_rate_control": (C.c_int, [_P, C.POINTER(RateControlC)]),
+    "amenv_rate_moment_actions": (C.c_int, [_P, _P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

@@ -251,6 +251,9 @@ class PidWaypointPolicy:
 
     @classmethod
     def for_env(cls, env, speed=0.6, dtype=torch.float32):
+        if getattr(env, "rate_control", None) is not None:   # (clone_pid_policy comes through here too)
+            raise _lib.AmenvError("PidWaypointPolicy.for_env: the baseline outputs moments, and this env takes body-rate commands (rate_control is on); "
+                                  "a rate-output baseline is not built")
         v = env.cfg.vehicle
         arm = v.n_joints > 0
         return cls(env.num_envs, dt=env.cfg.task.dt, mass=v.mass, g=v.g, moment_scale=v.moment_scale,

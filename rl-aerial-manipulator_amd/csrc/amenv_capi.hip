@@ -76,6 +76,7 @@ struct amenv {
   void* delay_h = nullptr;         // float4 [n_tiles][8][64] given rows | int32 [n_tiles * 64] d | head << 4; allocated when the delay or the history is first enabled
   int hist = 0;                    // amenv_set_action_history: given action rows appended to every observation row, 0..2; > 0 runs the DELAY kernels
   float* hist_obs = nullptr;       // [N][obs_dim] the task's rows of amenv_reset / amenv_observe while the history is on, widened into the caller's buffer
+  RateBlock rate = {0, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};   // amenv_set_rate_control: body-rate actions; on = 0: off
   bool delay_path() const { return delay || hist > 0; }   // the DELAY instantiations run: the latency, the history (range (0, 0) without the latency) or both
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
@@ -348,7 +349,7 @@ DelayArg<true> make_delay(const amenv& e) {
 // noise's sigmas in the NOISE ones, behind those the actuation latency's fields in the DELAY ones
 template <typename T, int NROT, unsigned DYN> DynArg<T, NROT, DYN> make_dyn(const amenv& e) {
   DynArg<T, NROT, DYN> a;
-  if constexpr ((DYN & kDynDr) != 0) a.R.r = e.dr_r; else a.R.unused = 0;
+  if constexpr ((DYN & kDynDr) != 0) { a.R.r = e.dr_r; a.R.q = e.rate; } else a.R.unused = 0;
   if constexpr ((DYN & kDynLag) != 0) a.L = make_lag<T, NROT>(e);
   if constexpr ((DYN & kDynNoise) != 0) a.Z.s = e.noise_s;
   if constexpr ((DYN & kDynDelay) != 0) a.D = make_delay(e);
@@ -492,6 +493,7 @@ std::string kernel_name(const amenv& e) {
   if (e.noise) name += " +noise";
   if (e.delay) name += " +delay";
   if (e.hist) name += " +history " + std::to_string(e.hist);
+  if (e.rate.on) name += " +rate";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -594,12 +596,12 @@ hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_
 }
 
 // The switch set a handle runs, for amenv_step, amenv_rollout and the closed-loop rollouts alike: the lag, the noise and the DELAY path, and DR with any
-// of them (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
+// of them or with rate control, whose block travels with the ranges (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
 unsigned dyn_set(const amenv& e) {
   const int nr = e.cfg.vehicle.n_rotors;
   if (e.cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6)) return 0;
   const unsigned on = (e.lag ? kDynLag : 0) | (e.noise ? kDynNoise : 0) | (e.delay_path() ? kDynDelay : 0);
-  return on | (on || e.dr ? kDynDr : 0);
+  return on | (on || e.dr || e.rate.on ? kDynDr : 0);
 }
 template <auto V> using const_c = std::integral_constant<decltype(V), V>;
 // f(const_c<NROT>, const_c<DYN>) with DYN == dyn, over the sets that are built for T (dyn_admitted) and NROT (the general rotor count: no switch)
@@ -739,6 +741,20 @@ __global__ void dr_factors_kernel(int n, uint32_t tile_bytes, const void* __rest
   dr_draw<NROT>(C, R, C.gid0 + i, episode, f);
 #pragma unroll
   for (int k = 0; k < 2 + NROT; k++) out[size_t(i) * (2 + NROT) + k] = f[k];
+}
+
+// amenv_rate_moment_actions: [N][4] = the thrust entry, then the moment action the rate loop forms from the given commands and every env's current
+// body rates (rate_to_moment: the kernels' own arithmetic)
+template <int NROT>
+__global__ void rate_moment_kernel(int n, uint32_t tile_bytes, const void* __restrict__ blob, const HotParams<float, NROT> P, const RateBlock Q,
+                                   const float4* __restrict__ actions, float4* __restrict__ out) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const Vec4<float> w = *gptr<float>(const_cast<char*>(tile_base(blob, tile_bytes, i)), i & 63, 3);   // {wx, wy, wz, ep_return}
+  const float4 a = actions[i];
+  float act[4] = {a.x, a.y, a.z, a.w};
+  rate_to_moment(P, Q, w.a, w.b, w.c, act);
+  out[i] = make_float4(act[0], act[1], act[2], act[3]);
 }
 
 // amenv_sensor_noise_samples: [N][12] = the twelve unit samples of every env's current (episode, step) (noise_block: the kernels' own draw)
@@ -1363,6 +1379,46 @@ int amenv_set_action_history(amenv* e, int32_t rows) {
 
 int32_t amenv_obs_dim(const amenv* e) { return e ? e->obs_dim + 4 * e->hist : 0; }
 
+int amenv_set_rate_control(amenv* e, const amenv_rate_control* r) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!r) {   // off: the handle launches the kernels it launched before
+    e->rate = RateBlock{0, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};
+    return AMENV_OK;
+  }
+  if (int rc = rigid_switch_served(e, "amenv_set_rate_control", true)) return rc;
+  const char* ax[3] = {"x", "y", "z"};
+  for (int k = 0; k < 3; k++) {
+    if (!std::isfinite(r->max_rate[k]) || !(r->max_rate[k] > 0.0) || !std::isfinite(float(r->max_rate[k])))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_rate_control: max_rate ") + ax[k] + " must be finite and > 0 (rad/s)");
+    if (!std::isfinite(r->gain[k]) || !(r->gain[k] > 0.0) || !(float(r->gain[k]) > 0.0f))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_rate_control: gain ") + ax[k] + " must be finite and > 0 (1/s)");
+    if (!(r->gain[k] * e->cfg.task.dt < 1.0))
+      return fail(e, AMENV_ERR_INVALID, std::string("amenv_set_rate_control: gain ") + ax[k] + " * task.dt must be < 1 (past that the held torque overshoots the command within one step)");
+  }
+  RateBlock Q;
+  Q.on = r->gyro_feedforward ? 3 : 1;
+  for (int k = 0; k < 3; k++) { Q.max_rate[k] = float(r->max_rate[k]); Q.gain[k] = float(r->gain[k]); }
+  Q.inv_ms = float(1.0 / double(float(e->cfg.vehicle.moment_scale)));   // of the fp32 scale the step multiplies a' by (HotParams::mscale_f)
+  if (!std::isfinite(Q.inv_ms) || Q.inv_ms == 0.0f) return fail(e, AMENV_ERR_INVALID, "amenv_set_rate_control: the vehicle's moment_scale has no finite fp32 reciprocal");
+  e->rate = Q;
+  return AMENV_OK;
+}
+
+int amenv_rate_moment_actions(amenv* e, const float* actions, float* out, void* stream) {
+  if (!e || !actions || !out) return fail(e, AMENV_ERR_INVALID, "amenv_rate_moment_actions: NULL argument");
+  if (!e->rate.on) return fail(e, AMENV_ERR_INVALID, "amenv_rate_moment_actions: rate control is off (amenv_set_rate_control)");
+  if (!aligned16(actions) || !aligned16(out)) return fail(e, AMENV_ERR_INVALID, "amenv_rate_moment_actions: actions / out must be 16-byte aligned");
+  DeviceGuard g(e->device);
+  const int n = e->cfg.num_envs;
+  with_rotors46(e->cfg.vehicle.n_rotors, [&](auto nrot) {
+    constexpr int NROT = decltype(nrot)::value;
+    hipLaunchKernelGGL(rate_moment_kernel<NROT>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, e->tile_bytes, (const void*)e->blob, make_hot<float, NROT>(*e), e->rate,
+                       reinterpret_cast<const float4*>(actions), reinterpret_cast<float4*>(out));
+  });
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
 int amenv_get_action_delay_state(amenv* e, int32_t* d_out, float* recent_out, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   if (!d_out && !recent_out) return fail(e, AMENV_ERR_INVALID, "amenv_get_action_delay_state: NULL arguments");
@@ -1497,7 +1553,7 @@ int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, ui
                          float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay_path() && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
+  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay_path() && !e->rate.on && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
   if (!quad && !rigid && !arm_pol_ok(e->cfg))
     return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
                 "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");

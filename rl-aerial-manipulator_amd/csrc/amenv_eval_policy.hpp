@@ -201,6 +201,7 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
         given = make_float4(act[0], act[1], act[2], act[3]);
         if constexpr (kHist) { hr.g0 = given; delay_apply(DA.D, i, dl, act, hr); } else delay_apply(DA.D, i, dl, act);
       }
+      if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: behind the clipped action and the latency, in front of the step
       float reward; bool was_reset; int ep_len; float ep_ret;
       LagLds<NROT, NE, LAG> lg;
       if constexpr (LAG) { lg.col = wl + el; lg.a_up = DA.L.a_up; lg.a_down = DA.L.a_down; }

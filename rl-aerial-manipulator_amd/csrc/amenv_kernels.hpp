@@ -498,6 +498,7 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
     const float4 a = io.actions[min(i, hd.n - 1)];  // padding lanes re-read the last env's action: no exec branch in the prologue
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     if constexpr (DELAY) { given = a; hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
+    if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: the row the step consumes, behind the latency
   } else {
     const float* ap = reinterpret_cast<const float*>(io.actions) + size_t(min(i, hd.n - 1)) * AD;   // 28-B rows: dword loads
 #pragma unroll
@@ -698,6 +699,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     DelayLane dl;
     std::conditional_t<DELAY, HistRows, NoHist> hr;   // DELAY: the rows' action history: the observation wave's alone, used before the barrier
     if constexpr (DELAY) { hr.g0 = a; if (role == 2) delay_apply(DA.D, i, dl, act, hr); else delay_apply(DA.D, i, dl, act); }   // (wave-uniform)
+    if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: both integrating waves form the same row
     if (role == 2) {
 #ifdef AMENV_STAMPS
       AMENV_STAMP_DRAIN();
@@ -798,6 +800,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     DelayLane dl;
     std::conditional_t<DELAY, HistRows, NoHist> hr;
     if constexpr (DELAY) { hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
+    if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
     uint32_t bits = step_lane<T, NROT, KW, VAR, 0, ARM_ROLE_WORDS, LdsXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false,
                                                                                     was_reset, ep_len, ep_ret, x, df, &lg, noise_of(DA), &hr);
@@ -1050,6 +1053,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
       if constexpr (NJ == 0) {
         const float4 a = *reinterpret_cast<const float4*>(ap); act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
         if constexpr (DELAY) { given = a; hr.g0 = a; delay_apply(DA.D, i, dl, act, hr); }
+        if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: the rates are those the lane holds at the start of step t
       }
       else {
 #pragma unroll

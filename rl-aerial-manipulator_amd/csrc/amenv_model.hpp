@@ -168,7 +168,11 @@ __device__ __forceinline__ Deriv<T> rhs(const PT& P, T vx, T vy, T vz, T qw, T q
 // Ranges travel as a kernel argument of their own, in the DR instantiations only (HotParams is at its SGPR budget).  A factor is
 // lo + span * u, span = hi - lo, all in fp32 (the library is built with -ffp-contract=off: a multiply, then an add).
 struct DrRanges { float lo[3], span[3]; };   // [0] mass, [1] inertia, [2] thrust (one draw per rotor)
-template <bool ON> struct DrArg { DrRanges r; };
+// ---- body-rate actions (include/amenv.h amenv_set_rate_control) ------------------------------------------------------
+// The block travels behind the ranges, so every kernel built with kDynDr receives it: no switch bit and no instantiation of its own.
+// on: 0 off, 1 the rate loop, 3 the rate loop with the gyroscopic feed-forward (wave-uniform: it sits in a scalar register).
+struct RateBlock { int32_t on; float max_rate[3], gain[3], inv_ms; };   // rad/s, 1/s, float(1 / moment_scale) formed on the host in fp64
+template <bool ON> struct DrArg { DrRanges r; RateBlock q; };
 template <> struct DrArg<false> { int unused; };
 // Per-lane factors of the lane's current episode, drawn once per launch (and again after an auto-reset inside a rollout); empty when off.
 // F = sum s_r t_r and M = mixm (s . t); translational acceleration F / (km m); rotational J (M / kI - w x I w).
@@ -661,6 +665,40 @@ __device__ __forceinline__ DynFac<T, NROT, true> dr_factors(const HotParams<T, N
   d.inv_mass = P.inv_mass * rcp_(T(f[0]));
   d.inv_ki = rcp_(T(f[1]));
   return d;
+}
+
+// ---- body-rate actions: the inner rate loop ---------------------------------------------------------------------------
+// Entries 1..3 of the row the step is about to consume are body-rate commands; they become the equivalent moment action
+//   w_cmd = a * max_rate;  u = gain * (w_cmd - w);  tau = I u (+ w x (I w));  a' = tau * (1 / moment_scale)
+// with I the NOMINAL inertia (a flight controller does not know the episode's factor) and w the rates at the start of the step.  fp32, every
+// operation named and in a fixed order, so that every kernel that inlines this forms the same bits (tests/rate_ref.py mirrors the order;
+// the longest path has 8 roundings: w_cmd, the difference, u, the three of the I u row, the feed-forward's sum, the scaling).
+template <typename PT>
+__device__ __forceinline__ void rate_to_moment(const PT& P, const RateBlock& Q, float wx, float wy, float wz, float* act) {
+  const float Ixx = float(P.Ixx), Ixy = float(P.Ixy), Ixz = float(P.Ixz), Iyy = float(P.Iyy), Iyz = float(P.Iyz), Izz = float(P.Izz);
+  const float ux = __fmul_rn(Q.gain[0], __fadd_rn(__fmul_rn(act[1], Q.max_rate[0]), -wx));
+  const float uy = __fmul_rn(Q.gain[1], __fadd_rn(__fmul_rn(act[2], Q.max_rate[1]), -wy));
+  const float uz = __fmul_rn(Q.gain[2], __fadd_rn(__fmul_rn(act[3], Q.max_rate[2]), -wz));
+  float tx = fmaf(Ixx, ux, fmaf(Ixy, uy, __fmul_rn(Ixz, uz)));
+  float ty = fmaf(Ixy, ux, fmaf(Iyy, uy, __fmul_rn(Iyz, uz)));
+  float tz = fmaf(Ixz, ux, fmaf(Iyz, uy, __fmul_rn(Izz, uz)));
+  if (Q.on & 2) {   // + w x (I w): the term the rigid body's own right-hand side subtracts
+    const float i0 = fmaf(Ixx, wx, fmaf(Ixy, wy, __fmul_rn(Ixz, wz)));
+    const float i1 = fmaf(Ixy, wx, fmaf(Iyy, wy, __fmul_rn(Iyz, wz)));
+    const float i2 = fmaf(Ixz, wx, fmaf(Iyz, wy, __fmul_rn(Izz, wz)));
+    tx = __fadd_rn(tx, fmaf(wy, i2, -__fmul_rn(wz, i1)));
+    ty = __fadd_rn(ty, fmaf(wz, i0, -__fmul_rn(wx, i2)));
+    tz = __fadd_rn(tz, fmaf(wx, i1, -__fmul_rn(wy, i0)));
+  }
+  act[1] = __fmul_rn(tx, Q.inv_ms); act[2] = __fmul_rn(ty, Q.inv_ms); act[3] = __fmul_rn(tz, Q.inv_ms);
+}
+// The call of the kernels built with kDynDr: behind the action load and delay_apply, in front of the step.  A wave-uniform branch on the flag;
+// the fp64 builds (logic gates of the dynamics, which no rate-mode handle runs) hold no rate code.
+template <typename T, int KW, typename PT>
+__device__ __forceinline__ void rate_apply(const PT& P, const RateBlock& Q, const Env<T, KW>& e, float* act) {
+  if constexpr (sizeof(T) == 4) {
+    if (Q.on != 0) rate_to_moment(P, Q, e.wx, e.wy, e.wz, act);
+  }
 }
 
 // ---- sensor noise -----------------------------------------------------------------------------------------------

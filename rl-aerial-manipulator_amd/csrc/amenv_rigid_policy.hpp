@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
       given = make_float4(act[0], act[1], act[2], act[3]);
       if constexpr (kHist) { hr.g0 = given; delay_apply(DA.D, i, dl, act, hr); } else delay_apply(DA.D, i, dl, act);
     }
+    if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: behind the clipped action and the latency, in front of the step
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
     sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * W : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;

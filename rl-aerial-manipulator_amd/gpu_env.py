@@ -13,13 +13,14 @@ from . import _lib as L
 from .action_delay import ActionDelay
 from .action_history import ActionHistory
 from .randomization import DynamicsRandomization
+from .rate_control import RateControl
 from .rotor_lag import RotorLag
 from .sensor_noise import SensorNoise
 
 # The opt-in switches, in the order the constructor applies them: keyword = attribute = the <name> of set_<name> and amenv_set_<name> ->
 # (class, the method that gives its C struct; the history's argument is its row count)
 _SWITCHES = {"randomization": (DynamicsRandomization, "to_c"), "rotor_lag": (RotorLag, "to_c"), "sensor_noise": (SensorNoise, "to_c"),
-             "action_delay": (ActionDelay, "_as_c"), "action_history": (ActionHistory, None)}
+             "action_delay": (ActionDelay, "_as_c"), "action_history": (ActionHistory, None), "rate_control": (RateControl, "to_c")}
 
 
 def _typed(who, x, cls):
@@ -48,9 +49,9 @@ class GpuWaypointEnv:
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
                  rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
-                 sensor_noise=None, action_delay=None, action_history=None):
+                 sensor_noise=None, action_delay=None, action_history=None, rate_control=None):
         switches = {"randomization": randomization, "rotor_lag": rotor_lag, "sensor_noise": sensor_noise, "action_delay": action_delay,
-                    "action_history": action_history}
+                    "action_history": action_history, "rate_control": rate_control}
         for name, x in switches.items():   # before any device is touched
             _typed(name, x, _SWITCHES[name][0])
         self.lib = L.load()
@@ -204,6 +205,26 @@ class GpuWaypointEnv:
         self.obs = torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
         self.terminal_obs = torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float32, device=self.device)
         self.kernel_name = self.lib.amenv_kernel_name(self._h).decode()
+
+    def set_rate_control(self, rate):
+        """Body-rate actions (a `RateControl`, or None = entries 1..3 of an action row are moments; fp32 rigid vehicles with 4 or 6 rotors,
+        not with kernel="team").  While it is on, entries 1..3 are rate commands in units of `max_rate` and a proportional rate loop on the
+        nominal inertia, inside the step and behind the latency, forms the moments.  The rows of the action history and of PPO's buffers stay
+        the commands as given.  No state, no allocation: it applies from the next launch."""
+        _typed("set_rate_control", rate, RateControl)
+        if rate is not None:
+            rate.validate(self.cfg.task.dt)
+        self._set_switch("rate_control", rate)
+
+    def moment_actions(self, actions):
+        """[N, 4] f32: the rows [a_0, a'_x, a'_y, a'_z] the rate loop forms from the command rows `actions` and every env's CURRENT body
+        rates, by the kernels' own device function (the latency is ignored: it converts the rows it is given).  Stepping a twin env without
+        rate control with them reproduces this env's next step.  Needs rate control on."""
+        a = self._actions(actions)
+        out = torch.empty(self.num_envs, 4, dtype=torch.float32, device=self.device)
+        self._check(self.lib.amenv_rate_moment_actions(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
+                    "amenv_rate_moment_actions")
+        return out
 
     def action_delay_state(self):
         """(d [N] int32, recent [N, 8, 4] f32): every env's delay and the last 8 action rows it was given, in age order (recent[:, k] was

@@ -4,6 +4,7 @@ possible across .so files, so each variant runs in its own child process, rounds
 
   python tools/ab_kernel.py --libs a.so b.so --envs 4096 32768 1048576 --rounds 3
 Child mode (--child) prints one JSON line: kernel_us (dispatch-stamped), loop_us (hipGraph replay) per env count.
+--randomize: the +dr switch set (mass / inertia +-20 %, thrust +-5 %; rigid vehicles); --rate-control: body-rate actions on top of it.
 """
 import argparse
 import json
@@ -21,7 +22,12 @@ def child(args):
     import rl_aerial_manipulator_amd as amd
     out = {}
     for n in args.envs:
-        env = amd.GpuWaypointEnv(n, vehicle=args.vehicle, seed=0, block_size=args.block_size)
+        kw = {}
+        if args.randomize:
+            kw["randomization"] = amd.DynamicsRandomization.around_one(mass=0.2, inertia=0.2, thrust=0.05)
+        if args.rate_control:
+            kw["rate_control"] = amd.RateControl()
+        env = amd.GpuWaypointEnv(n, vehicle=args.vehicle, seed=0, block_size=args.block_size, **kw)
         env.reset()
         g = torch.Generator(device="cuda").manual_seed(1)
         ring = torch.randn(64, n, env.act_dim, device="cuda", generator=g) * (0.1 if args.ring == "random" else 0.0)
@@ -61,6 +67,8 @@ def main():
     ap.add_argument("--block-size", type=int, default=0)
     ap.add_argument("--block-sizes", nargs="+", type=int, default=None)
     ap.add_argument("--ring", default="random", choices=["random", "hover"])
+    ap.add_argument("--randomize", action="store_true")
+    ap.add_argument("--rate-control", action="store_true")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
@@ -73,7 +81,7 @@ def main():
     for r in range(args.rounds):
         for lib, bs in variants:
             env = dict(os.environ, AMENV_LIB=os.path.abspath(lib))
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--vehicle", args.vehicle, "--block-size", str(bs), "--ring", args.ring, "--envs"] + [str(n) for n in args.envs]
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--vehicle", args.vehicle, "--block-size", str(bs), "--ring", args.ring] + ["--randomize"] * args.randomize + ["--rate-control"] * args.rate_control + ["--envs"] + [str(n) for n in args.envs]
             o = subprocess.run(cmd, env=env, capture_output=True, text=True)
             line = [l for l in o.stdout.splitlines() if l.startswith("{")]
             if not line:
