@@ -6,13 +6,18 @@ by formulation-independent invariants:
   - arm locked  => identical to the rigid-body oracle run on the composite mass / CoM / inertia;
   - link masses -> 0 => identical to the rigid hexacopter;
   - hover thrust balances the total weight; the gravity moment of the offset arm CoM is what tilts it.
+The default arm multiplies many of the model's terms by zero (link 1's CoM, entries of the joint origins, the products of inertia of links 1
+and 2), so the first three invariants and the forward kinematics also run on the fully general arm of tests/generic_vehicles.py, and on
+both with joint axes (y, z, x) and three skew axes beside the SDF's (z, x, x).
 """
 import ctypes as C
 
 import numpy as np
+import pytest
 
 import rl_aerial_manipulator_amd as amd
 from oracle import oracle as O
+from tests import generic_vehicles as GV
 
 
 def arm_cfg(**over):
@@ -20,6 +25,23 @@ def arm_cfg(**over):
     cfg = O.reference_quad_config(1, flags=0)
     C.memmove(C.byref(cfg.vehicle), C.byref(pc.vehicle), C.sizeof(O.Vehicle))
     cfg.task.ee_task = pc.task.ee_task               # the arm's default: the waypoint task measures from the tool point
+    for k, v in over.items():
+        setattr(cfg.vehicle, k, v)
+    return cfg
+
+
+# the invariants below on the default arm and on the fully general one of tests/generic_vehicles.py (its task constants with it), each with the
+# (z, x, x) axes of the SDF, with (y, z, x) and with three skew axes: (vehicle, axes)
+ARMS = [(v, a) for v in ("default", "generic") for a in ("zxx", "yzx", "skew")]
+
+
+def arm_case(vehicle, axes, **over):
+    cfg = arm_cfg()
+    if vehicle == "generic":
+        GV.generic_task(GV.generic_arm(cfg, axes=axes))
+    else:
+        for j, x in enumerate(GV.AXES[axes]):
+            cfg.vehicle.joint_axis[j] = x
     for k, v in over.items():
         setattr(cfg.vehicle, k, v)
     return cfg
@@ -63,28 +85,43 @@ def momenta(cfg, s):
     return P, Lw, xc / mt
 
 
-def test_momentum_conservation_with_moving_joints():
-    cfg = arm_cfg(g=0.0)
+def _momentum_drift(cfg, steps):
+    """Worst relative drift of P and L over `steps` steps without an external wrench, the joints slewing; and how far the arm moved."""
     rng = np.random.RandomState(0)
     q = rng.normal(size=4); q /= np.linalg.norm(q)
     s = np.concatenate([[0.3, -0.2, 1.5], [0.4, -0.1, 0.2], q, [0.5, -0.8, 0.3], [0.2, -0.4, 0.6], [0.0, 0.0, 0.0]])
     P0, L0, _ = momenta(cfg, s)
-    a = np.array([0, 0, 0, 0, 0.9, -0.7, 0.8], np.float32)           # zero rotor wrench (t_min = 0 below), joints slewing
-    cfg.vehicle.t_min[:] = (C.c_double * 8)(*([0.0] * 8))
+    a = np.array([0, 0, 0, 0, 0.9, -0.7, 0.8], np.float32)           # zero rotor wrench (t_min = 0), joints slewing
     worst = 0.0; peak_rate = 0.0
-    for t in range(400):
+    for t in range(steps):
         s, w = O.arm_dynamics_step(cfg, s, a)
         peak_rate = max(peak_rate, np.abs(s[16:19]).max())
         assert w[0] == 0 and not w[1:4].any()
         P, L, _ = momenta(cfg, s)
         worst = max(worst, np.abs(P - P0).max() / np.abs(P0).max(), np.abs(L - L0).max() / np.abs(L0).max())
-    assert peak_rate > 1.0 and np.abs(s[13:16] - [0.2, -0.4, 0.6]).max() > 0.5                 # the arm really moved
-    assert worst < 5e-9, worst                                                                 # RK4(5 ms) integration error only
+    return worst, peak_rate, np.abs(s[13:16] - [0.2, -0.4, 0.6]).max()
 
 
-def test_momentum_rate_equals_external_wrench():
+@pytest.mark.parametrize("vehicle,axes", ARMS)
+def test_momentum_conservation_with_moving_joints(vehicle, axes):
+    """Gated by ORDER: the drift over the same simulated time at dt and at dt / 2 falls by 16 (classical RK4; 12..20 accepted), whatever
+    the parameters; the default vehicle keeps its absolute bound as well."""
+    cfg = arm_case(vehicle, axes, g=0.0)
+    cfg.vehicle.t_min[:] = (C.c_double * 8)(*([0.0] * 8))
+    worst, peak_rate, moved = _momentum_drift(cfg, 400)
+    assert peak_rate > 1.0 and moved > 0.5                                                     # the arm really moved
+    cfg.task.dt = cfg.task.dt / 2
+    half, _, _ = _momentum_drift(cfg, 800)
+    print(f"{vehicle} {axes}: drift {worst:.2e}, at dt/2 {half:.2e}, ratio {worst / half:.2f}")
+    assert 12.0 < worst / half < 20.0, (worst, half)
+    if (vehicle, axes) == ("default", "zxx"):
+        assert worst < 5e-9, worst                                                             # RK4(5 ms) integration error only
+
+
+@pytest.mark.parametrize("vehicle,axes", ARMS)
+def test_momentum_rate_equals_external_wrench(vehicle, axes):
     """dP/dt = F_world + m g,  dL/dt = x_O x F_world + R M + sum x_k x m_k g  (finite differences of the same momenta)."""
-    cfg = arm_cfg()
+    cfg = arm_case(vehicle, axes)
     rng = np.random.RandomState(1)
     for trial in range(5):
         q = rng.normal(size=4); q /= np.linalg.norm(q)
@@ -124,8 +161,9 @@ def test_massless_arm_is_the_rigid_hexacopter():
         assert np.abs(sa[:13] - sr).max() < 1e-10
 
 
-def test_locked_arm_equals_composite_rigid_body():
-    cfg = arm_cfg(joint_kp=0.0, joint_kd=0.0)            # thdd = 0, joints stay where they are
+@pytest.mark.parametrize("vehicle,axes", ARMS)
+def test_locked_arm_equals_composite_rigid_body(vehicle, axes):
+    cfg = arm_case(vehicle, axes, joint_kp=0.0, joint_kd=0.0)            # thdd = 0, joints stay where they are
     th = np.array([0.4, -0.7, 0.9])
     s0 = np.concatenate([[0, 0, 2.0], [0, 0, 0], [1, 0, 0, 0], [0, 0, 0], th, [0, 0, 0]])
     _, _, xc0 = momenta(cfg, s0)
@@ -141,6 +179,7 @@ def test_locked_arm_equals_composite_rigid_body():
     rigid = O.reference_quad_config(1, flags=0)
     C.memmove(C.byref(rigid.vehicle), C.byref(cfg.vehicle), C.sizeof(O.Vehicle))
     rigid.vehicle.n_joints = 0
+    rigid.task.dt = cfg.task.dt
     for j in range(9):
         rigid.vehicle.inertia[j] = Ic.reshape(-1)[j]; rigid.vehicle.inv_inertia[j] = np.linalg.inv(Ic).reshape(-1)[j]
     rng = np.random.RandomState(3)
@@ -212,11 +251,15 @@ def fk_numpy(cfg, s):
     return s[0:3] + rot_q(s[6:10]).T @ p
 
 
-def test_forward_kinematics_matches_independent_chain_and_home_invariant():
-    cfg = arm_cfg()
+@pytest.mark.parametrize("vehicle,axes", ARMS)
+def test_forward_kinematics_matches_independent_chain_and_home_invariant(vehicle, axes):
+    cfg = arm_case(vehicle, axes)
     rng = np.random.RandomState(0)
     home = np.array(cfg.vehicle.joint_origin[:9]).reshape(3, 3).sum(0) + np.array(cfg.vehicle.tool_offset[:3])
-    assert abs(home[2] + 0.103522586 + 0.106 + 0.125) < 1e-9 and np.linalg.norm(home) < 0.4     # the tool hangs ~0.33 m below the body origin
+    if vehicle == "default":
+        assert abs(home[2] + 0.103522586 + 0.106 + 0.125) < 1e-9 and np.linalg.norm(home) < 0.4     # the tool hangs ~0.33 m below the body origin
+    else:
+        assert (np.abs(home) > 1e-3).all()
     for _ in range(200):
         s = np.zeros(19)
         s[0:3] = rng.normal(0, 2, 3); q = rng.normal(size=4); s[6:10] = q / np.linalg.norm(q)
@@ -225,13 +268,15 @@ def test_forward_kinematics_matches_independent_chain_and_home_invariant():
         # arm locked at home: the tool point is the base position plus a constant offset rotated by q (VERDICT invariant)
         s[13:16] = 0
         np.testing.assert_allclose(O.ee_position(cfg, s), s[0:3] + rot_q(s[6:10]).T @ home, rtol=0, atol=1e-13)
-    # joint 1 turns about body z through the joint origin: the tool stays on a circle around that axis at constant height
+    # joint 1 turns about its axis through the joint origin: the tool stays on a circle around that axis at constant height along it
     s = np.zeros(19); s[6] = 1; s[14:16] = (0.7, -0.4)
     pts = []
     for th1 in np.linspace(-3, 3, 13):
         s[13] = th1; pts.append(O.ee_position(cfg, s) - np.array(cfg.vehicle.joint_origin[:3]))
     pts = np.array(pts)
-    assert np.ptp(pts[:, 2]) < 1e-13 and np.ptp(np.hypot(pts[:, 0], pts[:, 1])) < 1e-13
+    ax = np.array(cfg.vehicle.joint_axis[:3]); ax /= np.linalg.norm(ax)
+    along = pts @ ax
+    assert np.ptp(along) < 1e-13 and np.ptp(np.linalg.norm(pts - np.outer(along, ax), axis=1)) < 1e-13
 
 
 def test_tool_point_task_measures_from_the_end_effector():

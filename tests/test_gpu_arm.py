@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import generic_vehicles as GV
 from tests.test_arm_cpu import arm_cfg, momenta
 from tests.test_gpu_parity import gpu_state, rel_err, REL32, OBS_ULP
 
@@ -510,9 +511,11 @@ def test_closed_loop_policy_rollout_forms_draw_the_same_actions():
     assert float((o1[1] - o2[1]).abs().max()) < 1e-4
 
 
+@pytest.mark.parametrize("vehicle", ["default", "generic"])
 @pytest.mark.parametrize("form", [0, 1])
-def test_arm_right_hand_side_device_code_vs_oracle(form):
-    """amenv_arm_rhs: the device code of both formulations of the arm vehicle's right-hand side -- form 0 = per-link Newton-Euler sums
+def test_arm_right_hand_side_device_code_vs_oracle(form, vehicle):
+    """vehicle: the default arm, or the fully general z,x,x one of tests/generic_vehicles.py (every origin, CoM and product of inertia non-zero).
+    amenv_arm_rhs: the device code of both formulations of the arm vehicle's right-hand side -- form 0 = per-link Newton-Euler sums
     (lane / two-wave kernels), form 1 = joint-configuration aggregates + base dynamics on them (stage-wave / lane-team kernels) -- on
     random states, wrenches and commands: the fp64 instantiation against the fp64 oracle (logic gate, <= 1e-12), the fp32 instantiation
     to fp32 rounding.  A third of the commands saturate the joint servos."""
@@ -528,6 +531,8 @@ def test_arm_right_hand_side_device_code_vs_oracle(form):
     cmd = s[:, 13:16] + rng.normal(size=(n, 3)) * np.where(rng.rand(n, 1) < 0.33, 2.0, 0.05)
     cfg = amd._lib.default_config("hexa_arm", 1)
     ocfg = arm_cfg()
+    if vehicle == "generic":
+        GV.generic_arm(cfg); GV.generic_arm(ocfg)
     ref = np.stack([O.arm_rhs(ocfg, s[i], w[i, 0], w[i, 1:], cmd[i]) for i in range(n)])
     scale = np.maximum(1.0, np.abs(ref))
     for dtype, code, tol in ((torch.float64, amd._lib.F64, 1e-12), (torch.float32, amd._lib.F32, 3e-5)):
@@ -536,6 +541,7 @@ def test_arm_right_hand_side_device_code_vs_oracle(form):
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         assert amd._lib.load().amenv_arm_rhs(C.byref(cfg), form, code, p(ts), p(tw), p(tc), p(d), n, None) == 0
         err = (np.abs(d.cpu().numpy().astype(np.float64) - ref) / scale).max()
+        print(f"amenv_arm_rhs form {form} {vehicle} {dtype}: {err:.3e} (tol {tol:g})")
         assert err < tol, (form, dtype, err)
     # a rigid vehicle has no such right-hand side
     assert amd._lib.load().amenv_arm_rhs(C.byref(amd._lib.default_config("hexa", 1)), form, amd._lib.F64, p(ts), p(tw), p(tc), p(d), n, None) == -1

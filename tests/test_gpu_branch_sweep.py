@@ -20,11 +20,13 @@ Worst errors measured on the TASK_SWEEP cases (MI355X, 12 cases x 6 steps x 300 
   fp64: state 4.3e-14 / 1.1e-13, reward 7.2e-15 / 1.3e-14, observation rows 6.6e-17 / 1.3e-17, ep_return 0 / 0, terminal rows 0 / 0
 
 tests/test_state_blob_cpu.py checks on the oracle alone that these states reach every branch and that the envs a flip could be excused on
-number no more than the cap."""
+number no more than the cap.  tests/test_gpu_generic_vehicles.py runs `_sweep`, the rollout and the closed-loop replay of this file on
+the fully general vehicles of tests/generic_vehicles.py (`make_env` builds their configs: `generic_config`)."""
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import generic_vehicles as GV
 from tests import golden_util as G
 from tests import state_blob as B
 from tests.test_state_blob_cpu import ACTION_SEED, ENV_SEED, RESEAT_SEED, ROLLOUT_STEPS, STEPS, start_state
@@ -32,15 +34,44 @@ from tests.test_state_blob_cpu import ACTION_SEED, ENV_SEED, RESEAT_SEED, ROLLOU
 pytestmark = pytest.mark.gpu
 
 ENV_KW = {"hexa_arm": dict(vehicle="hexa_arm"), "hexa_arm_2j": dict(vehicle="hexa_arm", n_joints=2), "hexa_arm_base": dict(vehicle="hexa_arm", ee_task="base"),
-          "hexa": dict(vehicle="hexa"), "quad": dict(vehicle="quad")}
+          "hexa": dict(vehicle="hexa"), "quad": dict(vehicle="quad"),
+          # the fully general vehicles of tests/generic_vehicles.py: the default vehicle each of them overwrites
+          "gen_quad": dict(vehicle="quad"), "gen_hexa": dict(vehicle="hexa"), "gen_arm": dict(vehicle="hexa_arm"), "gen_arm_2j": dict(vehicle="hexa_arm", n_joints=2),
+          "gen_arm_base": dict(vehicle="hexa_arm", ee_task="base"), "gen_arm_yzx": dict(vehicle="hexa_arm"), "gen_arm_skew": dict(vehicle="hexa_arm")}
 
 
 TASK_KW = {"v2": dict(), "v2k2": dict(num_waypoints=2), "v2k3": dict(num_waypoints=3), "v2k4": dict(num_waypoints=4), "v1_raw": dict(task="v1_raw"),
            "v1_scaled": dict(task="v1_scaled")}
 
 
-def make_env(vehicle, n, dtype="f32", kernel="auto", task="v2", **kw):
+def generic_config(vehicle, n, dtype="f32", kernel="auto", task="v2", seed=ENV_SEED, block_size=0):
+    """The config of a "gen_..." vehicle.  GpuWaypointEnv(config=...) ignores its other keyword arguments, so this builds the config the way
+    the constructor does -- default_config, seed, dtype, flags, step_kernel, block_size, the waypoint count with its trig table -- and then
+    overwrites vehicle and task constants with the generic ones."""
+    import math
     import rl_aerial_manipulator_amd as amd
+    L = amd._lib
+    kw = dict(ENV_KW[vehicle], **TASK_KW[task])
+    cfg = L.default_config(kw["vehicle"], n, kw.get("task", "v2"), n_joints=kw.get("n_joints"))
+    cfg.seed, cfg.dtype, cfg.flags = seed, L.F64 if dtype == "f64" else L.F32, L.FLAG_AUTO_RESET
+    cfg.block_size, cfg.step_kernel = block_size, L.KERNELS[kernel]
+    K = kw.get("num_waypoints", 1)
+    if K != 1:
+        cfg.task.num_waypoints = K
+        for k in range(1, K + 1):
+            t = k / K
+            cfg.task.traj_sin[k - 1] = math.sin(2.0 * t * math.pi)
+            cfg.task.traj_cos[k - 1] = math.cos(t * 2.0 * math.pi)
+    return GV.build(cfg, vehicle)
+
+
+def make_env(vehicle, n, dtype="f32", kernel="auto", task="v2", **kw):
+    """kw: the constructor's other keywords; on a "gen_..." vehicle seed and block_size go into the config, the opt-in switches to the constructor."""
+    import rl_aerial_manipulator_amd as amd
+    if vehicle in GV.VEHICLES:
+        cfg = generic_config(vehicle, n, dtype, kernel, task, **{k: kw.pop(k) for k in ("seed", "block_size") if k in kw})
+        assert set(kw) <= {"randomization", "rotor_lag", "rate_control"}, kw
+        return amd.GpuWaypointEnv(n, config=cfg, **kw)
     return amd.GpuWaypointEnv(n, seed=ENV_SEED, dtype=dtype, kernel=kernel, **ENV_KW[vehicle], **TASK_KW[task], **kw)
 
 

@@ -104,6 +104,13 @@ def test_kernels_match_the_oracle_with_per_env_vehicles(vehicle, task, nwp, dtyp
     n, T = 64, 30
     wide = amd.DynamicsRandomization(mass=(0.6, 1.6), inertia=(0.5, 2.0), thrust=(0.8, 1.2))
     env = _env(vehicle, task, nwp, n, seed=8, dtype=dtype, kernel=kernel, max_episode_steps=12, randomization=wide)
+    check_against_per_env_oracle(env, dtype, T)
+    env.close()
+
+
+def check_against_per_env_oracle(env, dtype, T):
+    """The gate of the test above on a handle with randomisation on (tests/test_gpu_generic_vehicles.py runs it on its vehicles)."""
+    n = env.num_envs
     env.reset()
     base = H.oracle_cfg(env)
     acts = _actions(T, n, 6, env.device, wide=True)
@@ -130,9 +137,10 @@ def test_kernels_match_the_oracle_with_per_env_vehicles(vehicle, task, nwp, dtyp
                 assert out["done"][0] == 0 and np.array_equal(orc.istate[:, 0], i_new[:, i]), (t, i)
             err = np.abs(orc.fstate[:13, 0] - f_new[:13, i]) / np.maximum(1.0, np.abs(orc.fstate[:13, 0]))
             worst = max(worst, float(err.max()))
+    print(f"randomisation gate {env.kernel_name}: state {worst:.3e} (tol {tol:g}), {ended} episode ends")
     assert worst <= tol, worst
     assert ended > 0
-    env.close()
+    return worst
 
 
 # ---- 4. one-launch rollout = T steps -------------------------------------------------------------------------------------------

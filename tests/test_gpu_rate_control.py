@@ -42,6 +42,13 @@ def test_moment_actions_are_the_restated_law(vehicle, rate):
     u, the product and two fmas of the I u row, the sum with the feed-forward, the scaling by 1 / ms), S_k the sum of the absolute values
     of every term that enters a'_k.  Rates of +-8 rad/s lie beyond max_rate as well.  The thrust column comes back bit-equal."""
     env = _rate_env(vehicle, "v2", 1, rate=rate)
+    check_the_law(env, rate, vehicle)
+    env.close()
+
+
+def check_the_law(env, rate, label):
+    """The gate of the test above on a handle in rate mode (tests/test_gpu_generic_vehicles.py runs it on its vehicles)."""
+    N = env.num_envs
     env.reset()
     g = torch.Generator().manual_seed(5)
     f, i = env.get_state()
@@ -56,10 +63,10 @@ def test_moment_actions_are_the_restated_law(vehicle, rate):
     assert np.array_equal(got[:, 0].view(np.uint32), rows.numpy()[:, 0].view(np.uint32))
     err = np.abs(got[:, 1:].astype(np.float64) - want[:, 1:])
     bound = rate_ref.N_ROUNDINGS * 2.0 ** -24 * S
-    print(f"law {vehicle} ff={rate.gyro_feedforward}: worst |delta a'| / (2^-24 S) = {(err / (2.0 ** -24 * S)).max():.2f} (bound {rate_ref.N_ROUNDINGS})")
+    print(f"law {label} ff={rate.gyro_feedforward}: worst |delta a'| / (2^-24 S) = {(err / (2.0 ** -24 * S)).max():.2f} (bound {rate_ref.N_ROUNDINGS})")
     assert np.all(err <= bound), (err / bound).max()
     assert np.all(S > 0.0) and not np.array_equal(got[:, 1:], rows.numpy()[:, 1:])
-    env.close()
+    return float((err / (2.0 ** -24 * S)).max())
 
 
 # ---- 2. the plumbing, bit for bit ---------------------------------------------------------------------------------------------------
@@ -238,9 +245,16 @@ def test_rate_mode_matches_the_oracle_fed_the_moment_rows(vehicle, task, nwp, ke
     """Teacher-forced per step: the unchanged fp64 oracle starts from the GPU's state and is fed moment_actions(command); its state after the
     step is the GPU's to the fp32 tolerance of tests/test_gpu_rotor_lag.py::test_lagged_kernels_match_the_pinned_oracle, 1e-5 relative
     to max(1, |x|).  The one-launch rollout of a twin publishes the same observation rows to the same tolerance."""
-    tol = 1e-5
     env = _rate_env(vehicle, task, nwp, seed=8, kernel=kernel)
     twin = _rate_env(vehicle, task, nwp, seed=8, kernel=kernel)
+    check_against_the_oracle_fed_the_moment_rows(env, twin, f"{vehicle} {task} {nwp} {kernel}")
+    env.close(); twin.close()
+
+
+def check_against_the_oracle_fed_the_moment_rows(env, twin, label, T=T):
+    """The gate of the test above on two handles in rate mode with the same seed (tests/test_gpu_generic_vehicles.py runs it on its vehicles)."""
+    tol = 1e-5
+    N = env.num_envs
     env.reset(); twin.reset()
     cmds = _actions(T, N, 6, env.device, wide=True)
     ro = twin.rollout(cmds)["obs"].cpu().numpy().astype(np.float64)
@@ -262,11 +276,11 @@ def test_rate_mode_matches_the_oracle_fed_the_moment_rows(vehicle, task, nwp, ke
         worst = max(worst, float(err.max()))
         oo = out["obs"][on].astype(np.float64)
         worst_o = max(worst_o, float((np.abs(ro[t][on] - oo) / np.maximum(1.0, np.abs(oo))).max()))
-    print(f"rate gate {vehicle} {task} {nwp} {kernel}: state {worst:.3e} rollout rows {worst_o:.3e} (tol {tol:g}), {ended} episode ends")
+    print(f"rate gate {label}: state {worst:.3e} rollout rows {worst_o:.3e} (tol {tol:g}), {ended} episode ends")
     assert worst <= tol, worst
     assert worst_o <= tol, worst_o
     assert ended > 0 and compared > T * N // 2
-    env.close(); twin.close()
+    return worst, worst_o
 
 
 # ---- 6. the one-launch evaluation -----------------------------------------------------------------------------------------------------

@@ -118,6 +118,13 @@ def test_lagged_kernels_match_the_pinned_oracle(vehicle, task, nwp, dtype, kerne
     relative to max(1, |x|) (DESIGN.md sections 2, 4i); the rotor state is compared as delivered thrust w'^2 with the same tolerances."""
     n, T = 64, 30
     env = _env(vehicle, task, nwp, n, seed=8, dtype=dtype, kernel=kernel, max_episode_steps=12, rotor_lag=lag, randomization=dr)
+    check_against_the_pinned_oracle(env, dtype, lag, dr, T, f"{vehicle} {task} {nwp} {dtype} {kernel}")
+    env.close()
+
+
+def check_against_the_pinned_oracle(env, dtype, lag, dr, T, label):
+    """The gate of the test above on a handle with the lag on (tests/test_gpu_generic_vehicles.py runs it on its vehicles)."""
+    n = env.num_envs
     assert env.kernel_name.endswith(" +dr +lag" if dr else " +lag")
     env.reset()
     base = _ocfg(env)
@@ -157,11 +164,11 @@ def test_lagged_kernels_match_the_pinned_oracle(vehicle, task, nwp, dtype, kerne
             worst = max(worst, float(err.max()))
             err_t = np.abs(w_new[i].astype(np.float64) ** 2 - t_eff) / np.maximum(1.0, t_eff)
             worst_t = max(worst_t, float(err_t.max()))
-    print(f"lag gate {vehicle} {task} {nwp} {dtype} {kernel}: state {worst:.3e} thrust {worst_t:.3e} (tol {tol:g}), {ended} episode ends")
+    print(f"lag gate {label}: state {worst:.3e} thrust {worst_t:.3e} (tol {tol:g}), {ended} episode ends")
     assert worst <= tol, worst
     assert worst_t <= tol, worst_t
     assert ended > 0 and fell > 0 and rose > 0
-    env.close()
+    return worst, worst_t
 
 
 # ---- 4. one launch = T steps ----------------------------------------------------------------------------------------------------

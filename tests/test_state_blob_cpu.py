@@ -7,7 +7,9 @@
      3e-5) number at most the cap, so a disagreement beyond them cannot hide behind it.
   3. `compare` accepts the oracle against itself and rejects a copy changed in any one field it guards.
   4. The same for the states of the other two task forms (TASK_STATES: v1, and v2 with 2..4 waypoints), with the classes of those tasks; and
-     the one-waypoint states are still, by checksum, the ones the sweep started from before the blob learnt the other tasks."""
+     the one-waypoint states are still, by checksum, the ones the sweep started from before the blob learnt the other tasks.
+  5. Conditions 1 and 2 on the fully general vehicles and task constants of tests/generic_vehicles.py (GENERIC_STATES, GENERIC_TASK_STATES:
+     what tests/test_gpu_generic_vehicles.py starts from); if a parameter set misses one, the parameters change, not the cap."""
 import copy
 import ctypes as C
 import functools
@@ -18,6 +20,7 @@ import pytest
 
 import rl_aerial_manipulator_amd as amd
 from oracle import oracle as O
+from tests import generic_vehicles as GV
 from tests import state_blob as B
 from tests.test_arm_cpu import arm_cfg
 
@@ -26,6 +29,11 @@ STEPS, ROLLOUT_STEPS = 6, 4
 # (vehicle, n, dtype) of every state the sweep starts from
 STATES = [("hexa_arm", 300, "f32"), ("hexa_arm", 300, "f64"), ("hexa_arm", 4100, "f32"), ("hexa_arm_2j", 300, "f32"), ("hexa_arm_base", 300, "f32"),
           ("hexa", 300, "f32"), ("hexa", 300, "f64"), ("quad", 300, "f32")]
+# the fully general vehicles of tests/generic_vehicles.py on its task constants (tests/test_gpu_generic_vehicles.py starts from these)
+GENERIC_STATES = [("gen_arm", 300, "f32"), ("gen_arm", 300, "f64"), ("gen_arm_2j", 300, "f32"), ("gen_arm_base", 300, "f32"), ("gen_arm_yzx", 300, "f32"),
+                  ("gen_arm_yzx", 300, "f64"), ("gen_arm_skew", 300, "f32"), ("gen_arm_skew", 300, "f64"), ("gen_quad", 300, "f32"), ("gen_quad", 300, "f64"),
+                  ("gen_hexa", 300, "f32"), ("gen_hexa", 300, "f64")]
+GENERIC_TASK_STATES = [("gen_quad", 300, "f32", "v1_raw"), ("gen_hexa", 300, "f32", "v2k3"), ("gen_arm", 300, "f32", "v2k3")]
 
 
 # The other two task forms the kernels are built in (KW = 4 on v2, KW = 2 on v1): (vehicle, n, dtype, task) of every state the sweep's cases
@@ -42,7 +50,11 @@ STATE_CRC = {("hexa_arm", 300, "f32"): 0x180aced9, ("hexa_arm", 300, "f64"): 0xf
 
 
 def oracle_cfg(vehicle, n, task="v2"):
-    """The oracle's config of a sweep vehicle: the package's vehicle parameters on the reference task, auto-reset on."""
+    """The oracle's config of a sweep vehicle: the package's vehicle parameters on the reference task, auto-reset on; a "gen_..." vehicle:
+    tests/generic_vehicles.py's parameters and task constants in their place."""
+    if vehicle in GV.VEHICLES:
+        cfg = oracle_cfg({"gen_quad": "quad", "gen_hexa": "hexa"}.get(vehicle, "hexa_arm"), n, task)
+        return GV.build(cfg, vehicle)
     if task != "v2":
         veh = oracle_cfg(vehicle, n)
         if task in V1_VARIANT:
@@ -94,7 +106,7 @@ def oracle_run(vehicle, n, dtype, task="v2"):
     return cfg, run
 
 
-@pytest.mark.parametrize("vehicle,n,dtype", STATES)
+@pytest.mark.parametrize("vehicle,n,dtype", STATES + GENERIC_STATES)
 def test_blob_reaches_every_branch_and_the_flip_cap_is_a_condition(vehicle, n, dtype):
     cfg, run = oracle_run(vehicle, n, dtype)
     per_step = []
@@ -120,7 +132,7 @@ def test_one_waypoint_states_are_the_ones_the_sweep_always_ran():
         assert zlib.crc32(fs.tobytes() + is_.tobytes()) == STATE_CRC[key], key
 
 
-@pytest.mark.parametrize("vehicle,n,dtype,task", TASK_STATES)
+@pytest.mark.parametrize("vehicle,n,dtype,task", TASK_STATES + GENERIC_TASK_STATES)
 def test_task_blob_reaches_every_branch_and_the_flip_cap_is_a_condition(vehicle, n, dtype, task):
     """The same two conditions on the states of the v1 and the multi-waypoint cases: every class of the task within the six steps (what the
     rollout cases rely on within theirs), and in every step no more envs within FLIP_MARGIN of a threshold than the cap."""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import generic_vehicles as GV
 from tests.test_arm_cpu import arm_cfg
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,3 +103,22 @@ def test_heavy_arm_with_full_inertias(emu):
     out, _, qc, _ = emu_step(emu, cfg, s, a)
     ref = np.stack([O.arm_dynamics_step(cfg, s[i], a[i])[0] for i in range(len(s))])
     assert (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max() < 1e-12 and qc.max() == 0.0
+
+
+@pytest.mark.parametrize("substeps", [1, 2])
+def test_generic_arm_through_the_team_tables(emu, substeps):
+    """The fully general z,x,x arm of tests/generic_vehicles.py: joint origins without a zero, asymmetric joint limits (mid != 0), a full base
+    inertia, a mixer and clamps that differ from rotor to rotor and the other step length all pass through team_const_table /
+    make_team_params -- the packing the fp32 and fp64 team kernels read."""
+    cfg = GV.generic_task(GV.generic_arm(arm_cfg(), axes="zxx"))
+    cfg.task.rk4_substeps = substeps
+    s, a = random_states(np.random.RandomState(20 + substeps), 512)
+    out, eo, qc, _ = emu_step(emu, cfg, s, a)
+    refs = [O.arm_dynamics_step(cfg, s[i], a[i]) for i in range(len(s))]
+    ref = np.stack([r[0] for r in refs])
+    # the per-rotor clamps act on most envs of this action box and leave some alone: total thrust != / == the commanded one
+    clamped = np.abs(np.array([r[1][0] for r in refs]) - a[:, 0].astype(np.float64) * cfg.vehicle.mass * cfg.vehicle.g) > 1e-4
+    assert 50 < clamped.sum() <= len(s) - 10, clamped.sum()
+    assert (np.abs(out - ref) / np.maximum(1.0, np.abs(ref))).max() < 1e-12 and qc.max() == 0.0
+    eo_ref = np.stack([O.ee_position(cfg, ref[i]) - ref[i, :3] for i in range(len(s))])
+    assert np.abs(eo - eo_ref).max() < 1e-14
