@@ -1,115 +1,25 @@
-// amenv_capi.hip -- host side of libamenv.so: the C ABI declared in include/amenv.h.
+// amenv_capi.hip -- core source of libamenv.so's host side, the C ABI declared in include/amenv.h: env lifecycle and switches, reset /
+// observe / state, the two normalisers, the PID / min-snap baseline, and the functions amenv_host.hpp declares for the other sources
+// (amenv_capi_step / _rollout / _policy / _policy_norm / _eval / _train.hip: DESIGN 4x).
 // Owns the SoA episode state on one device, validates arguments, picks the kernel
 // instantiation (arithmetic type x rotor count x workgroup size) and enqueues it on the
 // caller's stream.  No synchronisation and no allocation after amenv_create().
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "amenv_kernels.hpp"
-#include "amenv_team.hpp"
-#include "amenv_team_host.hpp"
-#include "amenv_quad.hpp"
-#include "amenv_team_policy.hpp"
-#include "amenv_quad_policy.hpp"
-#include "amenv_lane_policy.hpp"
-#include "amenv_rigid_policy.hpp"
-#include "amenv_eval_policy.hpp"
-#include "amenv_obsnorm.hpp"
+#include "amenv_host.hpp"
+#include "amenv_policy_pack.hpp"
+#include "amenv_obsnorm_kernels.hpp"
 #include "amenv_retnorm.hpp"
-#include "amenv_policy.hpp"
-#include "amenv_train.hpp"
-#include "amenv_mlp_train.hpp"
 #include "amenv_baseline.hpp"
 
-using namespace amenv_dev;
-
-// which step kernel amenv_step runs (select_step_family); amenv_rollout runs the family's own rollout kernel where it has one
-enum class StepFamily {
-  Lane,         // step_kernel: one lane per env
-  LaneHelper,   // step_kernel_pw: rigid vehicles at small batches, helper waves per tile (reset RNG words, observation rows, Monitor totals)
-  Quad,         // step_kernel_quad: rigid vehicles, 4 lanes per env (amenv_quad.hpp); opt-in
-  Team,         // step_kernel_team: z,x,x-arm vehicle in the latency regime, 16 lanes per env (amenv_team.hpp); fp64 = logic-gate build
-  Staged,       // step_kernel_armk: z,x,x-arm vehicle, four RK4 stage waves + a main wave per 64-env tile; fp64 = logic-gate build
-  TwoWave,      // step_kernel_arm2w: fp32 z,x,x-arm vehicle, main + helper wave per 64-env tile
-};
-
-struct amenv {
-  amenv_config cfg;
-  int device = -1;
-  int obs_dim = 20, act_dim = kActDim, nf = 0;
-  void* blob = nullptr;            // tiled episode state (amenv_kernels.hpp "Data layout")
-  unsigned long long* stats = nullptr;
-  size_t blob_bytes = 0, fbytes = 0, ibytes = 0;
-  uint32_t tile_bytes = 0;
-  int n_tiles = 0;
-  int block = 64;
-  StepFamily family = StepFamily::Lane;
-  void* team_consts = nullptr;     // per-lane constants of the team / quad kernels (amenv_team_host.hpp): float4 pieces, or plain doubles for the fp64 build
-  uint32_t* pol_pack = nullptr;    // amenv_rollout_policy: policy parameters as MFMA fragments (re-packed on every call)
-  // n-link arm with n < 3 (amenv_vehicle.n_joints = 1 or 2): inside, the vehicle is the 3-joint one with PHANTOM links behind the real ones (zero
-  // mass / inertia / offset, joint limits 0 -> command 0, state 0: every term they add is an exact zero), so every kernel family serves it;
-  // the C ABI keeps the caller's dimensions (4 + n actions, 20 + 2 n + 3 observations, 2 n joint fields): pack / unpack kernels at the boundary
-  int pub_nj = 0;                  // the caller's n_joints (cfg.vehicle.n_joints is the internal 3 when this is 1 or 2)
-  float* io_act = nullptr;         // [N][7]   padded actions
-  float* io_obs = nullptr;         // [N][29]  internal observation rows
-  float* io_term = nullptr;        // [N][29]  internal terminal-observation rows
-  uint64_t steps = 0;
-  bool dr = false;                 // amenv_set_randomization: per-episode dynamics randomisation on
-  DrRanges dr_r = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};   // its ranges (lo, hi - lo); {1, 1} = the nominal vehicle
-  bool lag = false;                // amenv_set_rotor_lag: first-order rotor lag on
-  double lag_a[2] = {1.0, 1.0};    // its coefficients -expm1(-dt / tau_up), -expm1(-dt / tau_down), fp64
-  bool noise = false;              // amenv_set_sensor_noise: sensor noise on the observation rows
-  NoiseSig noise_s = {0.0f, 0.0f, 0.0f, 0.0f};   // its standard deviations: position, velocity, body rate, attitude
-  void* lag_w = nullptr;           // [n_tiles][n_rotors][64] rotor states | [n_rotors] w0, of the handle's dtype; allocated when the lag is first enabled
-  bool delay = false;              // amenv_set_action_delay: per-episode actuation latency on
-  int32_t delay_lo = 0, delay_hi = 0;   // its range of control steps, for the episodes that start from now on
-  void* delay_h = nullptr;         // float4 [n_tiles][8][64] given rows | int32 [n_tiles * 64] d | head << 4; allocated when the delay or the history is first enabled
-  int hist = 0;                    // amenv_set_action_history: given action rows appended to every observation row, 0..2; > 0 runs the DELAY kernels
-  float* hist_obs = nullptr;       // [N][obs_dim] the task's rows of amenv_reset / amenv_observe while the history is on, widened into the caller's buffer
-  RateBlock rate = {0, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};   // amenv_set_rate_control: body-rate actions; on = 0: off
-  bool delay_path() const { return delay || hist > 0; }   // the DELAY instantiations run: the latency, the history (range (0, 0) without the latency) or both
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
-  std::string err;
-  mutable std::string kname;       // amenv_kernel_name forms it from the state above when it is asked for
-};
-
 static thread_local std::string g_create_err;
-
-namespace {
-
-constexpr int kStatsWords = kStampBase + kStampWaves * kStampSlots;  // totals + diagnostic stamp area
-
-struct DeviceGuard {
-  int prev = -1, dev;
-  explicit DeviceGuard(int d) : dev(d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 int fail(amenv* e, int code, const std::string& msg) {
   if (e) e->err = msg; else g_create_err = msg;
   return code;
 }
 
-#define AMENV_HIP(e, call)                                                                       \
-  do {                                                                                           \
-    hipError_t _s = (call);                                                                      \
-    if (_s != hipSuccess) return fail(e, AMENV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
-  } while (0)
+namespace {
+
+constexpr int kStatsWords = kStampBase + kStampWaves * kStampSlots;  // totals + diagnostic stamp area
 
 // small dense helpers (host, fp64) for the default vehicles
 bool invert(int n, const double* a, double* out) {  // Gauss-Jordan, partial pivoting, n <= 4
@@ -231,63 +141,6 @@ bool vehicle_hexa_arm(amenv_vehicle* v) {
   return true;
 }
 
-template <typename T, int NR>
-HotParams<T, NR> make_hot(const amenv& e) {
-  const amenv_config& c = e.cfg;
-  const amenv_vehicle& v = c.vehicle;
-  HotParams<T, NR> P;
-  std::memset(&P, 0, sizeof(P));
-  for (int r = 0; r < v.n_rotors; r++) {
-    for (int j = 0; j < 4; j++) P.alloc[r][j] = T(v.alloc[r * 4 + j]);
-    for (int j = 0; j < 3; j++) P.mixm[j][r] = T(v.mix[(1 + j) * v.n_rotors + r]);
-    P.tmin[r] = T(v.t_min[r]); P.tmax[r] = T(v.t_max[r]);
-  }
-  const double* I = v.inertia; const double* J = v.inv_inertia;
-  P.Ixx = T(I[0]); P.Ixy = T(I[1]); P.Ixz = T(I[2]); P.Iyy = T(I[4]); P.Iyz = T(I[5]); P.Izz = T(I[8]);
-  P.Jxx = T(J[0]); P.Jxy = T(J[1]); P.Jxz = T(J[2]); P.Jyy = T(J[4]); P.Jyz = T(J[5]); P.Jzz = T(J[8]);
-  const int ns = c.task.rk4_substeps > 0 ? c.task.rk4_substeps : 1;
-  P.inv_mass = T(1.0 / v.mass); P.g = T(v.g); P.h = T(c.task.dt / ns);
-  P.mass_f = float(v.mass); P.g_f = float(v.g); P.mscale_f = float(v.moment_scale);
-  P.n_rotors = v.n_rotors; P.substeps = ns;
-  P.max_steps = c.task.max_episode_steps; P.counter_limit = c.task.counter_limit;
-  P.flags = c.flags; P.K = c.task.num_waypoints; P.raw_obs = c.task.variant == AMENV_TASK_V1_RAW17 ? 1 : 0;
-  P.ee_task = (v.n_joints > 0 && c.task.ee_task == AMENV_EE_TASK_TOOL) ? 1 : 0;
-  return P;
-}
-
-// joint axes other than (z, x, x): the kernels take the general-axes body, and only the lane kernel serves them
-bool generic_axes(const amenv_vehicle& v) {
-  const double zxx[9] = {0, 0, 1, 1, 0, 0, 1, 0, 0};
-  return std::memcmp(v.joint_axis, zxx, sizeof(zxx)) != 0;
-}
-
-template <typename T>
-ArmParams<T> make_arm(const amenv& e) {
-  const amenv_vehicle& v = e.cfg.vehicle;
-  ArmParams<T> A;
-  std::memset(&A, 0, sizeof(A));
-  for (int k = 0; k < 3; k++) {
-    for (int c = 0; c < 3; c++) { A.jo[k][c] = T(v.joint_origin[3 * k + c]); A.ja[k][c] = T(v.joint_axis[3 * k + c]); A.lc[k][c] = T(v.link_com[3 * k + c]); }
-    A.lm[k] = T(v.link_mass[k]);
-    const double* I = &v.link_inertia[9 * k];
-    A.li[k][0] = T(I[0]); A.li[k][1] = T(I[1]); A.li[k][2] = T(I[2]); A.li[k][3] = T(I[4]); A.li[k][4] = T(I[5]); A.li[k][5] = T(I[8]);
-    const float lo = float(v.joint_limit[2 * k]), hi = float(v.joint_limit[2 * k + 1]);
-    A.half[k] = 0.5f * (hi - lo); A.mid[k] = 0.5f * (hi + lo);
-
-  }
-  A.kp = T(v.joint_kp); A.kd = T(v.joint_kd); A.amax = T(v.joint_acc_max);
-  A.generic_axes = generic_axes(v) ? 1 : 0;
-  A.mtot = T(v.mass); A.inv_mtot = T(1.0 / v.mass);
-  for (int c = 0; c < 3; c++) {
-    A.tool[c] = T(v.tool_offset[c]);
-    // arm at home: every joint rotation is the identity, whatever the axes
-    A.ee_home[c] = v.n_joints > 0 ? T(v.joint_origin[c] + v.joint_origin[3 + c] + v.joint_origin[6 + c] + v.tool_offset[c]) : T(0);
-  }
-  return A;
-}
-
-// per-lane constant table / wave-uniform parameters of the team kernels: amenv_team_host.hpp (shared with the host emulation of tests/emu)
-template <typename T> TeamParamsT<T> make_team(const amenv& e) { return make_team_params<T>(e.cfg, e.team_consts); }
 // the per-lane table on the device (float4 pieces for fp32, plain doubles for the fp64 build); with_params: the team kernels' parameters
 // behind it (the step kernel's source; the other team kernels take them as arguments)
 template <typename T> hipError_t upload_team_consts(amenv* e, bool with_params) {
@@ -301,66 +154,12 @@ template <typename T> hipError_t upload_team_consts(amenv* e, bool with_params) 
   return hipMemcpy(static_cast<char*>(e->team_consts) + team_table_bytes<T>(), &P, sizeof(P), hipMemcpyHostToDevice);
 }
 
-QuadParams make_quad(const amenv& e) {
-  const amenv_config& c = e.cfg;
-  const amenv_vehicle& v = c.vehicle;
-  QuadParams P;
-  std::memset(&P, 0, sizeof(P));
-  const int six[6] = {0, 1, 2, 4, 5, 8};
-  for (int j = 0; j < 6; j++) { P.I[j] = float(v.inertia[six[j]]); P.Iinv[j] = float(v.inv_inertia[six[j]]); }
-  P.inv_mass = float(1.0 / v.mass);
-  const int ns = c.task.rk4_substeps > 0 ? c.task.rk4_substeps : 1;
-  P.h = float(c.task.dt / ns); P.substeps = ns;
-  for (int r = 0; r < 6 && r < v.n_rotors; r++) { P.tmin[r] = float(v.t_min[r]); P.tmax[r] = float(v.t_max[r]); }
-  P.max_steps = c.task.max_episode_steps; P.counter_limit = c.task.counter_limit; P.flags = c.flags;
-  P.ee_task = 0; P.K = 1;
-  P.consts = reinterpret_cast<const float4*>(e.team_consts);
-  return P;
-}
-
-ColdParams make_cold(const amenv& e) {
-  const amenv_config& c = e.cfg;
-  ColdParams C;
-  for (int k = 0; k < AMENV_MAX_WAYPOINTS; k++) { C.traj_sin[k] = float(c.task.traj_sin[k]); C.traj_cos[k] = float(c.task.traj_cos[k]); }
-  C.seed_lo = uint32_t(c.seed); C.seed_hi = uint32_t(c.seed >> 32);
-  C.gid0 = c.env_id_offset;
-  return C;
-}
-
 // episode-start rotor state: the rotors spin at the NOMINAL hover command, sqrt(clamp(alloc[r] . (m g, 0, 0, 0))), fp64
 double lag_w0(const amenv_vehicle& v, int r) {
   const double t = v.alloc[r * 4] * (v.mass * v.g);
   return std::sqrt(std::fmax(std::fmin(t, v.t_max[r]), v.t_min[r]));
 }
-template <typename T, int NROT> LagArg<T, NROT, true> make_lag(const amenv& e) {
-  LagArg<T, NROT, true> L;
-  L.w = static_cast<T*>(e.lag_w); L.n_pad = uint32_t(e.n_tiles) * 64u;
-  L.a_up = T(e.lag_a[0]); L.a_down = T(e.lag_a[1]);
-  return L;
-}
-DelayArg<true> make_delay(const amenv& e) {
-  DelayArg<true> D;
-  D.h = static_cast<float4*>(e.delay_h); D.n_pad = uint32_t(e.n_tiles) * 64u;
-  D.lo = e.delay ? e.delay_lo : 0; D.span = e.delay ? e.delay_hi - e.delay_lo + 1 : 1;   // the history alone: range (0, 0), every d is 0
-  D.hist = e.hist;
-  return D;
-}
-// the kernels' last argument: the randomisation ranges, behind them the lag block in the LAG instantiations, behind that the sensor
-// noise's sigmas in the NOISE ones, behind those the actuation latency's fields in the DELAY ones
-template <typename T, int NROT, unsigned DYN> DynArg<T, NROT, DYN> make_dyn(const amenv& e) {
-  DynArg<T, NROT, DYN> a;
-  if constexpr ((DYN & kDynDr) != 0) { a.R.r = e.dr_r; a.R.q = e.rate; } else a.R.unused = 0;
-  if constexpr ((DYN & kDynLag) != 0) a.L = make_lag<T, NROT>(e);
-  if constexpr ((DYN & kDynNoise) != 0) a.Z.s = e.noise_s;
-  if constexpr ((DYN & kDynDelay) != 0) a.D = make_delay(e);
-  return a;
-}
-// the cold kernels' (reset, observe) runtime switch
-NoiseRt make_noise_rt(const amenv& e) {
-  return NoiseRt{e.noise_s, uint32_t(e.cfg.seed), uint32_t(e.cfg.seed >> 32), e.cfg.env_id_offset, e.noise ? 1 : 0};
-}
 
-bool is_v1(const amenv_config* c) { return c->task.variant == AMENV_TASK_V1_SCALED17 || c->task.variant == AMENV_TASK_V1_RAW17; }
 int obs_dim_of(const amenv_config* c) { return is_v1(c) ? 17 : 20 + 2 * c->vehicle.n_joints + (c->vehicle.n_joints ? 3 : 0); }
 int act_dim_of(const amenv_config* c) { return kActDim + c->vehicle.n_joints; }
 
@@ -396,25 +195,10 @@ const char* validate(const amenv_config* c) {
   return nullptr;
 }
 
-// The predicates below take the internal config: validated (an arm implies 6 rotors and the v2 task) and padded (an arm of 1 or 2 joints has
-// n_joints = 3, pad_arm_config).
-// z,x,x arm on the single-waypoint task: the team, stage-wave and two-wave kernels
-bool zxx_arm1(const amenv_config& c) { return c.vehicle.n_joints == 3 && !generic_axes(c.vehicle) && c.task.num_waypoints == 1; }
-// lane-quad kernels (step: opt-in; closed loop: amenv_rollout_policy): fp32 rigid vehicle with 4 or 6 rotors, single-waypoint v2 task, default workgroup size
-bool quad_ok(const amenv_config& c) {
-  return c.vehicle.n_joints == 0 && c.dtype == AMENV_F32 && (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6) && !is_v1(&c) && c.task.num_waypoints == 1 &&
-         c.block_size == 0;
-}
-// fp32 lane-team kernels (step, rollout, closed loop: amenv_rollout_policy)
-bool team_ok(const amenv_config& c) { return c.dtype == AMENV_F32 && zxx_arm1(c); }
-// one-lane-per-env closed loop of the rigid vehicles (amenv_rigid_policy.hpp): fp32, 4 or 6 rotors, every task, any workgroup size
-bool rigid_pol_ok(const amenv_config& c) { return c.vehicle.n_joints == 0 && c.dtype == AMENV_F32 && (c.vehicle.n_rotors == 4 || c.vehicle.n_rotors == 6); }
-// closed loop (amenv_rollout_policy) of an fp32 arm vehicle: every one of them -- 1..3 joints (the internal, phantom-padded config has 3),
-// 1..4 waypoints, any joint axes.  The team kernel where the step runs it (team_ok, family Team), the lane form (amenv_lane_policy.hpp) elsewhere
-bool arm_pol_ok(const amenv_config& c) { return c.vehicle.n_joints == 3 && c.dtype == AMENV_F32; }
-
 constexpr int kTeamAutoMax = 6144;    // AUTO: lane-team kernel up to this batch
 constexpr int kArmkAutoMax = 32768;   // AUTO: stage-wave kernel up to this batch
+
+}  // namespace
 
 // Which step kernel a config runs: amenv_config.step_kernel, or by batch size for AUTO (crossovers measured on MI355X).
 // Returns the refusal text when a requested kernel is not built for the config.
@@ -452,7 +236,7 @@ const char* select_step_family(const amenv_config& c, StepFamily* out) {
 
 // Lane-team step kernel: four integrating waves + one helper per workgroup while every workgroup gets a CU to itself, else one + one
 // (amenv_team.hpp, step_kernel_team).
-static bool team_wide(const amenv& e) {
+bool team_wide(const amenv& e) {
   static std::mutex m;
   static int cus[64] = {0};
   const int d = e.device >= 0 && e.device < 64 ? e.device : 0;
@@ -498,173 +282,7 @@ std::string kernel_name(const amenv& e) {
   return name;
 }
 
-// one kernel launch; timed: stamped at dispatch and completion with amenv_step_timed's events
-template <typename... P, typename... A>
-hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
-  if (timed) hipExtLaunchKernelGGL(k, grid, block, lds, s, e.ev_start, e.ev_stop, 0, args...);
-  else hipLaunchKernelGGL(k, grid, block, lds, s, args...);
-  return hipGetLastError();
-}
-
-// amenv_rollout, T_steps steps in one launch: the team and quad families have rollout kernels of their own, every other family's rollout
-// runs the lane kernel
-template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYN>
-hipError_t launch_rollout(const amenv& e, const StepIO& io, int T_steps, hipStream_t s) {
-  const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
-  const ColdParams C = make_cold(e);
-  const uint32_t tb = e.tile_bytes;
-  const int32_t n = e.cfg.num_envs;
-  switch (e.family) {
-    case StepFamily::Team:   // one wave per 4 envs; the fp64 build is a logic gate of amenv_step only (amenv_rollout refuses it)
-      if constexpr (NJ == 3 && sizeof(T) == 4 && DYN == 0)
-        return launch(e, false, rollout_kernel_team<NROT>, dim3(e.n_tiles * 16), dim3(64), 0, s, e.blob, tb, n, reinterpret_cast<const float*>(io.actions), io.obs,
-                      static_cast<float*>(io.reward), io.done, io.info, T_steps, tl, C, make_team<T>(e));
-      return hipErrorInvalidValue;
-    case StepFamily::Quad:   // one wave per 16 envs
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && DYN == 0)
-        return launch(e, false, rollout_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(64), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
-                      io.info, T_steps, tl, C, make_quad(e));
-      return hipErrorInvalidValue;
-    case StepFamily::Lane: case StepFamily::LaneHelper: case StepFamily::Staged: case StepFamily::TwoWave:
-      break;
-  }
-  ArmArg<T, NJ> AA;
-  if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
-  const int bs = e.block;
-  return launch(e, false, rollout_kernel<T, NROT, KW, VAR, NJ, DYN>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + ((DYN & kDynDelay) ? 4 * e.hist : 0)) * sizeof(float), s,
-                e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, T_steps, tl, make_hot<T, NROT>(e), C, AA, make_dyn<T, NROT, DYN>(e));
-}
-
-// amenv_step (T_steps = 0, timed: amenv_step_timed) or amenv_rollout (T_steps > 0) with one instantiation of the kernel templates; the
-// if constexpr guards keep every kernel out of the code object that no config pairs with this instantiation
-template <typename T, int NROT, int KW, int VAR, int NJ = 0, unsigned DYN = 0>
-hipError_t launch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (T_steps > 0) return launch_rollout<T, NROT, KW, VAR, NJ, DYN>(e, io, T_steps, s);
-  ArmArg<T, NJ> AA;
-  if constexpr (NJ > 0) AA.p = make_arm<T>(e); else AA.unused = 0;
-  const HotParams<T, NROT> P = make_hot<T, NROT>(e);
-  const ColdParams C = make_cold(e);
-  const StepTail tl{io.terminal_obs, io.ep_return, io.ep_len, io.stats};
-  const uint32_t tb = e.tile_bytes;
-  const int32_t n = e.cfg.num_envs;
-  switch (e.family) {
-    case StepFamily::Team:   // 16 lanes per env; 16 envs per workgroup (four main waves + one episode-end helper wave) while each workgroup has a CU to itself, else 4 (one + one)
-      if constexpr (NJ == 3 && DYN == 0) {   // (the kernel reads its parameters from the device block behind the table: amenv_create wrote them there)
-        const TeamParamsT<T> TP = make_team<T>(e);
-        if (team_wide(e))
-          return launch(e, timed, step_kernel_team<T, NROT, 4>, dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, n, int32_t(e.n_tiles * 4),
-                        reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
-        return launch(e, timed, step_kernel_team<T, NROT, 1>, dim3(e.n_tiles * 16), dim3(128), 0, s, e.blob, n, int32_t(e.n_tiles * 16),
-                      reinterpret_cast<const float*>(io.actions), TP.consts, io.obs, static_cast<T*>(io.reward), io.done, io.info, tl, C);
-      }
-      break;
-    case StepFamily::Staged:   // one tile per 320-thread workgroup: four stage waves + main wave
-      if constexpr (NJ == 3 && DYN == 0) {
-        if constexpr (sizeof(T) == 8) {   // the fp64 logic-gate build exchanges its aggregates in fp64: > 64 KB of dynamic LDS needs the attribute
-          hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel_armk<T, NROT>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          if (ea != hipSuccess) return ea;
-        }
-        const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + 12 * 64) * sizeof(float) + size_t((4 * kAggSlots + 6) * 64) * sizeof(T);   // obs rows | reset words | aggregates, joints (T)
-        return launch(e, timed, step_kernel_armk<T, NROT>, dim3(e.n_tiles), dim3(320), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
-      }
-      break;
-    case StepFamily::TwoWave:   // one tile per 128-thread workgroup: main + helper wave
-      if constexpr (NJ == 3 && sizeof(T) == 4 && DYN == 0) {
-        const size_t lds = size_t(64 * ObsDim<VAR, NJ>::value + (kArmXchgSlots + 12) * 64) * sizeof(float);   // obs rows | RK4 exchange | reset words
-        return launch(e, timed, step_kernel_arm2w<T, NROT>, dim3(e.n_tiles), dim3(128), lds, s, e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA);
-      }
-      break;
-    case StepFamily::Quad:   // 4 lanes per env, 16 envs per workgroup: main wave + episode-end helper wave
-      if constexpr (NJ == 0 && sizeof(T) == 4 && KW == 1 && VAR == VAR_V2 && (NROT == 4 || NROT == 6) && DYN == 0)
-        return launch(e, timed, step_kernel_quad<NROT>, dim3(e.n_tiles * 4), dim3(128), 0, s, e.blob, tb, n, io.actions, io.obs, static_cast<float*>(io.reward), io.done,
-                      io.info, tl, C, make_quad(e));
-      break;
-    case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
-      if constexpr (NJ == 0) {
-        const size_t lds = size_t(64 * (ObsDim<VAR, 0>::value + ((DYN & kDynDelay) ? 8 : 0)) + 12 * 64) * sizeof(float);   // (the DELAY forms stage rows of up to two more action rows)
-        return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DYN>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
-                      io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DYN>(e));
-      }
-      break;
-    case StepFamily::Lane: {
-      const int bs = e.block;
-      return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DYN>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + ((DYN & kDynDelay) ? 4 * e.hist : 0)) * sizeof(float), s,
-                    e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DYN>(e));
-    }
-  }
-  return hipErrorInvalidValue;   // a family this instantiation has no kernel for: select_step_family and dispatch_step never pair them
-}
-
-// The switch set a handle runs, for amenv_step, amenv_rollout and the closed-loop rollouts alike: the lag, the noise and the DELAY path, and DR with any
-// of them or with rate control, whose block travels with the ranges (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
-unsigned dyn_set(const amenv& e) {
-  const int nr = e.cfg.vehicle.n_rotors;
-  if (e.cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6)) return 0;
-  const unsigned on = (e.lag ? kDynLag : 0) | (e.noise ? kDynNoise : 0) | (e.delay_path() ? kDynDelay : 0);
-  return on | (on || e.dr || e.rate.on ? kDynDr : 0);
-}
-template <auto V> using const_c = std::integral_constant<decltype(V), V>;
-// f(const_c<NROT>, const_c<DYN>) with DYN == dyn, over the sets that are built for T (dyn_admitted) and NROT (the general rotor count: no switch)
-template <typename T, int NROT, unsigned DYN = 0, typename F>
-hipError_t with_dyn(unsigned dyn, F& f) {
-  if constexpr (DYN <= kDynAll) {
-    if constexpr (dyn_admitted<T, 0>(DYN) && (DYN == 0 || NROT == 4 || NROT == 6)) { if (dyn == DYN) return f(const_c<NROT>{}, const_c<DYN>{}); }
-    return with_dyn<T, NROT, DYN + 1>(dyn, f);
-  }
-  return hipErrorInvalidValue;
-}
-// a rigid handle's compile-time form: its rotor count (4, 6, or the general loop bound) and its switch set
-template <typename T, typename F>
-hipError_t with_rigid_form(const amenv& e, F f) {
-  const unsigned dyn = dyn_set(e);
-  const int nr = e.cfg.vehicle.n_rotors;
-  return nr == 4 ? with_dyn<T, 4>(dyn, f) : nr == 6 ? with_dyn<T, 6>(dyn, f) : with_dyn<T, AMENV_MAX_ROTORS>(dyn, f);
-}
-// a rigid handle's task: f(const_c<KW>, const_c<VAR>)
-template <typename F>
-hipError_t with_task(const amenv& e, F f) {
-  if (is_v1(&e.cfg)) return f(const_c<2>{}, const_c<VAR_V1>{});   // v1: up to 2 waypoints per episode
-  if (e.cfg.task.num_waypoints == 1) return f(const_c<1>{}, const_c<VAR_V2>{});
-  return f(const_c<AMENV_MAX_WAYPOINTS>{}, const_c<VAR_V2>{});
-}
-// the kernels built for 4 and 6 rotors alone (the caller has refused every other count): f(const_c<NROT>)
-template <typename F>
-auto with_rotors46(int nr, F f) { return nr == 4 ? f(const_c<4>{}) : f(const_c<6>{}); }
-
-// The (obs_dim, act_dim) pairs the policy kernels are built for (amenv_policy_forward, amenv_policy_forward_mfma, amenv_ppo_mlp_step), stated once here
-// for the library; ActorCritic._FUSED_DIMS (ppo.py) and the comments in include/amenv.h name the same nine, tests/test_gpu_policy_shapes.py holds them together
-template <int D, int A> struct shape_c {};
-template <typename... S> struct shape_list {};
-using PolicyShapes = shape_list<shape_c<20, 4>, shape_c<29, 7>, shape_c<17, 4>, shape_c<25, 5>, shape_c<27, 6>,   // v2 | hexacopter + 3-link arm | v1 | hexacopter + 1- / 2-link arm
-                                shape_c<24, 4>, shape_c<28, 4>, shape_c<21, 4>, shape_c<25, 4>>;                  // v2 / v1 rows of the rigid vehicles with one or two action rows of history
-// the action widths amenv_gaussian_act and amenv_ppo_loss_grad are built for: 4 = quad / hexa, 4 + n = hexa + n joints (the rows' width plays no part: 0)
-using ActionWidths = shape_list<shape_c<0, 4>, shape_c<0, 5>, shape_c<0, 6>, shape_c<0, 7>>;
-// f(const_c<D>, const_c<A>) for the listed pair that equals (d, a); hipErrorInvalidValue when none does
-template <typename F, int... D, int... A>
-hipError_t with_shape(shape_list<shape_c<D, A>...>, int d, int a, const F& f) {
-  hipError_t st = hipErrorInvalidValue;
-  (void)((d == D && a == A && (st = f(const_c<D>{}, const_c<A>{}), true)) || ...);
-  return st;
-}
-template <typename F> hipError_t with_policy_shape(int obs_dim, int act_dim, const F& f) { return with_shape(PolicyShapes{}, obs_dim, act_dim, f); }
-template <typename F> hipError_t with_act_dim(int act_dim, const F& f) { return with_shape(ActionWidths{}, 0, act_dim, [&](auto, auto a) { return f(a); }); }
-bool policy_shape_built(int obs_dim, int act_dim) { return with_policy_shape(obs_dim, act_dim, [](auto, auto) { return hipSuccess; }) == hipSuccess; }
-bool act_dim_built(int act_dim) { return with_act_dim(act_dim, [](auto) { return hipSuccess; }) == hipSuccess; }
-
-// The launchers below pick the handle's arithmetic type themselves: behind each template a plain overload that the entry points call
-template <typename T>
-hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed) {
-  if (e.cfg.vehicle.n_joints == 3) {
-    if (e.cfg.task.num_waypoints == 1) return launch_step<T, 6, 1, VAR_V2, 3>(e, io, T_steps, s, timed);   // BASELINE config 3
-    return launch_step<T, 6, AMENV_MAX_WAYPOINTS, VAR_V2, 3>(e, io, T_steps, s, timed);                    // arm + 2..4 waypoints: the lane kernel
-  }
-  return with_rigid_form<T>(e, [&](auto nrot, auto dyn) {
-    return with_task(e, [&](auto kw, auto var) {
-      return launch_step<T, decltype(nrot)::value, decltype(kw)::value, decltype(var)::value, 0, decltype(dyn)::value>(e, io, T_steps, s, timed);
-    });
-  });
-}
-hipError_t dispatch_step(const amenv& e, const StepIO& io, int T_steps, hipStream_t s, bool timed = false) { return e.cfg.dtype == AMENV_F64 ? dispatch_step<double>(e, io, T_steps, s, timed) : dispatch_step<float>(e, io, T_steps, s, timed); }
+namespace {
 
 template <typename T>
 hipError_t launch_reset(const amenv& e, const uint8_t* mask, float* obs, int pad_only, hipStream_t s) {
@@ -692,44 +310,6 @@ hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hip
   return hipGetLastError();
 }
 hipError_t launch_transpose(const amenv& e, void* f, int32_t* i, int to_api, hipStream_t s) { return e.cfg.dtype == AMENV_F64 ? launch_transpose<double>(e, f, i, to_api, s) : launch_transpose<float>(e, f, i, to_api, s); }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// amenv_rigid_policy.hpp: workgroup shape by batch size: 16 envs per workgroup fill the CUs at small batches, 64 or 128 envs
-// (one or two env wavefronts) cost fewer MLP wavefronts per env at large ones.  Measured on MI355X, v1_raw quadrotor with the normaliser, us per
-// step (NE = 16 / 64 / 128): 4096 envs 5.4 / 7.4 / 11.0, 8192 9.4 / 7.3 / 10.9, 16384 17.5 / 7.9 / 11.3, 32768 33.3 / 14.3 / 12.0
-// (profiles/r04/rigid_policy_crossover_*.json); the bounds sit at the interpolated crossovers.  -DAMENV_RIGID_WG16_MAX / -DAMENV_RIGID_WG64_MAX build the
-// variants the crossover was measured with (tools/build_variant.py)
-#ifndef AMENV_RIGID_WG16_MAX
-#define AMENV_RIGID_WG16_MAX 6144
-#endif
-#ifndef AMENV_RIGID_WG64_MAX
-#define AMENV_RIGID_WG64_MAX 24576
-#endif
-template <int NROT, int KW, int VAR, bool NORM, unsigned DYN>
-hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  const HotParams<float, NROT> HP = make_hot<float, NROT>(e);
-  const ColdParams C = make_cold(e);
-  const DynArg<float, NROT, DYN> R = make_dyn<float, NROT, DYN>(e);
-  const int n = e.cfg.num_envs;
-  if (n <= AMENV_RIGID_WG16_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DYN>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
-  else if (n <= AMENV_RIGID_WG64_MAX)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 64, DYN>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
-  else   // (n_tiles is a multiple of 4: every 128-env workgroup covers two whole tiles)
-    hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 128, DYN>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
-  return hipGetLastError();
-}
-template <bool NORM>
-hipError_t launch_rigid_policy(const amenv& e, int T, const PolicyIO& io, const NormArg& N, hipStream_t s) {
-  return with_rigid_form<float>(e, [&](auto nrot, auto dyn) {
-    if constexpr (decltype(nrot)::value == 4 || decltype(nrot)::value == 6)   // (rigid_pol_ok)
-      return with_task(e, [&](auto kw, auto var) {
-        return launch_rigid_policy_k<decltype(nrot)::value, decltype(kw)::value, decltype(var)::value, NORM, decltype(dyn)::value>(e, T, io, N, s);
-      });
-    else return hipErrorInvalidValue;
-  });
-}
 
 // amenv_dynamics_factors: [N][2 + NROT] = km, kI, s_0.. of every env's current episode (dr_draw: the kernels' own arithmetic)
 template <int NROT>
@@ -867,6 +447,8 @@ hipError_t launch_hist_widen(const amenv& e, float* out, hipStream_t s) {
   return hipGetLastError();
 }
 
+}  // namespace
+
 // amenv_rollout_policy[_norm] after the entry checks: pack the parameters, fill the kernel's I/O block
 PolicyIO policy_io(amenv& e, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards,
                    uint8_t* dones, uint32_t* info_bits, float* terminal_obs, hipStream_t s) {
@@ -881,109 +463,12 @@ PolicyIO policy_io(amenv& e, const float* flat_params, uint64_t seed, uint32_t d
   return io;
 }
 
-// amenv_rollout_policy, arm vehicles outside the team kernel's range: one lane per env (amenv_lane_policy.hpp; 64 envs per workgroup up to
-// 16384 envs, 128 above: one workgroup per CU either way).  PNJ: the caller's joints (a 1- / 2-link arm publishes its own row widths)
-template <int KW, int PNJ>
-hipError_t launch_lane_policy_k(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
-  ArmArg<float, 3> AA;
-  AA.p = make_arm<float>(e);
-  const HotParams<float, 6> HP = make_hot<float, 6>(e);
-  const int n = e.cfg.num_envs;
-  if (n <= 16384)
-    hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 1, KW, PNJ>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, make_cold(e), AA, e.io_term);
-  else
-    hipLaunchKernelGGL((rollout_policy_kernel_lane<6, 2, KW, PNJ>), dim3((e.n_tiles + 1) / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, make_cold(e), AA,
-                       e.io_term);
-  return hipGetLastError();
-}
-template <int KW>
-hipError_t launch_lane_policy_kw(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
-  if (e.pub_nj == 1) return launch_lane_policy_k<KW, 1>(e, T, io, s);
-  if (e.pub_nj == 2) return launch_lane_policy_k<KW, 2>(e, T, io, s);
-  return launch_lane_policy_k<KW, 3>(e, T, io, s);
-}
-hipError_t launch_lane_policy(const amenv& e, int T, const PolicyIO& io, hipStream_t s) {
-  return e.cfg.task.num_waypoints == 1 ? launch_lane_policy_kw<1>(e, T, io, s) : launch_lane_policy_kw<AMENV_MAX_WAYPOINTS>(e, T, io, s);
-}
-
-// amenv_evaluate_policy (amenv_eval_policy.hpp): one workgroup shape at every batch size -- 16 envs for the rigid vehicles, 64 for the arm
-template <bool NORM>
-hipError_t launch_rigid_eval(const amenv& e, int max_steps, const PolicyIO& io, const NormArg& N, const EvalArg& E, hipStream_t s) {
-  return with_rigid_form<float>(e, [&](auto nrot, auto dyn) {
-    if constexpr (decltype(nrot)::value == 4 || decltype(nrot)::value == 6)   // (rigid_pol_ok)
-      return with_task(e, [&](auto kw, auto var) {
-        constexpr int NROT = decltype(nrot)::value;
-        constexpr unsigned DYN = decltype(dyn)::value;
-        hipLaunchKernelGGL((evaluate_policy_kernel_rigid<NROT, decltype(kw)::value, decltype(var)::value, NORM, DYN>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes,
-                           e.cfg.num_envs, max_steps, io, make_hot<float, NROT>(e), make_cold(e), N, make_dyn<float, NROT, DYN>(e), E);
-        return hipGetLastError();
-      });
-    else return hipErrorInvalidValue;
-  });
-}
-template <int KW, int PNJ>
-hipError_t launch_lane_eval_k(const amenv& e, int max_steps, const PolicyIO& io, const EvalArg& E, hipStream_t s) {
-  ArmArg<float, 3> AA;
-  AA.p = make_arm<float>(e);
-  hipLaunchKernelGGL((evaluate_policy_kernel_lane<KW, PNJ>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, e.cfg.num_envs, max_steps, io, make_hot<float, 6>(e), make_cold(e), AA, E);
-  return hipGetLastError();
-}
-template <int KW>
-hipError_t launch_lane_eval_kw(const amenv& e, int max_steps, const PolicyIO& io, const EvalArg& E, hipStream_t s) {
-  if (e.pub_nj == 1) return launch_lane_eval_k<KW, 1>(e, max_steps, io, E, s);
-  if (e.pub_nj == 2) return launch_lane_eval_k<KW, 2>(e, max_steps, io, E, s);
-  return launch_lane_eval_k<KW, 3>(e, max_steps, io, E, s);
-}
-hipError_t launch_lane_eval(const amenv& e, int max_steps, const PolicyIO& io, const EvalArg& E, hipStream_t s) {
-  return e.cfg.task.num_waypoints == 1 ? launch_lane_eval_kw<1>(e, max_steps, io, E, s) : launch_lane_eval_kw<AMENV_MAX_WAYPOINTS>(e, max_steps, io, E, s);
-}
-
+namespace {
 template <typename V>
 __global__ void calibration_copy_kernel(const V* __restrict__ src, V* __restrict__ dst, size_t n) {
   for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) dst[i] = src[i];
 }
 
-}  // namespace
-
-// workspace of amenv_ppo_mlp_step: advantage partials | split-weight streams of both nets | per-workgroup gradient slabs of both nets
-namespace {
-constexpr size_t kMlpWsAdv = size_t(2) * kPpoMaxBlocks * sizeof(double);
-constexpr size_t kMlpWsWt = size_t(2) * kMlpFragsPerNet * 1024;
-constexpr size_t kMlpWsPart = size_t(2) * kMlpMaxBlocks * kAccSize * sizeof(float);
-constexpr size_t kMlpLds = kMlpLdsBytes;
-template <bool kCtl, int D, int A, bool kVclip = false>   // kVclip: the third form (ctl may be NULL there), with the old values and clip_range_vf
-hipError_t launch_mlp_step(const float* Pm, const u32x4* WS, const float* obs, const float* actions, const float* old_logp, const float* adv, const float* ret,
-                           const int64_t* index, int64_t n,
-                           float clip, float vf, int normalize, const double* adv_part, int adv_blocks, float* part, int blocks, amenv_ppo_ctl* ctl, hipStream_t s,
-                           const float* old_values = nullptr, float clip_vf = 0.0f) {
-  // > 64 KB of dynamic LDS needs the attribute on the device the launch goes to (the PPO entry points run on the CURRENT device): kept per
-  // device, under a lock -- a process that drives several GPUs would otherwise launch without it on the second one
-  {
-    static std::mutex mu;
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-      e = hipFuncSetAttribute(kVclip ? reinterpret_cast<const void*>(&ppo_mlp_fused_kernel_vclip<D, A>)
-                              : kCtl ? reinterpret_cast<const void*>(&ppo_mlp_fused_kernel_ctl<D, A>) : reinterpret_cast<const void*>(&ppo_mlp_fused_kernel<D, A>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, int(kMlpLds));
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-  }
-  if (kVclip)
-    hipLaunchKernelGGL((ppo_mlp_fused_kernel_vclip<D, A>), dim3(blocks, 2), dim3(256), kMlpLds, s, ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf, normalize,
-                       adv_part, adv_blocks, part, old_values, clip_vf);
-  else if (kCtl)
-    hipLaunchKernelGGL((ppo_mlp_fused_kernel_ctl<D, A>), dim3(blocks, 2), dim3(256), kMlpLds, s, ctl, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf, normalize,
-                       adv_part, adv_blocks, part);
-  else
-    hipLaunchKernelGGL((ppo_mlp_fused_kernel<D, A>), dim3(blocks, 2), dim3(256), kMlpLds, s, Pm, WS, obs, actions, old_logp, adv, ret, index, n, clip, vf, normalize, adv_part,
-                       adv_blocks, part);
-  return hipGetLastError();
-}
 }  // namespace
 
 extern "C" {
@@ -1174,7 +659,8 @@ int amenv_destroy(amenv* e) {
 const char* amenv_last_error(const amenv* e) { return e ? e->err.c_str() : g_create_err.c_str(); }
 const char* amenv_kernel_name(const amenv* e) { return e ? (e->kname = kernel_name(*e)).c_str() : ""; }   // of the handle's state by now: no setter keeps it current
 
-namespace {
+}  // extern "C"
+
 hipError_t pad_actions(const amenv& e, const float* actions, hipStream_t s) {
   const int n = e.cfg.num_envs;
   hipLaunchKernelGGL(arm_pad_actions_kernel, dim3((n * 7 + 255) / 256), dim3(256), 0, s, actions, n, e.pub_nj, e.io_act);
@@ -1185,7 +671,8 @@ hipError_t cut_obs(const amenv& e, const float* rows29, const uint8_t* rows_of, 
   hipLaunchKernelGGL(arm_cut_obs_kernel, dim3((n * od + 255) / 256), dim3(256), 0, s, rows29, n, e.pub_nj, rows_of, out);
   return hipGetLastError();
 }
-}  // namespace
+
+extern "C" {
 
 int amenv_set_seed(amenv* e, uint64_t seed) {
   if (!e) return AMENV_ERR_INVALID;
@@ -1496,98 +983,6 @@ int amenv_ee_position(amenv* e, float* ee_out, void* stream) {
   return AMENV_OK;
 }
 
-namespace {
-// amenv_step and amenv_step_timed after their NULL checks (who: the entry point, for the messages)
-int step_launch(amenv* e, const char* who, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits, float* terminal_obs,
-                float* ep_return, int32_t* ep_len, hipStream_t s, bool timed) {
-  if (!aligned16(actions) || !aligned16(obs) || (terminal_obs && !aligned16(terminal_obs)))
-    return fail(e, AMENV_ERR_INVALID, std::string(who) + ": actions/obs/terminal_obs must be 16-byte aligned");
-  DeviceGuard g(e->device);
-  StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, e->stats};
-  if (e->io_act) { AMENV_HIP(e, pad_actions(*e, actions, s)); io.actions = reinterpret_cast<const float4*>(e->io_act); io.obs = e->io_obs; io.terminal_obs = terminal_obs ? e->io_term : nullptr; }
-  AMENV_HIP(e, dispatch_step(*e, io, 0, s, timed));
-  if (e->io_act) { AMENV_HIP(e, cut_obs(*e, e->io_obs, nullptr, obs, s)); if (terminal_obs) AMENV_HIP(e, cut_obs(*e, e->io_term, done, terminal_obs, s)); }
-  e->steps += uint64_t(e->cfg.num_envs);
-  return AMENV_OK;
-}
-}  // namespace
-
-int amenv_step(amenv* e, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits, float* terminal_obs,
-               float* ep_return, int32_t* ep_len, void* stream) {
-  if (!e) return AMENV_ERR_INVALID;
-  if (!actions || !obs || !reward || !done || !info_bits) return fail(e, AMENV_ERR_INVALID, "amenv_step: actions/obs/reward/done/info_bits must be non-NULL");
-  return step_launch(e, "amenv_step", actions, obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, (hipStream_t)stream, false);
-}
-
-int amenv_step_timed(amenv* e, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits,
-                     float* terminal_obs, float* ep_return, int32_t* ep_len, void* stream, float* kernel_us) {
-  if (!e) return AMENV_ERR_INVALID;
-  if (!actions || !obs || !reward || !done || !info_bits || !kernel_us) return fail(e, AMENV_ERR_INVALID, "amenv_step_timed: NULL argument");
-  DeviceGuard g(e->device);
-  if (!e->ev_start) { AMENV_HIP(e, hipEventCreate(&e->ev_start)); AMENV_HIP(e, hipEventCreate(&e->ev_stop)); }
-  const int rc = step_launch(e, "amenv_step_timed", actions, obs, reward, done, info_bits, terminal_obs, ep_return, ep_len, (hipStream_t)stream, true);
-  if (rc != AMENV_OK) return rc;
-  AMENV_HIP(e, hipEventSynchronize(e->ev_stop));
-  float ms = 0.f;
-  AMENV_HIP(e, hipEventElapsedTime(&ms, e->ev_start, e->ev_stop));
-  *kernel_us = ms * 1000.0f;
-  return AMENV_OK;
-}
-
-int amenv_rollout(amenv* e, int32_t n_steps, const float* actions, float* obs, void* reward, uint8_t* done, uint32_t* info_bits,
-                  void* stream) {
-  if (!e) return AMENV_ERR_INVALID;
-  if (n_steps <= 0 || !actions) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: n_steps must be > 0 and actions non-NULL");
-  if (!aligned16(actions) || (obs && !aligned16(obs))) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: actions/obs must be 16-byte aligned");
-  if (e->family == StepFamily::Team && e->cfg.dtype == AMENV_F64) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: the fp64 lane-team build is a logic gate of amenv_step only");
-  if (e->io_act) return fail(e, AMENV_ERR_INVALID, "amenv_rollout: arms with 1 or 2 joints are served through amenv_step (the adapters at the C ABI are per step)");
-  DeviceGuard g(e->device);
-  StepIO io{reinterpret_cast<const float4*>(actions), obs, reward, done, info_bits, nullptr, nullptr, nullptr, e->stats};
-  hipError_t st = dispatch_step(*e, io, n_steps, (hipStream_t)stream);
-  AMENV_HIP(e, st);
-  e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
-  return AMENV_OK;
-}
-
-int amenv_rollout_policy(amenv* e, int32_t n_steps, const float* flat_params, uint64_t seed, uint32_t draw0, float* obs, float* actions, float* logp,
-                         float* values, float* rewards, uint8_t* dones, uint32_t* info_bits, float* terminal_obs, void* stream) {
-  if (!e) return AMENV_ERR_INVALID;
-  // with dynamics randomisation a quad_ok config runs the one-lane-per-env form: the lane-quad kernels are not built with it
-  const bool quad = !e->dr && !e->lag && !e->noise && !e->delay_path() && !e->rate.on && quad_ok(e->cfg), rigid = !quad && rigid_pol_ok(e->cfg);
-  if (!quad && !rigid && !arm_pol_ok(e->cfg))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: built for fp32 vehicles: rigid with 4 or 6 rotors (every task), or the 6-rotor vehicle with a "
-                "1..3-link arm (v2 task, 1..4 waypoints, any joint axes)");
-  if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
-  if (rigid && (!aligned16(obs) || !aligned16(actions) || (terminal_obs && !aligned16(terminal_obs))))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy: obs / actions / terminal_obs must be 16-byte aligned");
-  DeviceGuard g(e->device);
-  hipStream_t s = (hipStream_t)stream;
-  const PolicyIO io = policy_io(*e, flat_params, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits, terminal_obs, s);
-  const int n = e->cfg.num_envs;
-  if (quad) {   // rigid vehicle, single-waypoint v2 task, default workgroup size: 16 envs per workgroup, the lane-quad step inside (amenv_quad_policy.hpp)
-    const QuadParams QP = make_quad(*e);
-    const dim3 gq(e->n_tiles * 4), bq(256);
-    with_rotors46(e->cfg.vehicle.n_rotors, [&](auto nrot) {
-      hipLaunchKernelGGL((rollout_policy_kernel_quad<decltype(nrot)::value>), gq, bq, 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), QP);
-    });
-  } else if (rigid) {   // every other rigid config (v1 tasks, 2..4 waypoints, a set workgroup size): one lane per env (amenv_rigid_policy.hpp)
-    AMENV_HIP(e, launch_rigid_policy<false>(*e, (int)n_steps, io, NormArg{nullptr, 0.0f, 0.0, 0}, s));
-  } else if (e->family == StepFamily::Team && !e->io_act) {   // the caller's vehicle is the 3-joint z,x,x arm on one waypoint
-    // The env part follows the step kernel's choice: 16 lanes per env where amenv_step runs the lane-team kernel (small batches).  One 16-env
-    // workgroup per CU up to 4096 envs (5.15 vs 5.22 us per step there); above that the variant compiled for two wavefronts per SIMD pays
-    // (measured on MI355X at 8192 envs: 7.9 vs 10.1 us per step)
-    const TeamParams TP = make_team<float>(*e);
-    if (n <= 4096) hipLaunchKernelGGL((rollout_policy_kernel_team<6, 1>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
-    else hipLaunchKernelGGL((rollout_policy_kernel_team<6, 2>), dim3(e->n_tiles * 4), dim3(256), 0, s, e->blob, e->tile_bytes, n, (int)n_steps, io, e->stats, make_cold(*e), TP);
-  } else {   // every other fp32 arm config: one lane per env
-    AMENV_HIP(e, launch_lane_policy(*e, (int)n_steps, io, s));
-  }
-  AMENV_HIP(e, hipGetLastError());
-  e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
-  return AMENV_OK;
-}
-
 int amenv_get_state(amenv* e, void* fstate, int32_t* istate, void* stream) {
   if (!e) return AMENV_ERR_INVALID;
   DeviceGuard g(e->device);
@@ -1626,11 +1021,6 @@ int amenv_stats_read(amenv* e, amenv_stats* out, int reset, void* stream) {
 }
 
 // ---- observation normaliser ------------------------------------------------------------------------------------------
-struct amenv_obsnorm {
-  int dim = 0, device = 0;
-  double* buf = nullptr;   // obsnorm_words(dim) doubles on the device
-};
-
 int amenv_obsnorm_create(int32_t dim, int device, amenv_obsnorm** out) {
   if (!out || dim <= 0 || dim > 1024) return fail(nullptr, AMENV_ERR_INVALID, "amenv_obsnorm_create: bad argument");
   int ndev = 0;
@@ -1709,62 +1099,6 @@ int amenv_obsnorm_set(amenv_obsnorm* h, const double* mean, const double* var, d
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(h->buf, staging.data(), staging.size(), hipMemcpyHostToDevice) != hipSuccess)
     return AMENV_ERR_HIP;
   return AMENV_OK;
-}
-
-int amenv_rollout_policy_norm(amenv* e, amenv_obsnorm* h, int32_t update, float clip, double eps, int32_t n_steps, const float* flat_params, uint64_t seed,
-                              uint32_t draw0, float* obs, float* actions, float* logp, float* values, float* rewards, uint8_t* dones, uint32_t* info_bits,
-                              float* terminal_obs, void* stream) {
-  if (!e || !h) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: env and normaliser must be non-NULL");
-  if (!rigid_pol_ok(e->cfg))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: built for fp32 rigid vehicles with 4 or 6 rotors (arm vehicles: amenv_rollout_policy, normalise outside)");
-  if (e->hist)
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: not built with the action history (amenv_set_action_history): normalise step by step, or turn the history off");
-  if (h->dim != e->obs_dim) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser's dim differs from the env's obs_dim");
-  if (h->device != e->device) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: the normaliser lives on another device");
-  if (n_steps <= 0 || !flat_params || !obs || !actions || !logp || !values || !rewards || !dones)
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: n_steps must be > 0 and flat_params / obs / actions / logp / values / rewards / dones non-NULL");
-  if (!(clip > 0.0f) || !(eps >= 0.0)) return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: clip must be > 0 and eps >= 0");
-  if (!aligned16(obs) || !aligned16(actions) || (terminal_obs && !aligned16(terminal_obs)))
-    return fail(e, AMENV_ERR_INVALID, "amenv_rollout_policy_norm: obs / actions / terminal_obs must be 16-byte aligned");
-  DeviceGuard g(e->device);
-  hipStream_t s = (hipStream_t)stream;
-  const PolicyIO io = policy_io(*e, flat_params, seed, draw0, obs, actions, logp, values, rewards, dones, info_bits, terminal_obs, s);
-  AMENV_HIP(e, launch_rigid_policy<true>(*e, (int)n_steps, io, NormArg{h->buf, clip, eps, update}, s));
-  const int d = h->dim;
-  if (update)   // the launch left the sums of the raw rows 1..T in the batch slots: one merge of T x N rows (Chan's formula, associative)
-    hipLaunchKernelGGL(obsnorm_merge_kernel, dim3(1), dim3(((d + 63) / 64) * 64), 0, s, h->buf, d, double(n_steps) * double(e->cfg.num_envs));
-  AMENV_HIP(e, hipGetLastError());
-  e->steps += uint64_t(e->cfg.num_envs) * uint64_t(n_steps);
-  return AMENV_OK;
-}
-
-int amenv_evaluate_policy(amenv* e, amenv_obsnorm* h, float clip, double eps, const float* flat_params, int32_t deterministic, uint64_t seed, uint32_t draw0,
-                          int32_t episodes_per_env, int32_t max_steps, double* returns, int32_t* counts, int32_t* steps_run, void* stream) {
-  if (!e) return AMENV_ERR_INVALID;
-  if (!flat_params || !returns || !counts || !steps_run) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: flat_params / returns / counts / steps_run must be non-NULL");
-  if (episodes_per_env <= 0 || max_steps <= 0) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: episodes_per_env and max_steps must be > 0");
-  if (e->cfg.dtype != AMENV_F32) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: built for fp32 handles (an fp64 handle evaluates step by step)");
-  if (!(e->cfg.flags & AMENV_FLAG_AUTO_RESET))
-    return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: needs AMENV_FLAG_AUTO_RESET (an env whose episode ended would never start the next one)");
-  const bool rigid = rigid_pol_ok(e->cfg), arm = arm_pol_ok(e->cfg);
-  if (!rigid && !arm)
-    return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: built for rigid vehicles with 4 or 6 rotors (every task) and the 6-rotor vehicle with a 1..3-link arm (v2 task)");
-  if (h) {
-    if (!rigid) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: the normaliser form is built for rigid vehicles (arm vehicles: norm = NULL)");
-    if (e->hist) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: the normaliser form is not built with the action history (amenv_set_action_history)");
-    if (h->dim != e->obs_dim) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: the normaliser's dim differs from the env's obs_dim");
-    if (h->device != e->device) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: the normaliser lives on another device");
-    if (!(clip > 0.0f) || !(eps >= 0.0)) return fail(e, AMENV_ERR_INVALID, "amenv_evaluate_policy: clip must be > 0 and eps >= 0");
-  }
-  DeviceGuard g(e->device);
-  hipStream_t s = (hipStream_t)stream;
-  AMENV_HIP(e, hipMemsetAsync(steps_run, 0, sizeof(int32_t), s));
-  const PolicyIO io = policy_io(*e, flat_params, seed, draw0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-  const EvalArg E{deterministic, episodes_per_env, returns, counts, steps_run};
-  if (!rigid) AMENV_HIP(e, launch_lane_eval(*e, (int)max_steps, io, E, s));
-  else if (h) AMENV_HIP(e, launch_rigid_eval<true>(*e, (int)max_steps, io, NormArg{h->buf, clip, eps, 0}, E, s));
-  else AMENV_HIP(e, launch_rigid_eval<false>(*e, (int)max_steps, io, NormArg{nullptr, 0.0f, 0.0, 0}, E, s));
-  return AMENV_OK;   // (the step counter behind amenv_stats is host-side and stays: the steps executed are known on the device only)
 }
 
 // ---- reward normaliser (VecNormalize norm_reward; csrc/amenv_retnorm.hpp) ---------------------------------------------
@@ -1849,133 +1183,6 @@ int amenv_retnorm_set(amenv_retnorm* h, double mean, double var, double count, c
   return AMENV_OK;
 }
 
-// ---- PPO helpers (row f3): GAE over a [T, N] rollout buffer, Gaussian action sampling ------------------------------
-int amenv_gae(const float* rewards, const float* values, const uint8_t* dones, const float* last_values, float* advantages,
-              float* returns, int32_t n_steps, int64_t n_envs, float gamma, float gae_lambda, void* stream) {
-  if (!rewards || !values || !dones || !last_values || !advantages || !returns || n_steps <= 0 || n_envs <= 0 ||
-      !(gamma >= 0.0f && gamma <= 1.0f) || !(gae_lambda >= 0.0f && gae_lambda <= 1.0f))
-    return AMENV_ERR_INVALID;
-  const int bs = n_envs <= 65536 ? 64 : 256;
-  hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n_envs + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, rewards, values, dones,
-                     last_values, advantages, returns, (int)n_steps, (int64_t)n_envs, gamma, gae_lambda);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_gaussian_act(const float* mean, const float* log_std, const float* low, const float* high, float* raw, float* clipped,
-                       float* logp, int64_t n_envs, int32_t act_dim, uint64_t seed, uint32_t draw, int64_t env_id_offset, void* stream) {
-  if (!mean || !log_std || !low || !high || !raw || !clipped || !logp || n_envs <= 0 || env_id_offset < 0 || !act_dim_built(act_dim)) return AMENV_ERR_INVALID;
-  const int bs = n_envs <= 65536 ? 64 : 256;
-  const dim3 grid((unsigned)((n_envs + bs - 1) / bs)), block(bs);
-  const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
-  const hipError_t st = with_act_dim(act_dim, [&](auto a) {
-    hipLaunchKernelGGL(gaussian_act_kernel<decltype(a)::value>, grid, block, 0, (hipStream_t)stream, mean, log_std, low, high, raw, clipped, logp, (int64_t)n_envs, s_lo, s_hi, draw, (int64_t)env_id_offset);
-    return hipGetLastError();
-  });
-  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_policy_forward(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out,
-                         float* value_out, void* stream) {
-  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !policy_shape_built(obs_dim, act_dim)) return AMENV_ERR_INVALID;
-  const dim3 grid((unsigned)((n + 63) / 64), 2), block(64 * kPolWaves);
-  hipStream_t s = (hipStream_t)stream;
-  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
-    hipLaunchKernelGGL((policy_forward_kernel<decltype(d)::value, decltype(a)::value>), grid, block, 0, s, flat_params, obs, (int64_t)n, mean_out, value_out);
-    return hipGetLastError();
-  });
-  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_policy_forward_mfma(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, int64_t n, float* mean_out, float* value_out,
-                              void* workspace, void* stream) {
-  if (!flat_params || !obs || n <= 0 || (!mean_out && !value_out) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u) || !policy_shape_built(obs_dim, act_dim))
-    return AMENV_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  uint16_t* WS = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + kMlpWsAdv);   // the split-weight area of amenv_ppo_mlp_step's workspace
-  hipLaunchKernelGGL(mlp_pack_kernel, dim3((2 * kMlpPackThreadsPerNet + 255) / 256), dim3(256), 0, s, flat_params, (int)obs_dim, (int)act_dim, WS);
-  const int64_t ntiles = (n + 31) / 32;
-  const int nets = (mean_out ? 1 : 0) + (value_out ? 1 : 0);   // two wavefronts per SIMD (242 registers): 512 workgroups fill the chip
-  const dim3 grid((unsigned)std::min<int64_t>(512 / nets, (ntiles + 3) / 4), 2), block(256);
-  const u32x4* ws = reinterpret_cast<const u32x4*>(WS);
-  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
-    hipLaunchKernelGGL((mlp_forward_kernel<decltype(d)::value, decltype(a)::value>), grid, block, 0, s, flat_params, ws, obs, (int64_t)n, mean_out, value_out);
-    return hipGetLastError();   // (of the pack kernel's launch too)
-  });
-  return st == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-size_t amenv_ppo_workspace_bytes(void) { return size_t(kPpoMaxBlocks) * (2 * sizeof(double) + kPpoPartial * sizeof(float)); }
-
-size_t amenv_ppo_ctl_bytes(void) { return sizeof(amenv_ppo_ctl); }
-
-int amenv_ppo_ctl_arm(amenv_ppo_ctl* ctl, float kl_limit, void* stream) {
-  if (!ctl || (reinterpret_cast<uintptr_t>(ctl) & 3u) || kl_limit != kl_limit) return AMENV_ERR_INVALID;
-  hipLaunchKernelGGL(ppo_ctl_arm_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ctl, kl_limit);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-// The plain entry point and the _ctl one state their launch geometry themselves and share one launcher; the plain one passes no control
-// block.  RULE: the geometry lines of a _ctl entry point are a verbatim copy of its plain twin's -- tests/test_launch_geometry_cpu.py derives
-// the thresholds from the plain one's body, and both launch on the same workspace layout: change one, change the other.
-static int ppo_loss_grad_launch(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
-                                const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
-                                float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
-                                void* workspace, amenv_ppo_ctl* ctl, int blocks, void* stream, const float* old_values = nullptr, float clip_range_vf = 0.0f) {
-  if (reinterpret_cast<uintptr_t>(ctl) & 3u) return AMENV_ERR_INVALID;
-  if (!mean || !value || !log_std || !actions || !old_logp || !advantages || !returns || !d_mean || !d_value || !d_log_std || !stats4 ||
-      !workspace || n <= 0 || !(clip_range >= 0.0f) || (reinterpret_cast<uintptr_t>(workspace) & 7u) || !act_dim_built(act_dim))
-    return AMENV_ERR_INVALID;
-  double* adv_part = static_cast<double*>(workspace);
-  float* part = reinterpret_cast<float*>(adv_part + 2 * kPpoMaxBlocks);
-  hipStream_t s = (hipStream_t)stream;
-  // with a control block the _ctl forms of the kernels, without one the plain forms: the code that ran before the block existed (amenv_train.hpp)
-  if (ctl) hipLaunchKernelGGL(ppo_adv_partials_ctl, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, advantages, (int64_t)n, adv_part, (const int64_t*)nullptr);
-  else hipLaunchKernelGGL(ppo_adv_partials, dim3(blocks), dim3(kPpoBlock), 0, s, advantages, (int64_t)n, adv_part, (const int64_t*)nullptr);
-  (void)with_act_dim(act_dim, [&](auto a) {   // (a launch error is read below)
-    if (old_values)   // the value-clip form, ctl or none; the launches around it are the _ctl or the plain ones
-      hipLaunchKernelGGL(ppo_loss_grad_vclip<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, mean, value, log_std, actions, old_logp, advantages, returns,
-                         (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part, old_values, clip_range_vf);
-    else if (ctl)
-      hipLaunchKernelGGL(ppo_loss_grad_ctl<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, mean, value, log_std, actions, old_logp, advantages, returns,
-                         (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part);
-    else
-      hipLaunchKernelGGL(ppo_loss_grad<decltype(a)::value>, dim3(blocks), dim3(kPpoBlock), 0, s, mean, value, log_std, actions, old_logp, advantages, returns,
-                         (int64_t)n, clip_range, vf_coef, (int)normalize_advantage, (const double*)adv_part, blocks, d_mean, d_value, part);
-    return hipSuccess;
-  });
-  if (ctl) hipLaunchKernelGGL(ppo_finalize_ctl, dim3(1), dim3(64), 0, s, ctl, (const float*)part, blocks, (int)act_dim, (int64_t)n, log_std, ent_coef, d_log_std, stats4);
-  else hipLaunchKernelGGL(ppo_finalize, dim3(1), dim3(64), 0, s, (const float*)part, blocks, (int)act_dim, (int64_t)n, log_std, ent_coef, d_log_std, stats4);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_ppo_loss_grad(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
-                        const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
-                        float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
-                        void* workspace, void* stream) {
-  const int blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  return ppo_loss_grad_launch(mean, value, log_std, actions, old_logp, advantages, returns, n, act_dim, clip_range, ent_coef, vf_coef, normalize_advantage, d_mean,
-                              d_value, d_log_std, stats4, workspace, nullptr, blocks, stream);
-}
-
-int amenv_ppo_loss_grad_ctl(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
-                            const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
-                            float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
-                            void* workspace, amenv_ppo_ctl* ctl, void* stream) {
-  const int blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  return ppo_loss_grad_launch(mean, value, log_std, actions, old_logp, advantages, returns, n, act_dim, clip_range, ent_coef, vf_coef, normalize_advantage, d_mean,
-                              d_value, d_log_std, stats4, workspace, ctl, blocks, stream);
-}
-
-int amenv_ppo_loss_grad_vclip(const float* mean, const float* value, const float* log_std, const float* actions, const float* old_logp,
-                              const float* advantages, const float* returns, int64_t n, int32_t act_dim, float clip_range, float ent_coef,
-                              float vf_coef, int32_t normalize_advantage, float* d_mean, float* d_value, float* d_log_std, float* stats4,
-                              void* workspace, amenv_ppo_ctl* ctl, const float* old_values, float clip_range_vf, void* stream) {
-  if (!old_values || !(clip_range_vf > 0.0f) || !std::isfinite(clip_range_vf)) return AMENV_ERR_INVALID;
-  const int blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  return ppo_loss_grad_launch(mean, value, log_std, actions, old_logp, advantages, returns, n, act_dim, clip_range, ent_coef, vf_coef, normalize_advantage, d_mean,
-                              d_value, d_log_std, stats4, workspace, ctl, blocks, stream, old_values, clip_range_vf);
-}
-
 // Bench / profiling utility: a copy of known size with a chosen access width per lane, so that the PMC traffic counters (FETCH_SIZE,
 // WRITE_SIZE) can be calibrated on the access pattern of the kernel under test (16 B per lane: one-lane-per-env kernels; 4 B per lane:
 // lane-team kernels) -- /opt/skills/guides/MI355X_MICROARCH.md, HBM section.
@@ -1984,119 +1191,6 @@ int amenv_calibration_copy(const void* src, void* dst, size_t bytes, int32_t byt
   hipStream_t s = (hipStream_t)stream;
   if (bytes_per_lane == 4) hipLaunchKernelGGL((calibration_copy_kernel<float>), dim3(2048), dim3(256), 0, s, (const float*)src, (float*)dst, bytes / 4);
   else hipLaunchKernelGGL((calibration_copy_kernel<float4>), dim3(2048), dim3(256), 0, s, (const float4*)src, (float4*)dst, bytes / 16);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-size_t amenv_ppo_mlp_workspace_bytes(void) { return kMlpWsAdv + kMlpWsWt + kMlpWsPart; }
-
-static int ppo_mlp_step_launch(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
-                               const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
-                               int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, amenv_ppo_ctl* ctl, int adv_blocks, int blocks,
-                               void* stream, const float* old_values = nullptr, float clip_range_vf = 0.0f) {
-  if ((reinterpret_cast<uintptr_t>(ctl) & 3u) || !flat_params || !obs || !actions || !old_logp || !advantages || !returns || !flat_grad || !stats4 || !workspace || n <= 0 || !(clip_range >= 0.0f) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15u) || !policy_shape_built(obs_dim, act_dim))
-    return AMENV_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  double* adv_part = reinterpret_cast<double*>(ws);
-  uint16_t* WS = reinterpret_cast<uint16_t*>(ws + kMlpWsAdv);
-  float* part = reinterpret_cast<float*>(ws + kMlpWsAdv + kMlpWsWt);
-  const dim3 pro_grid(adv_blocks + (2 * kMlpPackThreadsPerNet + kPpoBlock - 1) / kPpoBlock);
-  if (ctl) hipLaunchKernelGGL(ppo_mlp_prologue_kernel_ctl, pro_grid, dim3(kPpoBlock), 0, s, (const amenv_ppo_ctl*)ctl, advantages, (int64_t)n, adv_part, index, adv_blocks, flat_params,
-                              (int)obs_dim, (int)act_dim, WS);
-  else hipLaunchKernelGGL(ppo_mlp_prologue_kernel, pro_grid, dim3(kPpoBlock), 0, s, advantages, (int64_t)n, adv_part, index, adv_blocks, flat_params, (int)obs_dim, (int)act_dim, WS);
-  const hipError_t st = with_policy_shape(obs_dim, act_dim, [&](auto d, auto a) {
-    constexpr int D_ = decltype(d)::value, A_ = decltype(a)::value;
-    const u32x4* ws4 = reinterpret_cast<const u32x4*>(WS);
-    if (old_values)   // the value-clip form, ctl or none
-      return launch_mlp_step<true, D_, A_, true>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
-                                                 part, blocks, ctl, s, old_values, clip_range_vf);
-    return ctl ? launch_mlp_step<true, D_, A_>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
-                                               part, blocks, ctl, s)
-               : launch_mlp_step<false, D_, A_>(flat_params, ws4, obs, actions, old_logp, advantages, returns, index, n, clip_range, vf_coef, normalize_advantage, adv_part, adv_blocks,
-                                                part, blocks, nullptr, s);
-  });
-  if (st != hipSuccess) return AMENV_ERR_HIP;
-  const int trunk = kH1 * obs_dim + kH1 + kH2 * kH1 + kH2 + kH3 * kH2 + kH3;
-  const int total = act_dim + 2 * trunk + act_dim * kH3 + act_dim + kH3 + 1;
-  // plain form: the four scalars follow the gradient entries; _ctl form: one more workgroup that holds the scalars alone
-  if (ctl)
-    hipLaunchKernelGGL(mlp_grad_reduce_kernel_ctl, dim3((total + 63) / 64 + 1), dim3(64 * kRedGroups), 0, s, ctl, (const float*)part, blocks, (int)obs_dim, (int)act_dim, (int64_t)n,
-                       flat_params, ent_coef, flat_grad, stats4);
-  else
-    hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3((total + 4 + 63) / 64), dim3(64 * kRedGroups), 0, s, (const float*)part, blocks, (int)obs_dim, (int)act_dim, (int64_t)n, flat_params,
-                       ent_coef, flat_grad, stats4);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_ppo_mlp_step(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
-                       const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
-                       int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, void* stream) {
-  const int adv_blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  const int64_t ntiles = (n + 31) / 32;
-  const int blocks = int(std::min<int64_t>(128, (ntiles + 3) / 4));   // 128 x 2 nets x 4 wavefronts = one wavefront per SIMD
-  return ppo_mlp_step_launch(flat_params, obs_dim, act_dim, obs, actions, old_logp, advantages, returns, index, n, clip_range, ent_coef, vf_coef, normalize_advantage,
-                             flat_grad, stats4, workspace, nullptr, adv_blocks, blocks, stream);
-}
-
-int amenv_ppo_mlp_step_ctl(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
-                           const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
-                           int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, amenv_ppo_ctl* ctl, void* stream) {
-  const int adv_blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  const int64_t ntiles = (n + 31) / 32;
-  const int blocks = int(std::min<int64_t>(128, (ntiles + 3) / 4));   // 128 x 2 nets x 4 wavefronts = one wavefront per SIMD
-  return ppo_mlp_step_launch(flat_params, obs_dim, act_dim, obs, actions, old_logp, advantages, returns, index, n, clip_range, ent_coef, vf_coef, normalize_advantage,
-                             flat_grad, stats4, workspace, ctl, adv_blocks, blocks, stream);
-}
-
-int amenv_ppo_mlp_step_vclip(const float* flat_params, int32_t obs_dim, int32_t act_dim, const float* obs, const float* actions, const float* old_logp,
-                             const float* advantages, const float* returns, const int64_t* index, int64_t n, float clip_range, float ent_coef, float vf_coef,
-                             int32_t normalize_advantage, float* flat_grad, float* stats4, void* workspace, amenv_ppo_ctl* ctl, const float* old_values,
-                             float clip_range_vf, void* stream) {
-  if (!old_values || !(clip_range_vf > 0.0f) || !std::isfinite(clip_range_vf)) return AMENV_ERR_INVALID;
-  const int adv_blocks = int(std::min<int64_t>(kPpoMaxBlocks, (n + kPpoBlock - 1) / kPpoBlock));
-  const int64_t ntiles = (n + 31) / 32;
-  const int blocks = int(std::min<int64_t>(128, (ntiles + 3) / 4));   // 128 x 2 nets x 4 wavefronts = one wavefront per SIMD
-  return ppo_mlp_step_launch(flat_params, obs_dim, act_dim, obs, actions, old_logp, advantages, returns, index, n, clip_range, ent_coef, vf_coef, normalize_advantage,
-                             flat_grad, stats4, workspace, ctl, adv_blocks, blocks, stream, old_values, clip_range_vf);
-}
-
-static int ppo_adam_step_launch(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6, float* grad_norm_out,
-                                uint32_t* ticket, amenv_ppo_ctl* ctl, int blocks, void* stream) {
-  if ((reinterpret_cast<uintptr_t>(ctl) & 3u) || !flat_params || !flat_grad || !exp_avg || !exp_avg_sq || !step || !hyper6 || !ticket || n <= 0 || !aligned16(flat_grad)) return AMENV_ERR_INVALID;
-  if (ctl)
-    hipLaunchKernelGGL(adam_clip_kernel_ctl, dim3(blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, ctl, flat_params, (const float*)flat_grad, exp_avg, exp_avg_sq, step, (int64_t)n, hyper6,
-                       grad_norm_out, ticket);
-  else
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, flat_params, (const float*)flat_grad, exp_avg, exp_avg_sq, step, (int64_t)n, hyper6,
-                       grad_norm_out, ticket);
-  return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
-}
-
-int amenv_ppo_adam_step(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6, float* grad_norm_out,
-                        uint32_t* ticket, void* stream) {
-  const int blocks = int(std::min<int64_t>(kAdamMaxBlocks, (n + kAdamBlock - 1) / kAdamBlock));
-  return ppo_adam_step_launch(flat_params, flat_grad, exp_avg, exp_avg_sq, step, n, hyper6, grad_norm_out, ticket, nullptr, blocks, stream);
-}
-
-int amenv_ppo_adam_step_ctl(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, const float* hyper6, float* grad_norm_out,
-                            uint32_t* ticket, amenv_ppo_ctl* ctl, void* stream) {
-  const int blocks = int(std::min<int64_t>(kAdamMaxBlocks, (n + kAdamBlock - 1) / kAdamBlock));
-  return ppo_adam_step_launch(flat_params, flat_grad, exp_avg, exp_avg_sq, step, n, hyper6, grad_norm_out, ticket, ctl, blocks, stream);
-}
-
-// The KL-adaptive form: its own launch, the rule copied into it; geometry as amenv_ppo_adam_step's.
-int amenv_ppo_adam_step_adapt(float* flat_params, const float* flat_grad, float* exp_avg, float* exp_avg_sq, float* step, int64_t n, float* hyper6, float* grad_norm_out,
-                              uint32_t* ticket, amenv_ppo_ctl* ctl, const amenv_ppo_lr_rule* rule, void* stream) {
-  if (!ctl || (reinterpret_cast<uintptr_t>(ctl) & 3u) || !rule || rule->struct_size != sizeof(amenv_ppo_lr_rule)) return AMENV_ERR_INVALID;
-  const amenv_ppo_lr_rule r = *rule;
-  if (!std::isfinite(r.desired_kl) || !std::isfinite(r.band) || !std::isfinite(r.factor) || !std::isfinite(r.lr_min) || !std::isfinite(r.lr_max) ||
-      !(r.desired_kl > 0.0f) || !(r.band >= 1.0f) || !(r.factor > 1.0f) || !(r.lr_min > 0.0f) || !(r.lr_min <= r.lr_max))
-    return AMENV_ERR_INVALID;
-  if (!flat_params || !flat_grad || !exp_avg || !exp_avg_sq || !step || !hyper6 || !ticket || n <= 0 || !aligned16(flat_grad)) return AMENV_ERR_INVALID;
-  const int blocks = int(std::min<int64_t>(kAdamMaxBlocks, (n + kAdamBlock - 1) / kAdamBlock));
-  hipLaunchKernelGGL(adam_clip_kernel_adapt, dim3(blocks), dim3(kAdamBlock), 0, (hipStream_t)stream, ctl, flat_params, (const float*)flat_grad, exp_avg, exp_avg_sq, step, (int64_t)n, hyper6,
-                     grad_norm_out, ticket, r);
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
 
@@ -2205,35 +1299,5 @@ int amenv_pid_policy(const amenv_pid_policy_params* p, int32_t dtype, const floa
   else hipLaunchKernelGGL(pid_policy_kernel<float>, grid, block, 0, (hipStream_t)stream, d, obs, done, (float*)pstate, actions, (int64_t)n);
   return hipGetLastError() == hipSuccess ? AMENV_OK : AMENV_ERR_HIP;
 }
-
-#ifdef AMENV_STAMPS
-// diagnostic build only: an empty kernel with the step kernel's grid, to measure the dependent-launch floor
-__global__ void noop_kernel(void* blob, uint32_t tile_bytes, int32_t n, unsigned long long* sink) {
-  if (n < 0) sink[0] = tile_bytes;
-}
-__global__ void touch_kernel(void* blob, uint32_t tile_bytes, int32_t n, unsigned long long* sink) {
-  // one 16-B load + one 16-B store per lane: the minimal memory round trip
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int4* p = reinterpret_cast<int4*>(static_cast<char*>(blob) + size_t(i >> 6) * tile_bytes) + (threadIdx.x & 63);
-  int4 v = *p; v.w ^= 0; *p = v;
-}
-int amenv_debug_noop(amenv* e, int which, int block, void* stream) {
-  DeviceGuard g(e->device);
-  const int bs = block > 0 ? block : e->block, n_pad = e->n_tiles * 64;
-  if (which >= 2) hipLaunchKernelGGL(noop_kernel, dim3(which), dim3(bs), 0, (hipStream_t)stream, e->blob, e->tile_bytes, e->cfg.num_envs, e->stats);   // explicit grid
-  else if (which == 0) hipLaunchKernelGGL(noop_kernel, dim3((n_pad + bs - 1) / bs), dim3(bs), 0, (hipStream_t)stream, e->blob, e->tile_bytes, e->cfg.num_envs, e->stats);
-  else hipLaunchKernelGGL(touch_kernel, dim3((n_pad + bs - 1) / bs), dim3(bs), 0, (hipStream_t)stream, e->blob, e->tile_bytes, e->cfg.num_envs, e->stats);
-  AMENV_HIP(e, hipGetLastError());
-  return AMENV_OK;
-}
-
-// diagnostic build only: copy the per-wave s_memtime stamps of the last step launch to host (synchronises)
-int amenv_debug_stamps(amenv* e, unsigned long long* host_out /*[64][8]*/) {
-  DeviceGuard g(e->device);
-  AMENV_HIP(e, hipDeviceSynchronize());
-  AMENV_HIP(e, hipMemcpy(host_out, e->stats + kStampBase, sizeof(unsigned long long) * kStampWaves * kStampSlots, hipMemcpyDeviceToHost));
-  return AMENV_OK;
-}
-#endif
 
 }  // extern "C"

@@ -27,7 +27,7 @@ struct QuadParams {          // wave-uniform (SGPRs)
   float tmin[6], tmax[6];
   int32_t substeps, max_steps, counter_limit, ee_task, K;   // ee_task = 0, K = 1 (the task code reads them)
   uint32_t flags;
-  const float4* consts;      // the team constant table (amenv_capi.hip team_const_table): this kernel reads the columns of body 0
+  const float4* consts;      // the team constant table (amenv_team_host.hpp team_const_table): this kernel reads the columns of body 0
 };
 
 struct QuadLane {

@@ -1,5 +1,5 @@
 // amenv_team_host.hpp -- host side of the lane-team kernels: the per-lane constant table and the wave-uniform parameters, from an
-// amenv_config.  Plain C++ (no HIP): included by amenv_capi.hip (product) and by tests/emu/team_emu.cpp (host emulation of the arithmetic).
+// amenv_config.  Plain C++ (no HIP): included through amenv_host.hpp by the amenv_capi*.hip sources (product) and by tests/emu/team_emu.cpp (host emulation of the arithmetic).
 #pragma once
 #include <cstring>
 #include <vector>

@@ -1,6 +1,6 @@
 """Every launch-geometry threshold of the training-side kernels (everything behind the C ABI that is not an env step) against fp64.
 
-Each launcher in csrc/amenv_capi.hip caps its grid and loops inside the kernel beyond the cap, or switches its block size at a batch size.
+Each launcher in csrc/amenv_capi*.hip caps its grid and loops inside the kernel beyond the cap, or switches its block size at a batch size.
 GEOMETRY below is the one table of those thresholds with the n values that straddle them; tests/test_launch_geometry_cpu.py recomputes every
 threshold from the sources, so a changed cap fails there instead of silently un-testing a loop.  Every case here fills its outputs with NaN,
 keeps 64 NaN guard rows behind each output, asserts that the guards are untouched and every row below n written, and compares with an fp64

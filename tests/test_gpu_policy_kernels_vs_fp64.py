@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 W32 = 2 ** 32
 
 # (id, form, vehicle, task, waypoints, n, joints, axes, env_id_offset, seed, draw0, normaliser).  All batch sizes are ragged (not a
-# multiple of the workgroup's envs).  Instantiations (amenv_capi.hip amenv_rollout_policy / launch_rigid_policy_k / launch_lane_policy_k):
+# multiple of the workgroup's envs).  Instantiations (amenv_capi_policy.hip amenv_rollout_policy / launch_lane_policy_k, amenv_rigid_policy_host.hpp launch_rigid_policy_k):
 #   quad  <NROT>                    : rigid vehicle, v2, one waypoint, default workgroup size
 #   rigid <NROT,KW,VAR,NORM,NE>     : NE 16 up to 6144 envs, 64 up to 24576, 128 above
 #   team  <6,OCC>                   : 3-joint z,x,x arm, one waypoint, up to 6144 envs (the lane-team step family); OCC 2 above 4096

@@ -4,6 +4,7 @@ table from them, and asserts that each has a tested size at or below it and one 
 import os
 import re
 
+from rl_aerial_manipulator_amd.build import SOURCES
 from tests.test_gpu_launch_geometry import GEOMETRY
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rl-aerial-manipulator_amd", "csrc")
@@ -36,7 +37,8 @@ def _int(body, pattern, what):
 
 def thresholds_from_sources(csrc=CSRC):
     """{row: threshold} of every GEOMETRY row, from the sources under `csrc`."""
-    train, mlp, capi = _read(csrc, "amenv_train.hpp"), _read(csrc, "amenv_mlp_train.hpp"), _read(csrc, "amenv_capi.hip")
+    train, mlp = _read(csrc, "amenv_train.hpp"), _read(csrc, "amenv_mlp_train.hpp")
+    capi = "\n".join(_read(csrc, s) for s in SOURCES)   # the C-ABI entry points, whichever source holds them
     ppo_block, ppo_max = _const(train, "kPpoBlock"), _const(train, "kPpoMaxBlocks")
     adam_block, adam_max = _const(mlp, "kAdamBlock"), _const(mlp, "kAdamMaxBlocks")
     red_groups, mlp_max = _const(mlp, "kRedGroups"), _const(mlp, "kMlpMaxBlocks")

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
-"""Compare two device assembly files (hipcc --cuda-device-only -S, same flags) kernel by kernel.
+"""Compare two sets of device assembly files (hipcc --cuda-device-only -S, same flags) kernel by kernel.
 
-    python tools/asm_kernel_diff.py A.s B.s [--fold-bools N] [--list-same] > report.txt
+    python tools/asm_kernel_diff.py A B [--fold-bools N] [--list-same] > report.txt
+
+A and B are each one .s file, several joined by commas, or a directory (every .s in it: what build.dump_asm writes, one file per source
+of the library).  The kernels of a side's files are merged; a kernel name met twice on one side is an error (exit status 2): every kernel
+of the library is compiled in exactly one source.
 
 A kernel is its text from the entry label to the function's end label (instructions, local labels), its kernel descriptor, the
 compiler's occupancy comment and its entry in the amdhsa.kernels metadata (.kernarg_segment_size, every argument's offset and size,
@@ -22,6 +26,8 @@ body renames them in kernels whose instructions did not move.  Everything that i
 number of RES and the occupancy that is not listed is equal), the differing kernels in which none moved counted per kernel name, and with
 --list-same the identical kernels counted per kernel name."""
 import argparse
+import glob
+import os
 import re
 import subprocess
 import sys
@@ -101,6 +107,21 @@ def load(path, nfold, no_block_names=False):
     return kernels
 
 
+def load_side(spec, nfold, no_block_names=False):
+    """The merged kernels of one side: a file, files joined by commas, or a directory of .s files."""
+    paths = sorted(glob.glob(os.path.join(spec, "*.s"))) if os.path.isdir(spec) else spec.split(",")
+    if not paths:
+        sys.exit(f"no .s file in {spec}")
+    merged, origin = {}, {}
+    for p in paths:
+        for k, text in load(p, nfold, no_block_names).items():
+            if k in merged:
+                print(f"error: kernel compiled twice on one side: {k}\n  in {origin[k]}\n  and {p}")
+                sys.exit(2)
+            merged[k], origin[k] = text, p
+    return merged
+
+
 def numbers(text):
     meta = text[text.index("; metadata"):]
     got = {k: next((x.split()[-1] for x in meta if x.strip(" -").startswith("." + k + ":")), "?") for k in RES}
@@ -114,14 +135,14 @@ def resources(text):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("a")
-    ap.add_argument("b")
+    ap.add_argument("a", help="one .s file, several joined by commas, or a directory of them")
+    ap.add_argument("b", help="the same for the other side")
     ap.add_argument("--fold-bools", type=int, default=0, metavar="N")
     ap.add_argument("--list-same", action="store_true", help="also list the kernels that are identical, with their resource numbers")
     ap.add_argument("--no-block-names", action="store_true", help="ignore the IR block names in label comments (names of inlined functions)")
     ap.add_argument("--brief", action="store_true", help="one line per differing kernel; --list-same counts the identical ones per kernel name")
     a = ap.parse_args()
-    A, B = load(a.a, a.fold_bools, a.no_block_names), load(a.b, 0, a.no_block_names)
+    A, B = load_side(a.a, a.fold_bools, a.no_block_names), load_side(a.b, 0, a.no_block_names)
     both = sorted(set(A) & set(B))
     same = [k for k in both if A[k] == B[k]]
     diff = [k for k in both if A[k] != B[k]]

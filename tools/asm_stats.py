@@ -1,26 +1,24 @@
 #!/usr/bin/env python3
 """Instruction mix of the gfx950 kernels: hipcc -S the library and count per kernel.
-Usage: python tools/asm_stats.py [filter-substring] [--asm FILE]   (--asm: count an assembly file made before instead of compiling)"""
+Usage: python tools/asm_stats.py [filter-substring] [--asm FILE[,FILE..]]   (--asm: count assembly files made before instead of compiling)"""
 import collections
 import os
 import re
-import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rl_aerial_manipulator_amd.build as B
 
-out = "/tmp/amenv.s"
 if "--asm" in sys.argv:
     k = sys.argv.index("--asm")
-    out = sys.argv[k + 1]
+    outs = sys.argv[k + 1].split(",")
     del sys.argv[k:k + 2]
-else:   # the library's own flags (build.FLAGS), assembly instead of a shared object
-    subprocess.check_call([B.hipcc()] + [f for f in B.FLAGS if f not in ("-shared", "-fPIC", "-Wall")] +
-                          ["-S", "--cuda-device-only", "-Wno-unused-command-line-argument", "-o", out, "amenv_capi.hip"], cwd=B.CSRC)
+else:   # the library's own flags, assembly instead of objects: one file per source (build.dump_asm)
+    outs = B.dump_asm(os.path.join(tempfile.gettempdir(), "amenv_asm"))
 filt = sys.argv[1] if len(sys.argv) > 1 else "step_kernelIf"
-lines = open(out).read().split("\n")
+lines = [ln for out in outs for ln in open(out).read().split("\n")]
 starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if l.startswith("_ZN9amenv_dev") and ":" in l]
 for (i, name), nxt in zip(starts, starts[1:] + [(len(lines), "")]):
     if filt not in name:

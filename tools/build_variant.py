@@ -3,7 +3,6 @@
   python tools/build_variant.py stamps -DAMENV_STAMPS        -> tools/micro/libamenv_stamps.so  (use with AMENV_LIB=...)
   python tools/build_variant.py slp --drop=-fno-slp-vectorize -> the library with packed fp32 (SLP vectorisation) allowed"""
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +12,5 @@ name, extra = sys.argv[1], sys.argv[2:]
 drop = {"-Wall"} | {a[len("--drop="):] for a in extra if a.startswith("--drop=")}   # --drop=<flag>: remove one of the library's flags
 extra = [a for a in extra if not a.startswith("--drop=")]
 out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "micro", f"libamenv_{name}.so")
-cmd = [B.hipcc()] + [f for f in B.FLAGS if f not in drop] + extra + [os.path.join(B.CSRC, s) for s in B.SOURCES] + ["-o", out]
-subprocess.check_call(cmd, cwd=B.CSRC)
-print(out)
+# the library's own build (sources in parallel, one link), the variant's objects kept apart from the product's
+print(B.build(force=True, extra_flags=extra, drop_flags=drop, objdir=os.path.join(B.OBJDIR, "variant_" + name), lib=out))

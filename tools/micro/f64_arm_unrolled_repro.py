@@ -22,17 +22,34 @@ sys.path.insert(0, ROOT)
 
 
 def build():
-    csrc = os.path.join(ROOT, "rl-aerial-manipulator_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc", "-ffp-contract=off", "-fno-slp-vectorize",
-           "-DAMENV_F64_ARM_UNROLLED", "-Rpass-analysis=kernel-resource-usage", os.path.join(csrc, "amenv_capi.hip"), "-o", ALT]
-    r = subprocess.run(cmd, cwd=csrc, stderr=subprocess.PIPE, text=True)
-    want = None
-    for ln in r.stderr.splitlines():   # resource usage of the fp64 arm step kernel only
-        if "Function Name" in ln:
-            want = "step_kernelIdLi6ELi1ELi0ELi3" in ln
-        elif want and any(k in ln for k in ("VGPRs:", "AGPRs:", "ScratchSize", "Spill")):
+    # the library's own build with two more flags and objects of its own; the compilers' remarks (stderr of the sources compiled in
+    # parallel) go to one file
+    import tempfile
+
+    import rl_aerial_manipulator_amd.build as B
+    rc = 0
+    with tempfile.TemporaryFile("w+") as err:
+        saved = os.dup(2)
+        os.dup2(err.fileno(), 2)
+        try:
+            B.build(force=True, extra_flags=["-DAMENV_F64_ARM_UNROLLED", "-Rpass-analysis=kernel-resource-usage"], drop_flags=["-Wall"],
+                    objdir=os.path.join(B.OBJDIR, "variant_f64unrolled"), lib=ALT)
+        except subprocess.CalledProcessError as e:
+            rc = e.returncode
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        err.seek(0)
+        remarks = [ln for ln in err.read().splitlines() if " remark:" in ln]
+    want, where = None, None
+    for ln in remarks:   # resource usage of the fp64 arm step kernel only: its remarks share the location of its "Function Name" line
+        if "Function Name" in ln and "step_kernelIdLi6ELi1ELi0ELi3" in ln:
+            want, where = True, ln.split(" remark:")[0]
+        elif "Function Name" in ln and where and ln.startswith(where):
+            want = False
+        elif want and ln.startswith(where) and any(k in ln for k in ("VGPRs:", "AGPRs:", "ScratchSize", "Spill")):
             print(ln.split("remark:")[1].strip())
-    sys.exit(r.returncode)
+    sys.exit(rc)
 
 
 def child():

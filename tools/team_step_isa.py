@@ -11,7 +11,6 @@ its first; the last conditional scalar branch in front of that load is the role 
 runs to the end of the kernel.  Checked here: s_setprio (integrating waves only) lies on the integrating side, and nowhere else."""
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
@@ -23,9 +22,7 @@ args = sys.argv[1:]
 if args[:1] == ["--asm"]:
     asm = args[1]
 else:
-    asm = os.path.join(tempfile.gettempdir(), "amenv_team_step.s")
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC", "-Wall")]
-    subprocess.check_call([B.hipcc()] + flags + args + ["-S", "--cuda-device-only", "-Wno-unused-command-line-argument", "-o", asm, "amenv_capi.hip"], cwd=B.CSRC)
+    (asm,) = B.dump_asm(os.path.join(tempfile.gettempdir(), "amenv_team_step"), extra_flags=args, sources=["amenv_capi_step.hip"])   # the source of the step kernels
 lines = open(asm).read().split("\n")
 VLOAD = re.compile(r"^\s+(global_load|buffer_load|flat_load|scratch_load)_\w+")
 VSTORE = re.compile(r"^\s+(global_store|buffer_store|flat_store)_\w+")
