@@ -59,6 +59,9 @@ def main():
                     help="body-rate actions: entries 1..3 of an action are rate commands and a rate loop inside the step forms the moments (what a PX4 "
                          "offboard controller accepts).  No values: max_rate 5 5 2.5 rad/s, gain 25 25 10 1/s; or six: RX RY RZ GX GY GZ (fp32 rigid "
                          "vehicles; not with --warm-start-pid; DESIGN 4v)")
+    ap.add_argument("--rotor-failure", type=float, default=None, metavar="P",
+                    help="per-episode rotor failure: with probability P an episode loses one rotor (drawn per episode) at a control step drawn from "
+                         "50..400, which from then on delivers 0..50 %% of its thrust; not observed (rigid vehicles; pair it with --action-history; DESIGN 4y)")
     ap.add_argument("--target-kl", type=float, default=None, metavar="X",
                     help="SB3's target_kl: leave an update once a minibatch's approx_kl exceeds 1.5 X (decided on the GPU, no extra synchronisation; one rank only)")
     ap.add_argument("--lr-schedule", default="constant", choices=["constant", "linear", "adaptive"],
@@ -105,6 +108,8 @@ def main():
             e.set_action_history(amd.ActionHistory(a.action_history))
         if a.rate_control is not None:
             e.set_rate_control(amd.RateControl(a.rate_control[:3], a.rate_control[3:]) if a.rate_control else amd.RateControl())
+        if a.rotor_failure is not None:
+            e.set_rotor_failure(amd.RotorFailure(probability=a.rotor_failure, onset=(50, 400), remaining=(0.0, 0.5)))
         return e
 
     env = make_env(a.envs, a.seed, sh.env_id_offset, cfg)

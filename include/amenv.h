@@ -638,6 +638,42 @@ int amenv_set_rate_control(amenv* env, const amenv_rate_control* r);
  * control is off. */
 int amenv_rate_moment_actions(amenv* env, const float* actions, float* out, void* stream);
 
+/* ---- per-episode rotor failure -----------------------------------------------------------------------------------
+ * Opt-in, per handle, off by default; composes with randomisation, rotor lag, sensor noise, the action delay, the action history and
+ * rate control.  With `probability` an episode has ONE failure: one rotor, drawn among those of rotor_mask, delivers from control step
+ * `onset` of the episode on only the fraction f (`remaining`, 0 = a dead rotor) of what it would deliver.  The plan is a pure function of
+ * (seed, global env id, episode, these parameters), with no stored state: ONE Philox4x32-10 block, key = the config seed, counter
+ * (gid lo, gid hi, episode, 0x46410000), cut into 16-bit halves v0..v3 (low / high half of word 0, low / high half of word 1):
+ *   failure iff v0 < floor(probability * 65536 + 0.5)       (an integer compare: 0 never fails, 1 always)
+ *   rotor  = the k-th set bit of rotor_mask in ascending order, k = (v1 * popcount(rotor_mask)) >> 16
+ *   onset  = onset_min + ((v2 * (onset_max - onset_min + 1)) >> 16)
+ *   f      = remaining_min + (remaining_max - remaining_min) * (float(v3) * 2^-16)      (fp32: a multiply, then an add)
+ * In every control step whose step field, as the step finds it (istate[AMENV_I_STEP]), is >= onset, the failed rotor's thrust factor is
+ * s'_r = s_r * f (one rounded multiply in the handle's dtype), wherever the step uses s_r (amenv_set_randomization): F = sum s_r t_r,
+ * M = mixm (s . t), with the rotor lag on the delivered w'^2.  Commands still clamp at the nominal limits and the lag state keeps
+ * following the command.  Action scaling, reward, observation, reset draws, Monitor totals and the state layout are untouched; the failure
+ * is not observed.  The compare is on the loaded step, so amenv_set_state into the middle of an episode behaves as running up to that
+ * step; new parameters apply from the next launch, to running episodes too.
+ * Served: what amenv_set_randomization serves (rigid vehicles with 4 or 6 rotors, fp32 and fp64, lane and helper-wave step kernels,
+ * amenv_rollout, amenv_rollout_policy[_norm] and amenv_evaluate_policy in the one-lane-per-env form).  Refused with AMENV_ERR_INVALID, the
+ * handle untouched: arm vehicles, other rotor counts, a handle whose step kernel is the lane-quad one, a wrong struct_size, a probability
+ * that is not finite in 0..1, an onset range outside 0 <= min <= max <= 65535, a remaining range that is not finite with
+ * 0 <= min <= max <= 1, a rotor_mask bit at or above n_rotors.  A configuration call without allocation or launch. */
+typedef struct amenv_rotor_failure {
+  uint32_t struct_size;
+  float probability;                   /* chance that an episode has a failure */
+  int32_t onset_min, onset_max;        /* control step of the episode at which the rotor fails, inclusive */
+  float remaining_min, remaining_max;  /* fraction of its thrust the failed rotor still delivers */
+  uint32_t rotor_mask;                 /* bit r: rotor r may fail; 0 = all */
+} amenv_rotor_failure;
+/* f NULL = off: the handle launches exactly the kernels it launched before. */
+int amenv_set_rotor_failure(amenv* env, const amenv_rotor_failure* f);
+/* plan [N, 2] int32: the failed rotor (-1: this episode has none) and its onset step (0 with -1); factors [N, n_rotors] f32: the multiplier
+ * on s_r in effect for the NEXT step (f on the failed rotor once step >= onset, else 1.0), by the device functions the kernels inline.
+ * amenv_dynamics_factors keeps its meaning: the episode's km, kI, s_r, constant within an episode.  Either pointer may be NULL, not both
+ * (device memory).  Only enqueues.  Refused while the failure is off. */
+int amenv_rotor_failure_state(amenv* env, int32_t* plan, float* factors, void* stream);
+
 /* The part of SB3's PPO.train between the network outputs and the backward pass, fused (three launches instead of ~60 torch
  * kernels): per-minibatch advantage normalisation (mean, unbiased std, eps 1e-8), Gaussian log-prob of `actions` under
  * (mean, log_std), ratio to old_logp, clipped surrogate, value MSE, entropy bonus -- and the gradient of

@@ -13,6 +13,7 @@ from .gpu_env import GpuWaypointEnv
 from .randomization import DynamicsRandomization
 from .rotor_lag import RotorLag
 from .rate_control import RateControl
+from .rotor_failure import RotorFailure
 from .sensor_noise import SensorNoise
 from .action_delay import ActionDelay
 from .action_history import ActionHistory
@@ -23,4 +24,4 @@ from . import baselines, ppo
 from .baselines import MinSnapTrajectory, PidController, PidWaypointPolicy
 from .ppo import PPO, ActorCritic, KlAdaptiveLr, evaluate_policy, reduce_evaluation, clone_pid_policy
 
-__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "RateControl", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "RewardNormalizer", "PPO", "ActorCritic", "KlAdaptiveLr", "evaluate_policy", "reduce_evaluation", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]
+__all__ = ["GpuWaypointEnv", "DynamicsRandomization", "RotorLag", "SensorNoise", "ActionDelay", "ActionHistory", "RateControl", "RotorFailure", "GpuVecEnv", "GpuVecNormalize", "ObsNormalizer", "RewardNormalizer", "PPO", "ActorCritic", "KlAdaptiveLr", "evaluate_policy", "reduce_evaluation", "clone_pid_policy", "ppo", "baselines", "PidController", "MinSnapTrajectory", "PidWaypointPolicy", "vec_env", "AmenvError", "_lib", "sharding"]

@@ -90,6 +90,11 @@ class RateControlC(C.Structure):
     _fields_ = [("max_rate", C.c_double * 3), ("gain", C.c_double * 3), ("gyro_feedforward", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RotorFailureC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("probability", C.c_float), ("onset_min", C.c_int32), ("onset_max", C.c_int32),
+                ("remaining_min", C.c_float), ("remaining_max", C.c_float), ("rotor_mask", C.c_uint32)]
+
+
 class PpoCtl(C.Structure):
     """amenv_ppo_ctl: the device control block of a PPO update (include/amenv.h); this is the layout of the bytes read back from it."""
     _fields_ = [("struct_size", C.c_uint32), ("kl_limit", C.c_float), ("stop", C.c_uint32), ("stop_seen", C.c_uint32), ("evaluated", C.c_uint32),
@@ -132,6 +137,8 @@ SYMBOLS = {
     "amenv_obs_dim": (C.c_int32, [_P]),
     "amenv_set_rate_control": (C.c_int, [_P, C.POINTER(RateControlC)]),
     "amenv_rate_moment_actions": (C.c_int, [_P, _P, _P, _P]),
+    "amenv_set_rotor_failure": (C.c_int, [_P, C.POINTER(RotorFailureC)]),
+    "amenv_rotor_failure_state": (C.c_int, [_P, _P, _P, _P]),
     "amenv_reset": (C.c_int, [_P, _P, _P, _P]),
     "amenv_step": (C.c_int, [_P] * 10),
     "amenv_step_timed": (C.c_int, [_P] * 10 + [C.POINTER(C.c_float)]),

@@ -278,6 +278,7 @@ std::string kernel_name(const amenv& e) {
   if (e.delay) name += " +delay";
   if (e.hist) name += " +history " + std::to_string(e.hist);
   if (e.rate.on) name += " +rate";
+  if (e.fail.ctl) name += " +fail";
   if (e.pub_nj == 1 || e.pub_nj == 2) name += " [" + std::to_string(e.pub_nj) + "-joint arm: phantom links inside, pack / unpack at the C ABI]";
   return name;
 }
@@ -335,6 +336,26 @@ __global__ void rate_moment_kernel(int n, uint32_t tile_bytes, const void* __res
   float act[4] = {a.x, a.y, a.z, a.w};
   rate_to_moment(P, Q, w.a, w.b, w.c, act);
   out[i] = make_float4(act[0], act[1], act[2], act[3]);
+}
+
+// amenv_rotor_failure_state: plan [N][2] = the rotor (-1: none) and the onset of every env's current episode, factors [N][NROT] = the multiplier
+// on s_r in effect for the NEXT step (fail_draw and fail_hit: the kernels' own draw and compare, on a row of ones)
+template <int NROT>
+__global__ void fail_state_kernel(int n, uint32_t tile_bytes, const void* __restrict__ blob, const ColdParams C, const FailBlock X, int32_t* __restrict__ plan,
+                                  float* __restrict__ factors) {
+  const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int4 iv = *iptr4(const_cast<char*>(tile_base(blob, tile_bytes, i)), i & 63);   // {step, counter, flags, episode}
+  FailLane fl = fail_draw<NROT>(C, X, C.gid0 + i, iv.w);
+  if (plan) { plan[2 * size_t(i)] = fl.key >= 0 ? fl.key >> 16 : -1; plan[2 * size_t(i) + 1] = fl.key >= 0 ? fl.key & 0xffff : 0; }
+  float s[NROT];
+#pragma unroll
+  for (int r = 0; r < NROT; r++) s[r] = 1.0f;
+  fail_hit<float, NROT>(fl, iv.x, s);
+  if (factors) {
+#pragma unroll
+    for (int r = 0; r < NROT; r++) factors[size_t(i) * NROT + r] = s[r];
+  }
 }
 
 // amenv_sensor_noise_samples: [N][12] = the twelve unit samples of every env's current (episode, step) (noise_block: the kernels' own draw)
@@ -901,6 +922,50 @@ int amenv_rate_moment_actions(amenv* e, const float* actions, float* out, void* 
     constexpr int NROT = decltype(nrot)::value;
     hipLaunchKernelGGL(rate_moment_kernel<NROT>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, e->tile_bytes, (const void*)e->blob, make_hot<float, NROT>(*e), e->rate,
                        reinterpret_cast<const float4*>(actions), reinterpret_cast<float4*>(out));
+  });
+  AMENV_HIP(e, hipGetLastError());
+  return AMENV_OK;
+}
+
+int amenv_set_rotor_failure(amenv* e, const amenv_rotor_failure* f) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!f) {   // off: the handle launches the kernels it launched before
+    e->fail = FailBlock{0u, 0u, 0u, 0.0f, 0.0f};
+    return AMENV_OK;
+  }
+  if (f->struct_size != sizeof(amenv_rotor_failure)) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_failure: struct_size must be sizeof(amenv_rotor_failure)");
+  if (int rc = rigid_switch_served(e, "amenv_set_rotor_failure", false)) return rc;   // (fp64 too, as randomisation: the oracle gate runs there)
+  const int nr = e->cfg.vehicle.n_rotors;
+  if (!std::isfinite(f->probability) || !(f->probability >= 0.0f) || !(f->probability <= 1.0f))
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_failure: probability must be finite, 0..1");
+  if (f->onset_min < 0 || f->onset_min > f->onset_max || f->onset_max > 65535)
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_failure: onset must be a range of control steps with 0 <= min <= max <= 65535");
+  if (!std::isfinite(f->remaining_min) || !std::isfinite(f->remaining_max) || !(f->remaining_min >= 0.0f) || !(f->remaining_min <= f->remaining_max) || !(f->remaining_max <= 1.0f))
+    return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_failure: remaining must be finite with 0 <= min <= max <= 1");
+  const uint32_t all = (1u << nr) - 1u;
+  if (f->rotor_mask & ~all) return fail(e, AMENV_ERR_INVALID, "amenv_set_rotor_failure: rotor_mask has a bit at or above the vehicle's rotor count");
+  const uint32_t p16 = uint32_t(std::floor(double(f->probability) * 65536.0 + 0.5));   // 0: never, 65536: always (the draw's half is below 65536)
+  const uint32_t mask = f->rotor_mask ? f->rotor_mask : all;
+  FailBlock X;
+  X.ctl = 0x80000000u | uint32_t(__builtin_popcount(mask)) << 17 | p16;
+  X.rotors = 0u;
+  for (int r = 0, k = 0; r < nr; r++)
+    if ((mask >> r) & 1u) X.rotors |= uint32_t(r) << (4 * k++);   // the admissible rotors in ascending order
+  X.onset = uint32_t(f->onset_min) | uint32_t(f->onset_max - f->onset_min) << 16;
+  X.rem_lo = f->remaining_min; X.rem_span = f->remaining_max - f->remaining_min;
+  e->fail = X;
+  return AMENV_OK;
+}
+
+int amenv_rotor_failure_state(amenv* e, int32_t* plan, float* factors, void* stream) {
+  if (!e) return AMENV_ERR_INVALID;
+  if (!plan && !factors) return fail(e, AMENV_ERR_INVALID, "amenv_rotor_failure_state: NULL arguments");
+  if (!e->fail.ctl) return fail(e, AMENV_ERR_INVALID, "amenv_rotor_failure_state: the rotor failure is off (amenv_set_rotor_failure)");
+  DeviceGuard g(e->device);
+  const int n = e->cfg.num_envs;
+  with_rotors46(e->cfg.vehicle.n_rotors, [&](auto nrot) {
+    hipLaunchKernelGGL(fail_state_kernel<decltype(nrot)::value>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, e->tile_bytes, (const void*)e->blob, make_cold(*e), e->fail,
+                       plan, factors);
   });
   AMENV_HIP(e, hipGetLastError());
   return AMENV_OK;

@@ -50,12 +50,22 @@ hipError_t launch_step(const amenv& e, const StepIO& io, hipStream_t s, bool tim
     case StepFamily::LaneHelper:   // one tile per workgroup: main wave + reset-RNG wave (+ observation and Monitor waves for the single-waypoint v2 task)
       if constexpr (NJ == 0) {
         const size_t lds = size_t(64 * (ObsDim<VAR, 0>::value + ((DYN & kDynDelay) ? 8 : 0)) + 12 * 64) * sizeof(float);   // (the DELAY forms stage rows of up to two more action rows)
+        if constexpr (sizeof(T) == 8 && (DYN & kDynDr) != 0) {   // fp64 with the rotor failure set: the forms that carry its code (kDynFailForm)
+          if (e.fail.ctl != 0u)
+            return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, (DYN | kDynFailForm)>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n,
+                          io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DYN>(e));
+        }
         return launch(e, timed, step_kernel_pw<T, NROT, KW, VAR, DYN>, dim3(e.n_tiles), dim3((KW == 1 && VAR == VAR_V2) ? 256 : 128), lds, s, e.blob, tb, n, io.actions,
                       io.obs, io.reward, io.done, io.info, tl, P, C, make_dyn<T, NROT, DYN>(e));
       }
       break;
     case StepFamily::Lane: {
       const int bs = e.block;
+      if constexpr (sizeof(T) == 8 && (DYN & kDynDr) != 0) {   // (as above)
+        if (e.fail.ctl != 0u)
+          return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, (DYN | kDynFailForm)>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * ObsDim<VAR, NJ>::value * sizeof(float), s,
+                        e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DYN>(e));
+      }
       return launch(e, timed, step_kernel<T, NROT, KW, VAR, NJ, DYN>, dim3((e.n_tiles * 64 + bs - 1) / bs), dim3(bs), size_t(bs) * (ObsDim<VAR, NJ>::value + ((DYN & kDynDelay) ? 4 * e.hist : 0)) * sizeof(float), s,
                     e.blob, tb, n, io.actions, io.obs, io.reward, io.done, io.info, tl, P, C, AA, make_dyn<T, NROT, DYN>(e));
     }

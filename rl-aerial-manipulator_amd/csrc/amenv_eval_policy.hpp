@@ -95,6 +95,8 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
   __shared__ double md[NORM ? 2 * OD : 1];                                // entry statistics: mean | 1 / sqrt(var + eps)
   __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors (amenv_rigid_policy.hpp)
   constexpr bool kNoiseLds = NOISE && NORM;
+  constexpr bool kFailLds = DR && NORM;                                   // rotor failure: the NORM forms keep the lanes' plans in LDS
+  __shared__ int32_t fkl[kFailLds ? 2 * NE : 1];                          // [2][NE] words: key, f; each lane reads and writes its own column
   __shared__ float zl[kNoiseLds ? 13 * NE : 1];
   __shared__ int pend;                                                    // the exit protocol's word (policy_mlp_waves)
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
@@ -114,6 +116,7 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
   const int K = KW == 1 ? 1 : P.K;
   Env<float, KW> e;
   DynFac<float, NROT, DR> df;
+  FailLane fl{-1, 0.0f};                                          // rotor failure: the episode's plan, spent when the factor holds it
   float std_a[AD];
   float o[kObsDimMax];
   constexpr bool kHist = DELAY && !NORM;
@@ -146,6 +149,10 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
 #pragma unroll
       for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[lag_slot<NROT>(i) + r * 64];
       LagLds<NROT, NE, true>{wl + el, 0.0f, 0.0f}.put(dr_factors<float, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode));
+    }
+    if constexpr (DR) {
+      if (DA.R.x.ctl != 0u) fl = fail_draw<NROT>(C, DA.R.x, C.gid0 + i, e.episode);
+      if constexpr (kFailLds) fail_put<NE>(fkl + el, fl);
     }
     const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
 #pragma unroll
@@ -202,6 +209,9 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
         if constexpr (kHist) { hr.g0 = given; delay_apply(DA.D, i, dl, act, hr); } else delay_apply(DA.D, i, dl, act);
       }
       if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: behind the clipped action and the latency, in front of the step
+      if constexpr (kFailLds) fail_hit_lds<NROT, NE>(fkl + el, e.step, LAG ? nullptr : df.s, wl + el);   // rotor failure: the step field as this step finds it
+      else if constexpr (DR && LAG) fail_hit_scol<NROT, NE>(fl, e.step, wl + el);
+      else if constexpr (DR) fail_hit<float, NROT>(fl, e.step, df.s);
       float reward; bool was_reset; int ep_len; float ep_ret;
       LagLds<NROT, NE, LAG> lg;
       if constexpr (LAG) { lg.col = wl + el; lg.a_up = DA.L.a_up; lg.a_down = DA.L.a_down; }
@@ -218,6 +228,12 @@ __global__ __launch_bounds__(320) void evaluate_policy_kernel_rigid(void* __rest
 #pragma unroll
           for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[size_t(NROT) * DA.L.n_pad + r];
           lg.put(dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode));
+        }
+      }
+      if constexpr (DR) {
+        if (was_reset && DA.R.x.ctl != 0u) {   // the new episode's plan
+          const FailLane nf = fail_draw<NROT>(C, DA.R.x, gid, e.episode);
+          if constexpr (kFailLds) fail_put<NE>(fkl + el, nf); else fl = nf;
         }
       }
       if constexpr (DELAY) {

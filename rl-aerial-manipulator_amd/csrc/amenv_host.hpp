@@ -70,6 +70,7 @@ struct amenv {
   int hist = 0;                    // amenv_set_action_history: given action rows appended to every observation row, 0..2; > 0 runs the DELAY kernels
   float* hist_obs = nullptr;       // [N][obs_dim] the task's rows of amenv_reset / amenv_observe while the history is on, widened into the caller's buffer
   RateBlock rate = {0, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};   // amenv_set_rate_control: body-rate actions; on = 0: off
+  FailBlock fail = {0u, 0u, 0u, 0.0f, 0.0f};   // amenv_set_rotor_failure: per-episode rotor failure; ctl = 0: off
   bool delay_path() const { return delay || hist > 0; }   // the DELAY instantiations run: the latency, the history (range (0, 0) without the latency) or both
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // amenv_step_timed only
   std::string err;
@@ -220,7 +221,7 @@ DelayArg<true> make_delay(const amenv& e) {
 // noise's sigmas in the NOISE ones, behind those the actuation latency's fields in the DELAY ones
 template <typename T, int NROT, unsigned DYN> DynArg<T, NROT, DYN> make_dyn(const amenv& e) {
   DynArg<T, NROT, DYN> a;
-  if constexpr ((DYN & kDynDr) != 0) { a.R.r = e.dr_r; a.R.q = e.rate; } else a.R.unused = 0;
+  if constexpr ((DYN & kDynDr) != 0) { a.R.r = e.dr_r; a.R.q = e.rate; a.R.x = e.fail; } else a.R.unused = 0;
   if constexpr ((DYN & kDynLag) != 0) a.L = make_lag<T, NROT>(e);
   if constexpr ((DYN & kDynNoise) != 0) a.Z.s = e.noise_s;
   if constexpr ((DYN & kDynDelay) != 0) a.D = make_delay(e);
@@ -259,12 +260,12 @@ hipError_t launch(const amenv& e, bool timed, void (*k)(P...), dim3 grid, dim3 b
 }
 
 // The switch set a handle runs, for amenv_step, amenv_rollout and the closed-loop rollouts alike: the lag, the noise and the DELAY path, and DR with any
-// of them or with rate control, whose block travels with the ranges (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
+// of them, with rate control or with the rotor failure, whose blocks travel with the ranges (unit ranges when randomisation is off).  The setters admit rigid vehicles with 4 or 6 rotors only: every other handle runs the kernels without switches (a switch on such a handle, which no setter lets happen, would be dropped here, not refused).
 unsigned dyn_set(const amenv& e) {
   const int nr = e.cfg.vehicle.n_rotors;
   if (e.cfg.vehicle.n_joints > 0 || (nr != 4 && nr != 6)) return 0;
   const unsigned on = (e.lag ? kDynLag : 0) | (e.noise ? kDynNoise : 0) | (e.delay_path() ? kDynDelay : 0);
-  return on | (on || e.dr || e.rate.on ? kDynDr : 0);
+  return on | (on || e.dr || e.rate.on || e.fail.ctl ? kDynDr : 0);
 }
 template <auto V> using const_c = std::integral_constant<decltype(V), V>;
 // f(const_c<NROT>, const_c<DYN>) with DYN == dyn, over the sets that are built for T (dyn_admitted) and NROT (the general rotor count: no switch)

@@ -466,11 +466,14 @@ struct Head { void* blob; uint32_t tile_bytes; int32_t n; };
 // NOISE: sensor noise on the observation rows, built together with DR only, fp32 only.
 // DELAY: per-episode actuation latency, built together with DR only, fp32 only; the row given d steps ago is loaded from the
 // handle's side buffer in place of the given one, which enters the buffer after the step.
-template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYN = 0>
+template <typename T, int NROT, int KW, int VAR, int NJ, unsigned DYNF = 0>
 __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                    float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                    uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, DYN> DA) {
+                                                   const ArmArg<T, NJ> AA, const DynArg<T, NROT, (DYNF & kDynAll)> DA) {
+  constexpr unsigned DYN = DYNF & kDynAll;                                  // the switch set; kDynFailForm on top of it names a form (amenv_model.hpp)
+  constexpr bool FAIL = sizeof(T) == 4 || (DYNF & kDynFailForm) != 0;       // the rotor failure's code: every fp32 form, and the fp64 forms of their own
+  static_assert(DYNF <= kDynAll || (sizeof(T) == 8 && (DYN & kDynDr) != 0), "the failure's forms: fp64, with the randomisation's block");
   static_assert(dyn_admitted<T, NJ>(DYN), "a switch set that is not built (amenv_model.hpp)");
   constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, NJ>::value, AD = kActDim + NJ;
@@ -509,7 +512,7 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
   AMENV_STAMP(2);          // loads landed
   T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
   DynFac<T, NROT, DR> df;
-  if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+  if constexpr (DR) { df = dr_factors<T, NROT, FAIL>(P, C, DA.R.r, C.gid0 + i, e.episode); if constexpr (FAIL) fail_step<T, NROT>(C, DA.R.x, C.gid0 + i, e.episode, e.step, df); }   // (rotor failure: DESIGN 4y)
   uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io, tile, lane, false, was_reset,
                                                                       ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA), &hr);
   const bool is_done = active && (bits & (AMENV_INFO_TERMINATED | AMENV_INFO_TRUNCATED)) != 0;
@@ -584,11 +587,14 @@ __global__ __launch_bounds__(256) AMENV_STEP_WAVES_ATTR void step_kernel(void* _
 // DELAY: the waves that integrate load the same delayed row before the barrier; the main wave alone stores, after it.  In the
 // 256-thread form the reset wave draws the next episode's d for every lane and leaves it in LDS (no Philox on the main wave); in the
 // 128-thread form the main wave draws it on its episode-end path.
-template <typename T, int NROT, int KW, int VAR, unsigned DYN = 0>
+template <typename T, int NROT, int KW, int VAR, unsigned DYNF = 0>
 __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, const float4* __restrict__ actions,
                                                       float* __restrict__ obs, void* __restrict__ reward_out, uint8_t* __restrict__ done,
                                                       uint32_t* __restrict__ info, const StepTail tl, const HotParams<T, NROT> P, const ColdParams C,
-                                                      const DynArg<T, NROT, DYN> DA) {
+                                                      const DynArg<T, NROT, (DYNF & kDynAll)> DA) {
+  constexpr unsigned DYN = DYNF & kDynAll;                                  // the switch set; kDynFailForm on top of it names a form (amenv_model.hpp)
+  constexpr bool FAIL = sizeof(T) == 4 || (DYNF & kDynFailForm) != 0;       // the rotor failure's code: every fp32 form, and the fp64 forms of their own
+  static_assert(DYNF <= kDynAll || (sizeof(T) == 8 && (DYN & kDynDr) != 0), "the failure's forms: fp64, with the randomisation's block");
   static_assert(dyn_admitted<T, 0>(DYN), "a switch set that is not built (amenv_model.hpp)");
   constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
   constexpr int OD = ObsDim<VAR, 0>::value;
@@ -693,7 +699,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     const float4 a = io.actions[min(i, hd.n - 1)];
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     DynFac<T, NROT, DR> df;
-    if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    if constexpr (DR) { df = dr_factors<T, NROT, FAIL>(P, C, DA.R.r, C.gid0 + i, e.episode); if constexpr (FAIL) fail_step<T, NROT>(C, DA.R.x, C.gid0 + i, e.episode, e.step, df); }   // (rotor failure: DESIGN 4y)
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     DelayLane dl;
@@ -794,7 +800,7 @@ __global__ __launch_bounds__(256) void step_kernel_pw(void* __restrict__ blob, u
     act[0] = a.x; act[1] = a.y; act[2] = a.z; act[3] = a.w;
     const LdsXchg x{lds, lane, words};
     DynFac<T, NROT, DR> df;
-    if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    if constexpr (DR) { df = dr_factors<T, NROT, FAIL>(P, C, DA.R.r, C.gid0 + i, e.episode); if constexpr (FAIL) fail_step<T, NROT>(C, DA.R.x, C.gid0 + i, e.episode, e.step, df); }   // (rotor failure: DESIGN 4y)
     LagLane<T, NROT, LAG> lg;
     if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
     DelayLane dl;
@@ -1039,7 +1045,11 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
   Env<T, KW> e;
   load_env<T, KW, NJ>(K, tile, lane, e);
   DynFac<T, NROT, DR> df;
-  if constexpr (DR) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+  FailLane fl{-1, 0.0f};   // rotor failure: the episode's plan, drawn at entry and after an auto-reset; spent when the factor holds it
+  if constexpr (DR) {
+    df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    if (DA.R.x.ctl != 0u) fl = fail_draw<NROT>(C, DA.R.x, C.gid0 + i, e.episode);
+  }
   LagLane<T, NROT, LAG> lg;
   if constexpr (LAG) lag_load<T, NROT>(DA.L, i, lg);
   bool any_reset = false;
@@ -1060,10 +1070,16 @@ __global__ __launch_bounds__(256) void rollout_kernel(void* __restrict__ blob, u
         for (int j = 0; j < AD; j++) act[j] = ap[j];
       }
     }
+    if constexpr (DR) fail_hit<T, NROT>(fl, e.step, df.s);   // the step field as step t finds it
     T reward; float o[kObsDimMax]; bool was_reset; int ep_len; float ep_ret;
     uint32_t bits = step_lane<T, NROT, KW, VAR, NJ, 0, NoXchg, DR, LagLane<T, NROT, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, io_t, tile, lane, any_reset, was_reset,
                                                                         ep_len, ep_ret, NoXchg{}, df, &lg, noise_of(DA));
-    if constexpr (DR) { if (was_reset) df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode); }   // the new episode's vehicle
+    if constexpr (DR) {
+      if (was_reset) {   // the new episode's vehicle, and its plan
+        df = dr_factors<T, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+        if (DA.R.x.ctl != 0u) fl = fail_draw<NROT>(C, DA.R.x, C.gid0 + i, e.episode);
+      }
+    }
     if constexpr (LAG) { if (was_reset) lag_restart<T, NROT>(DA.L, lg); }
     if constexpr (DELAY) {
       if (was_reset) { dl.d = delay_draw(C.seed_lo, C.seed_hi, DA.D, C.gid0 + i, e.episode); hr.hover(); }

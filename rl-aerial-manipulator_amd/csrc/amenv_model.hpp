@@ -172,7 +172,18 @@ struct DrRanges { float lo[3], span[3]; };   // [0] mass, [1] inertia, [2] thrus
 // The block travels behind the ranges, so every kernel built with kDynDr receives it: no switch bit and no instantiation of its own.
 // on: 0 off, 1 the rate loop, 3 the rate loop with the gyroscopic feed-forward (wave-uniform: it sits in a scalar register).
 struct RateBlock { int32_t on; float max_rate[3], gain[3], inv_ms; };   // rad/s, 1/s, float(1 / moment_scale) formed on the host in fp64
-template <bool ON> struct DrArg { DrRanges r; RateBlock q; };
+// ---- per-episode rotor failure (include/amenv.h amenv_set_rotor_failure) ----------------------------------------------
+// The block travels behind the rate block, as that one behind the ranges: no switch bit and no instantiation of its own.  Five dwords, packed
+// on the host, because every kernel that carries them is at its scalar-register budget:
+//   ctl     0 = off (wave-uniform: a handle with randomisation but without the failure draws no second Philox block), else
+//           bit 31 | count << 17 | p16, with p16 = floor(probability * 65536 + 0.5) in 0..65536 and count the number of admissible rotors;
+//   rotors  the admissible rotors in ascending order, four bits each (entry k in bits 4 k ..): the k-th one is a shift and a mask on the
+//           lane's k, where a walk over a bit mask cost seven pairs of scalar registers for its lane masks;
+//   onset   lo | (hi - lo) << 16;   rem_lo, rem_span: the remaining fraction's lo and hi - lo, fp32.
+struct FailBlock { uint32_t ctl, rotors, onset; float rem_lo, rem_span; };
+static_assert(sizeof(DrRanges) == 24 && sizeof(RateBlock) == 32 && sizeof(FailBlock) == 20, "the blocks behind the ranges are packed dwords");
+template <bool ON> struct DrArg { DrRanges r; RateBlock q; FailBlock x; };
+static_assert(sizeof(DrArg<true>) == 76 && alignof(DrArg<true>) == 4, "ranges | rate block | failure block, no padding between them");
 template <> struct DrArg<false> { int unused; };
 // Per-lane factors of the lane's current episode, drawn once per launch (and again after an auto-reset inside a rollout); empty when off.
 // F = sum s_r t_r and M = mixm (s . t); translational acceleration F / (km m); rotational J (M / kI - w x I w).
@@ -241,6 +252,11 @@ struct NoHist { static constexpr bool on = false; };
 // ---- the switch set ---------------------------------------------------------------------------------------------
 // One template parameter names the opt-in features a kernel is built with: a mask of these bits.
 constexpr unsigned kDynDr = 1, kDynLag = 2, kDynNoise = 4, kDynDelay = 8, kDynAll = 15;
+// Not a switch: a FORM of a kernel, named on top of its switch set (template arguments 17u..31u; the kernel's argument stays the set's DynArg).
+// The kernels that cannot carry the rotor failure's code without scratch or spilled registers -- the closed loop's NORM forms, the fp64 step
+// kernels -- have instantiations of their own with it, which a handle runs only while the failure is set; their other forms hold none of its
+// code and draw the randomisation as before it, so that a handle without the failure pays nothing.
+constexpr unsigned kDynFailForm = 16;
 // The build rule, stated once: LAG, NOISE and DELAY are built only together with DR (unit ranges when randomisation is off); NOISE and
 // DELAY are fp32 only; every switch is built for rigid vehicles only.
 template <typename T, int NJ> constexpr bool dyn_admitted(unsigned dyn) {
@@ -644,10 +660,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t
 // A pure function of (seed, gid, episode, ranges): no state is stored, a change of ranges applies from the next launch.
 constexpr uint32_t kDrBlock = 0x44520000u;
 template <int NROT>
-__device__ __forceinline__ void dr_draw(const ColdParams& C, const DrRanges& R, int64_t gid, int32_t episode, float* f /*[2 + NROT]*/) {
+__device__ __forceinline__ void dr_draw_keyed(uint32_t k0, uint32_t k1, const DrRanges& R, int64_t gid, int32_t episode, float* f /*[2 + NROT]*/) {
   static_assert(NROT <= 6, "eight 16-bit uniforms per block: km, kI and up to six rotors");
   uint32_t w[4];
-  philox4x32_10(C.seed_lo, C.seed_hi, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), kDrBlock, w);
+  philox4x32_10(k0, k1, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), kDrBlock, w);
 #pragma unroll
   for (int k = 0; k < 2 + NROT; k++) {
     const uint32_t v = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
@@ -655,16 +671,102 @@ __device__ __forceinline__ void dr_draw(const ColdParams& C, const DrRanges& R, 
     f[k] = R.lo[q] + R.span[q] * (float(v) * 1.52587890625e-05f);
   }
 }
-template <typename T, int NROT>
+template <int NROT>
+__device__ __forceinline__ void dr_draw(const ColdParams& C, const DrRanges& R, int64_t gid, int32_t episode, float* f /*[2 + NROT]*/) {
+  dr_draw_keyed<NROT>(C.seed_lo, C.seed_hi, R, gid, episode, f);
+}
+// The key of a draw inside a step or rollout kernel goes through an empty asm.  Every Philox block of a kernel has the same key, and the
+// compiler would otherwise form the ten rounds' key words once, for this block, and keep all twenty alive for the reset path's blocks at the
+// kernel's far end -- in kernels that have no scalar register to spare, where they end up spilled to vector lanes.  Two scalar
+// adds per round buy them back.  (Read off the assembly of AMD clang 22.0.0git, ROCm 7.2.0, for gfx950: the values do not depend on it, the
+// register numbers may.  To re-check after a compiler change: build.dump_asm() of this tree and of one without the asm, then
+// tools/asm_kernel_diff.py A B --brief, and compare sgpr_spill_count of the step kernels.)
+__device__ __forceinline__ void philox_own_key(const ColdParams& C, uint32_t& k0, uint32_t& k1) {
+  k0 = C.seed_lo; k1 = C.seed_hi;
+  asm volatile("" : "+s"(k0), "+s"(k1));
+}
+// OWN_KEY = false: the forms without the rotor failure's code of the kernels that have forms of their own with it (kDynFailForm).
+template <typename T, int NROT, bool OWN_KEY = true>
 __device__ __forceinline__ DynFac<T, NROT, true> dr_factors(const HotParams<T, NROT>& P, const ColdParams& C, const DrRanges& R, int64_t gid, int32_t episode) {
   float f[2 + NROT];
-  dr_draw<NROT>(C, R, gid, episode, f);
+  uint32_t k0 = C.seed_lo, k1 = C.seed_hi;
+  if constexpr (OWN_KEY) philox_own_key(C, k0, k1);
+  dr_draw_keyed<NROT>(k0, k1, R, gid, episode, f);
   DynFac<T, NROT, true> d;
 #pragma unroll
   for (int r = 0; r < NROT; r++) d.s[r] = T(f[2 + r]);
   d.inv_mass = P.inv_mass * rcp_(T(f[0]));
   d.inv_ki = rcp_(T(f[1]));
   return d;
+}
+
+// ---- rotor failure: the plan of (env, episode) and its effect on the thrust factors ------------------------------------------
+// ONE Philox block, counter (gid, episode, kFailBlock); the top byte 0x46 is no other draw's (resets 0..4, randomisation 0x4452...., latency
+// 0x4C54...., noise 0x4E......).  The 16-bit halves v0..v3 are cut as dr_draw cuts them.  v0 < p16: the episode has a failure (an integer
+// compare: p16 = 0 never, p16 = 65536 always); v1 picks the k-th admissible rotor in ascending order, k = (v1 count) >> 16; v2 the onset step,
+// lo + ((v2 span) >> 16) with span = hi - lo + 1 <= 65536 (the product fits 32 bits); v3 the remaining fraction lo + span * (v3 2^-16) in fp32,
+// a multiply, then an add (dr_draw's arithmetic).  A pure function of (seed, gid, episode, block): no state is stored.
+constexpr uint32_t kFailBlock = 0x46410000u;
+// What a lane keeps of its plan: key = rotor << 16 | onset, or -1 (no failure in this episode, or the factor already holds it), and f.
+struct FailLane { int32_t key; float f; };
+template <int NROT>
+__device__ __forceinline__ FailLane fail_draw(const ColdParams& C, const FailBlock& X, int64_t gid, int32_t episode) {
+  uint32_t w[4];
+  uint32_t k0 = C.seed_lo, k1 = C.seed_hi;
+  asm volatile("" : "+v"(k0), "+v"(k1));   // a key of its own, as dr_factors', and in vector registers: the block sits behind a branch that costs the kernels no scalar register
+  philox4x32_10(k0, k1, uint32_t(uint64_t(gid)), uint32_t(uint64_t(gid) >> 32), uint32_t(episode), kFailBlock, w);
+  const uint32_t v0 = w[0] & 0xffffu, v1 = w[0] >> 16, v2 = w[1] & 0xffffu, v3 = w[1] >> 16;
+  const uint32_t p16 = X.ctl & 0x1ffffu, count = (X.ctl >> 17) & 7u;
+  const uint32_t rot = (X.rotors >> (((v1 * count) >> 16) << 2)) & 7u;
+  const uint32_t onset = (X.onset & 0xffffu) + ((v2 * ((X.onset >> 16) + 1u)) >> 16);
+  FailLane fl;
+  fl.key = v0 < p16 ? int((rot << 16) | onset) : -1;
+  fl.f = X.rem_lo + X.rem_span * (float(v3) * 1.52587890625e-05f);
+  return fl;
+}
+// From the control step whose loaded step field reaches the onset, the failed rotor delivers f of what it delivered: s'_r = s_r * T(f), ONE
+// rounded multiply, applied in place once; the key is spent with it.  A step kernel draws and tests once per launch; a rollout kernel draws at
+// entry and after an auto-reset and tests in front of every step, so both compare the same step field with >=.
+template <typename T, int NROT>
+__device__ __forceinline__ void fail_hit(FailLane& fl, int32_t step, T* s) {
+  if (fl.key >= 0 && step >= (fl.key & 0xffff)) {
+    const int rot = fl.key >> 16;
+    const T f = T(fl.f);
+#pragma unroll
+    for (int r = 0; r < NROT; r++) s[r] = r == rot ? s[r] * f : s[r];
+    fl.key = -1;
+  }
+}
+// The closed-loop kernel's NORM forms have no VGPR to spare: there the plan waits in an LDS column of the lane's own, [2][NE]
+// words (key, f; no barrier), and a step reads the key alone.  s: the factors in registers, or null where they sit in the LagLds column
+// `scol` (rows NROT.. hold s_r).
+template <int NE> __device__ __forceinline__ void fail_put(int32_t* col, const FailLane& fl) { col[0] = fl.key; col[NE] = __float_as_int(fl.f); }
+template <int NROT, int NE>
+__device__ __forceinline__ void fail_hit_lds(int32_t* col, int32_t step, float* s, float* scol) {
+  const int32_t key = col[0];
+  if (key >= 0 && step >= (key & 0xffff)) {
+    FailLane fl{key, __int_as_float(col[NE])};
+    if (s) fail_hit<float, NROT>(fl, step, s);
+    else { float* p = scol + (NROT + (key >> 16)) * NE; *p = *p * fl.f; }
+    col[0] = -1;
+  }
+}
+// the same for a plan in registers and factors in the LagLds column
+template <int NROT, int NE>
+__device__ __forceinline__ void fail_hit_scol(FailLane& fl, int32_t step, float* scol) {
+  if (fl.key >= 0 && step >= (fl.key & 0xffff)) {
+    float* p = scol + (NROT + (fl.key >> 16)) * NE;
+    *p = *p * fl.f;
+    fl.key = -1;
+  }
+}
+// The step kernels' call, behind dr_factors: everything sits behind the wave-uniform flag.
+template <typename T, int NROT>
+__device__ __forceinline__ void fail_step(const ColdParams& C, const FailBlock& X, int64_t gid, int32_t episode, int32_t step, DynFac<T, NROT, true>& df) {
+  if (X.ctl != 0u) {
+    FailLane fl = fail_draw<NROT>(C, X, gid, episode);
+    fail_hit<T, NROT>(fl, step, df.s);
+  }
 }
 
 // ---- body-rate actions: the inner rate loop ---------------------------------------------------------------------------

@@ -40,13 +40,21 @@ struct NormArg {
 // DELAY: per-episode actuation latency: the clipped sample is the GIVEN row; the row given d steps ago is applied.  Nothing of the
 // history is held in registers over a step: the env's word and one slot are loaded from the handle's (L2-resident) side buffer in front of
 // the dynamics, one slot and the word are stored behind them.  `actions` and `logp` record the policy's own samples.
-template <int NROT, int KW, int VAR, bool NORM, int NE, unsigned DYN = 0>
+// The rotor failure and the NORM forms: they sit at the vector-register limit and cannot carry a line more without scratch.  For
+// them the failure has instantiations of its own, named by kDynFailForm on top of the switch set (DYN = 17u..31u: a form of THIS kernel, not a
+// switch bit -- the argument is the set's DynArg), which a handle runs only while the failure is set; the forms every other handle runs
+// (DYN <= 15u) hold none of its code and draw the randomisation as before it.  Without the normaliser there is one form, which carries it.
+template <int NROT, int KW, int VAR, bool NORM, int NE, unsigned DYNF = 0>
 __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kernel_rigid(void* __restrict__ blob, uint32_t tile_bytes, int32_t n_envs, int n_steps,
                                                                                          const PolicyIO io, unsigned long long* __restrict__ stats,
                                                                                          const HotParams<float, NROT> P, const ColdParams C, const NormArg N,
-                                                                                         const DynArg<float, NROT, DYN> DA) {
+                                                                                         const DynArg<float, NROT, (DYNF & kDynAll)> DA) {
+  constexpr unsigned DYN = DYNF & kDynAll;
+  constexpr bool FAIL = !NORM || (DYNF & kDynFailForm) != 0;
+  static_assert(DYNF <= kDynAll || (NORM && (DYN & kDynDr) != 0), "the failure's forms: NORM, with the randomisation's block");
   static_assert(dyn_admitted<float, 0>(DYN), "a switch set that is not built (amenv_model.hpp)");
   constexpr bool DR = (DYN & kDynDr) != 0, LAG = (DYN & kDynLag) != 0, NOISE = (DYN & kDynNoise) != 0, DELAY = (DYN & kDynDelay) != 0;
+  constexpr bool kFail = DR && FAIL, kOwnKey = FAIL;                       // (without the failure's code the randomisation's draw is as it was, too)
   constexpr int OD = ObsDim<VAR, 0>::value, AD = 4, EW = NE < 64 ? 1 : NE / 64;   // env wavefronts per workgroup
   static_assert(NE == 16 || NE == 64 || NE == 128, "workgroup shapes");
   __shared__ __attribute__((aligned(16))) __bf16 xin[NE * kXS];
@@ -58,6 +66,8 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   __shared__ double md[NORM ? 2 * OD : 1];                                // entry statistics: mean | 1 / sqrt(var + eps)
   __shared__ float wl[LAG ? (2 * NROT + 2) * NE : 1];                     // rotor states | dynamics factors, [2 NROT + 2][NE]: each lane reads and writes its own column
   constexpr bool kNoiseLds = NOISE && NORM;
+  constexpr bool kFailLds = kFail && NORM;                                   // rotor failure: the NORM forms keep the lanes' plans in LDS
+  __shared__ int32_t fkl[kFailLds ? 2 * NE : 1];                          // [2][NE] words: key, f; each lane reads and writes its own column
   __shared__ float zl[kNoiseLds ? 13 * NE : 1];                           // sensor noise: the perturbed copy of the 13 state numbers, [13][NE]
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
   const int lane = int(threadIdx.x) & 63;
@@ -77,6 +87,7 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   const int K = KW == 1 ? 1 : P.K;
   Env<float, KW> e;
   DynFac<float, NROT, DR> df;
+  FailLane fl{-1, 0.0f};                                          // rotor failure: the episode's plan, spent when the factor holds it
   float std_a[AD], ls_a[AD];
   float o[kObsDimMax];
   double s1[NORM ? OD : 1], s2[NORM ? OD : 1];                    // fp64 column sums / sums of squares of this lane's raw rows 1..T
@@ -114,11 +125,15 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
   };
   if (mine) {
     load_env<float, KW, 0>(K, tile, tl, e);
-    if constexpr (DR && !LAG) df = dr_factors<float, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode);
+    if constexpr (DR && !LAG) df = dr_factors<float, NROT, kOwnKey>(P, C, DA.R.r, C.gid0 + i, e.episode);
     if constexpr (LAG) {
 #pragma unroll
       for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[lag_slot<NROT>(i) + r * 64];
-      LagLds<NROT, NE, true>{wl + el, 0.0f, 0.0f}.put(dr_factors<float, NROT>(P, C, DA.R.r, C.gid0 + i, e.episode));
+      LagLds<NROT, NE, true>{wl + el, 0.0f, 0.0f}.put(dr_factors<float, NROT, kOwnKey>(P, C, DA.R.r, C.gid0 + i, e.episode));
+    }
+    if constexpr (kFail) {
+      if (DA.R.x.ctl != 0u) fl = fail_draw<NROT>(C, DA.R.x, C.gid0 + i, e.episode);
+      if constexpr (kFailLds) fail_put<NE>(fkl + el, fl);
     }
     const uint4* ac = io.pack + size_t(4) * (kPolFrags + kPolBias) * 64;   // policy_pack_kernel's per-entry {std, log_std}
 #pragma unroll
@@ -179,6 +194,9 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
       if constexpr (kHist) { hr.g0 = given; delay_apply(DA.D, i, dl, act, hr); } else delay_apply(DA.D, i, dl, act);
     }
     if constexpr (DR) rate_apply(P, DA.R.q, e, act);   // body-rate actions: behind the clipped action and the latency, in front of the step
+    if constexpr (kFailLds) fail_hit_lds<NROT, NE>(fkl + el, e.step, LAG ? nullptr : df.s, wl + el);   // rotor failure: the step field as this step finds it
+    else if constexpr (kFail && LAG) fail_hit_scol<NROT, NE>(fl, e.step, wl + el);
+    else if constexpr (kFail) fail_hit<float, NROT>(fl, e.step, df.s);
     // ---- env step (amenv_step's lane kernel code); the terminal row is written raw by step_lane and normalised in place below
     sio.terminal_obs = io.terminal_obs ? io.terminal_obs + tn * W : nullptr;
     float reward; bool was_reset; int ep_len; float ep_ret;
@@ -191,12 +209,18 @@ __global__ __launch_bounds__(256 + (NE < 64 ? 64 : NE)) void rollout_policy_kern
     else
       bits = step_lane<float, NROT, KW, VAR, 0, 0, NoXchg, DR, LagLds<NROT, NE, LAG>, NoiseArg<NOISE>>(P, C, AA, e, act, i, active, reward, o, sio, tile, tl, any_reset, was_reset, ep_len,
                                                                                                       ep_ret, NoXchg{}, df, &lg, noise_of(DA), &hr);
-    if constexpr (DR && !LAG) { if (was_reset) df = dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode); }   // the new episode's vehicle
+    if constexpr (DR && !LAG) { if (was_reset) df = dr_factors<float, NROT, kOwnKey>(P, C, DA.R.r, gid, e.episode); }   // the new episode's vehicle
     if constexpr (LAG) {
       if (was_reset) {   // the new episode's rotors: w0 (behind the states in the side buffer), and the new episode's vehicle
 #pragma unroll
         for (int r = 0; r < NROT; r++) wl[r * NE + el] = DA.L.w[size_t(NROT) * DA.L.n_pad + r];
-        lg.put(dr_factors<float, NROT>(P, C, DA.R.r, gid, e.episode));
+        lg.put(dr_factors<float, NROT, kOwnKey>(P, C, DA.R.r, gid, e.episode));
+      }
+    }
+    if constexpr (kFail) {
+      if (was_reset && DA.R.x.ctl != 0u) {   // the new episode's plan
+        const FailLane nf = fail_draw<NROT>(C, DA.R.x, gid, e.episode);
+        if constexpr (kFailLds) fail_put<NE>(fkl + el, nf); else fl = nf;
       }
     }
     if constexpr (DELAY) {

@@ -23,6 +23,17 @@ hipError_t launch_rigid_policy_k(const amenv& e, int T, const PolicyIO& io, cons
   const ColdParams C = make_cold(e);
   const DynArg<float, NROT, DYN> R = make_dyn<float, NROT, DYN>(e);
   const int n = e.cfg.num_envs;
+  if constexpr (NORM && (DYN & kDynDr) != 0) {
+    if (e.fail.ctl != 0u) {   // the rotor failure inside the normaliser forms: instantiations of its own (amenv_rigid_policy.hpp, kDynFailForm)
+      if (n <= AMENV_RIGID_WG16_MAX)
+        hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, true, 16, (DYN | kDynFailForm)>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+      else if (n <= AMENV_RIGID_WG64_MAX)
+        hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, true, 64, (DYN | kDynFailForm)>), dim3(e.n_tiles), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+      else
+        hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, true, 128, (DYN | kDynFailForm)>), dim3(e.n_tiles / 2), dim3(384), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
+      return hipGetLastError();
+    }
+  }
   if (n <= AMENV_RIGID_WG16_MAX)
     hipLaunchKernelGGL((rollout_policy_kernel_rigid<NROT, KW, VAR, NORM, 16, DYN>), dim3(e.n_tiles * 4), dim3(320), 0, s, e.blob, e.tile_bytes, n, T, io, e.stats, HP, C, N, R);
   else if (n <= AMENV_RIGID_WG64_MAX)

@@ -14,13 +14,15 @@ from .action_delay import ActionDelay
 from .action_history import ActionHistory
 from .randomization import DynamicsRandomization
 from .rate_control import RateControl
+from .rotor_failure import RotorFailure
 from .rotor_lag import RotorLag
 from .sensor_noise import SensorNoise
 
 # The opt-in switches, in the order the constructor applies them: keyword = attribute = the <name> of set_<name> and amenv_set_<name> ->
 # (class, the method that gives its C struct; the history's argument is its row count)
 _SWITCHES = {"randomization": (DynamicsRandomization, "to_c"), "rotor_lag": (RotorLag, "to_c"), "sensor_noise": (SensorNoise, "to_c"),
-             "action_delay": (ActionDelay, "_as_c"), "action_history": (ActionHistory, None), "rate_control": (RateControl, "to_c")}
+             "action_delay": (ActionDelay, "_as_c"), "action_history": (ActionHistory, None), "rate_control": (RateControl, "to_c"),
+             "rotor_failure": (RotorFailure, "to_c")}
 
 
 def _typed(who, x, cls):
@@ -49,9 +51,9 @@ class GpuWaypointEnv:
     def __init__(self, num_envs, device=0, vehicle="quad", seed=0, dtype="f32", auto_reset=True, nan_guard=False,
                  num_waypoints=1, env_id_offset=0, block_size=0, max_episode_steps=None, counter_limit=None,
                  rk4_substeps=1, task="v2", config=None, kernel="auto", ee_task=None, n_joints=None, randomization=None, rotor_lag=None,
-                 sensor_noise=None, action_delay=None, action_history=None, rate_control=None):
+                 sensor_noise=None, action_delay=None, action_history=None, rate_control=None, rotor_failure=None):
         switches = {"randomization": randomization, "rotor_lag": rotor_lag, "sensor_noise": sensor_noise, "action_delay": action_delay,
-                    "action_history": action_history, "rate_control": rate_control}
+                    "action_history": action_history, "rate_control": rate_control, "rotor_failure": rotor_failure}
         for name, x in switches.items():   # before any device is touched
             _typed(name, x, _SWITCHES[name][0])
         self.lib = L.load()
@@ -225,6 +227,26 @@ class GpuWaypointEnv:
         self._check(self.lib.amenv_rate_moment_actions(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
                     "amenv_rate_moment_actions")
         return out
+
+    def set_rotor_failure(self, failure):
+        """Per-episode rotor failure (a `RotorFailure`, or None = every rotor delivers its factor for the whole episode; rigid vehicles with
+        4 or 6 rotors, not with kernel="team").  With its probability an episode has one failure: from the drawn onset step on, the drawn
+        rotor delivers only the drawn fraction of its thrust.  A pure function of (seed, env id, episode, parameters): nothing is stored,
+        new parameters apply from the next launch, to the episodes already running too.  The failure is not observed."""
+        _typed("set_rotor_failure", failure, RotorFailure)
+        if failure is not None:
+            failure.validate(self.n_rotors)
+        self._set_switch("rotor_failure", failure)
+
+    def rotor_failure_state(self):
+        """(plan [N, 2] int32, factors [N, n_rotors] f32): every env's failed rotor (-1: its current episode has none) and onset step, and
+        the multiplier on each rotor's thrust factor in effect for the NEXT step (the remaining fraction on the failed rotor once the env's
+        step has reached the onset, else 1), by the kernels' own device functions.  Needs the rotor failure on."""
+        plan = torch.empty(self.num_envs, 2, dtype=torch.int32, device=self.device)
+        factors = torch.empty(self.num_envs, self.n_rotors, dtype=torch.float32, device=self.device)
+        self._check(self.lib.amenv_rotor_failure_state(self._h, C.c_void_p(plan.data_ptr()), C.c_void_p(factors.data_ptr()), self._stream()),
+                    "amenv_rotor_failure_state")
+        return plan, factors
 
     def action_delay_state(self):
         """(d [N] int32, recent [N, 8, 4] f32): every env's delay and the last 8 action rows it was given, in age order (recent[:, k] was
